@@ -23,6 +23,15 @@ value_device_resident times the same steps without the copy.
 
 With --gpus N and no WORLD_SIZE in the environment, bench.py starts itself
 under torch.distributed.run with N ranks (one per GPU) before touching the GPU.
+
+A plain run does what the headline needs and no more: it plans and uploads the
+batch, warms up, times --steps steps, writes the outputs of the last timed step
+if --dump-outputs DIR is given, and prints the result line. --full adds every
+other measurement and check, each in runs of its own after the timed steps:
+value_device_resident (--device-steps), the per-kernel HIP-event roofline
+(--steps more executes with profiling on, so S + W + S executes in all), the RMS
+check against the oracle (--rms-calls), the CPU baseline (--cpu-budget) and, at
+N > 1, the timed gather to rank 0.
 """
 import argparse
 import ctypes as C
@@ -249,6 +258,48 @@ def rms_check(plans, out, calls, n_check):
             "tolerance": 1e-5, "within_tolerance": int(sum(e <= 1e-5 for e in errs))}
 
 
+DUMP_WAVE_BYTES = 32 << 20   # --dump-outputs: whole waveforms of a seeded sample of calls
+DUMP_POINTS = 1 << 20        # ... and single samples at seeded positions over every call
+
+
+def dump_outputs(dirpath, fetch, itemsize, offs, lens, ids, suffix=""):
+    """--dump-outputs: what the timed path delivered in its last step, as .npy files
+    (under 50 MB in all). `offs` / `lens`: where each call's waveform lies in the
+    output buffer the caller receives (length 0: not synthesized); `ids`: the calls'
+    indices in the whole batch; fetch(pos) returns the buffer's values at the int64
+    positions `pos`. The sample is drawn from PCG64(SEED + 77), so it is the same for
+    the same arguments:
+      lengths.npy         float64 (calls,)     samples of every call, in batch order of `ids`
+      waveform_calls.npy  float64 (k, 2)       (batch index, length) of the k sampled calls
+      waveforms.npy       float32/64           their whole waveforms, one after the other
+      point_index.npy     float64 (m,)         m sorted positions in the concatenation of
+                                               every call's waveform (in the order of `ids`)
+      points.npy          float32/64 (m,)      the output samples at those positions"""
+    os.makedirs(dirpath, exist_ok=True)
+    offs, lens, ids = (np.asarray(x, dtype=np.int64) for x in (offs, lens, ids))
+    rng = _rng(77)
+    order = rng.permutation(len(lens))
+    k = int(np.searchsorted(np.cumsum(lens[order]), DUMP_WAVE_BYTES // itemsize, side="right"))
+    pick = np.sort(order[:k])
+    pick = pick[lens[pick] > 0]
+    n = int(lens[pick].sum())
+    start = np.cumsum(lens[pick]) - lens[pick]
+    pos = np.repeat(offs[pick] - start, lens[pick]) + np.arange(n, dtype=np.int64)
+    total = int(lens.sum())
+    end = np.cumsum(lens)
+    q = np.sort(rng.integers(0, max(total, 1), size=min(total, DUMP_POINTS)))
+    j = np.searchsorted(end, q, side="right")
+    qpos = offs[j] + q - (end[j] - lens[j])
+
+    def save(name, a):
+        np.save(os.path.join(dirpath, name + suffix + ".npy"), a)
+    save("lengths", lens.astype(np.float64))
+    save("waveform_calls", np.stack([ids[pick], lens[pick]], axis=1).astype(np.float64))
+    save("waveforms", fetch(pos))
+    save("point_index", q.astype(np.float64))
+    save("points", fetch(qpos))
+
+
 def traffic_from_profiles(config, kernels, launches_per_step):
     """HBM bytes per launch of the kernel group `kernels` (one launch of each per
     plan) from the committed rocprofv3 PMC summary of this workload
@@ -449,8 +500,11 @@ def node_bench(args):
     dt = time.perf_counter() - t
     samples = int(plan.lengths[plan.status == 0].sum())
     failed = int((plan.status != 0).sum())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, lambda pos: host[pos], host.itemsize, plan.offsets,
+                     np.where(plan.status == 0, plan.lengths, 0), np.arange(n_calls))
     rms = None
-    if args.rms_calls > 0:  # the timed outputs against the oracle, calls spread over the batch
+    if args.full and args.rms_calls > 0:  # the timed outputs against the oracle, calls spread over the batch
         from concurrent.futures import ThreadPoolExecutor
         from oracle import oracle as O
         O.lib()
@@ -484,11 +538,49 @@ def node_bench(args):
     return 0
 
 
+def full_results(res, args, plans, prof, out, calls, samples_all, dt_dev, world):
+    """--full: the fields beside the headline (device-resident value, RMS check against the
+    oracle, rooflines of the profiled kernel groups, CPU baseline), added to `res`."""
+    st = {}
+    for p, _, _ in plans:
+        for k, v in p.stats().items():
+            st[k] = st.get(k, 0) + v
+        # task descriptors per class (128 B each, read once by their class kernel)
+        for k, v in zip(("tasks_long", "tasks_short", "tasks_tall", "tasks_tallp", "tasks_hp"), p.sine_tasks()):
+            st[k] = st.get(k, 0) + v
+        tabs, tab_samples, tab_terms = p.table_stats()  # wavetable spans (no row recurrence)
+        st["tab_spans"] = st.get("tab_spans", 0) + tabs
+        st["tab_samples"] = st.get("tab_samples", 0) + tab_samples
+        st["tab_terms"] = st.get("tab_terms", 0) + tab_terms
+    tot = {k: v[0] * v[1] for k, v in prof.items()}
+    dom = max(tot, key=tot.get) if any(tot.values()) else "sg_sine_bank"
+    roof = roofline(st, prof, args.steps, args.config, dom)
+    other = [k for k in prof if k != dom and prof[k][1] > 0]
+    rms = rms_check(plans, out, calls, args.rms_calls)
+    res["value_device_resident"] = (samples_all * args.device_steps / dt_dev) if dt_dev else None
+    res["ms_per_step_device_resident"] = (dt_dev / args.device_steps * 1e3) if dt_dev else None
+    res["rms_error_vs_oracle"] = rms["max"] if rms else None
+    res["rms_check"] = rms
+    res["roofline"] = roof
+    for k in other:  # the other profiled kernel group (C5: the sine-bank classes)
+        res["roofline_" + ("sine_bank" if k == "sg_sine_bank" else "stft_ola")] = \
+            roofline(st, prof, args.steps, args.config, k)
+    if not args.no_cpu_baseline and world == 1:  # the CPU leg runs at N=1 only
+        res["cpu_baseline"] = cpu_baseline(calls, args.cpu_budget)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beside the headline: "
+                         "--device-steps, the per-kernel roofline, --rms-calls against the oracle, the CPU "
+                         "baseline, the gather at N > 1 (a plain run does none of these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step delivered as DIR/<name>.npy (a fixed, seeded sample "
+                         "of the waveforms; see dump_outputs)")
     ap.add_argument("--config", default="c5", choices=sorted(CONFIGS))
     ap.add_argument("--calls", type=int, default=0, help="calls in the whole batch (default: the config's)")
     ap.add_argument("--plan-chunk", type=int, default=16384,
@@ -498,19 +590,21 @@ def main():
     ap.add_argument("--no-d2h", action="store_true",
                     help="profiling runs only: the timed steps leave the outputs in HBM (no copy kernels beside them)")
     ap.add_argument("--device-steps", type=int, default=5,
-                    help="extra steps timed with the outputs left in HBM (value_device_resident; 0: skip)")
-    ap.add_argument("--cpu-budget", type=float, default=16.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: extra steps timed with the outputs left in HBM (value_device_resident; 0: skip)")
+    ap.add_argument("--cpu-budget", type=float, default=16.0, help="--full: seconds for the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-gather", action="store_true",
-                    help="N>1: skip the timed gather of every rank's packed output to rank 0 after the timed steps")
+                    help="--full, N>1: skip the timed gather of every rank's packed output to rank 0 after the timed steps")
     ap.add_argument("--rms-calls", type=int, default=66,
-                    help="calls checked against the oracle after timing, spread over every plan")
+                    help="--full: calls checked against the oracle after timing, spread over every plan")
     ap.add_argument("--node", action="store_true",
                     help="the whole-node C-ABI path R reaches (sg_node_*): one process, --node-devices, "
                          "the batch planned once and executed into a caller's (pageable) host buffer")
     ap.add_argument("--node-devices", default="0", help="--node: comma-separated device ordinals")
     ap.add_argument("--node-f64", action="store_true", help="--node: into doubles (R's numeric vectors)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.node:
         return node_bench(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -613,23 +707,39 @@ def main():
         main_step()
     torch.cuda.synchronize(dev)
     dt = timed(main_step, args.steps)  # the headline: host-resident
+    if args.dump_outputs:
+        # the last timed step's outputs where that step left them: the pinned host buffer,
+        # or (--no-d2h) the device buffer
+        if args.no_d2h:
+            def fetch(pos):
+                return out[torch.from_numpy(pos).to(dev)].cpu().numpy()
+        else:
+            def fetch(pos):
+                return host.numpy()[pos]
+        dump_outputs(args.dump_outputs, fetch, 4,
+                     np.concatenate([b + p.offsets for p, b, _ in plans]),
+                     np.concatenate([np.where(p.status == 0, p.lengths, 0) for p, _, _ in plans]),
+                     np.concatenate([ix for _, _, ix in plans]), ".rank%d" % rank if world > 1 else "")
+    if not args.full:
+        args.device_steps = 0
     # the same steps with the outputs left in HBM (no D2H copy)
     dt_dev = timed(step, args.device_steps) if args.device_steps > 0 else None
-    L = native.lib()
-    # per-kernel HIP events (roofline) over the same number of extra steps, outside the
-    # timed region: with profiling on, the harmonic chain and the noise phase run one
-    # after the other, so each launch's duration is its own, not shared with a
-    # concurrent kernel
-    L.sg_set_profiling(ctx.ptr, 1)
-    for _ in range(args.steps):
-        step()
-    torch.cuda.synchronize(dev)
-    L.sg_set_profiling(ctx.ptr, 0)
     prof = {}
-    for kid, name in ((0, "sg_sine_bank"), (1, "sg_stft_ola")):
-        ms, n = C.c_double(), C.c_int64()
-        native.check(L.sg_profile_read_kernel(ctx.ptr, kid, C.byref(ms), C.byref(n)), ctx.ptr)
-        prof[name] = (ms.value, n.value)
+    if args.full:
+        L = native.lib()
+        # per-kernel HIP events (roofline) over the same number of extra steps, outside the
+        # timed region: with profiling on, the harmonic chain and the noise phase run one
+        # after the other, so each launch's duration is its own, not shared with a
+        # concurrent kernel
+        L.sg_set_profiling(ctx.ptr, 1)
+        for _ in range(args.steps):
+            step()
+        torch.cuda.synchronize(dev)
+        L.sg_set_profiling(ctx.ptr, 0)
+        for kid, name in ((0, "sg_sine_bank"), (1, "sg_stft_ola")):
+            ms, n = C.c_double(), C.c_int64()
+            native.check(L.sg_profile_read_kernel(ctx.ptr, kid, C.byref(ms), C.byref(n)), ctx.ptr)
+            prof[name] = (ms.value, n.value)
     del host
 
     samples_rank = int(sum(int(p.lengths.sum()) for p, _, _ in plans))  # synthesized samples (padding excluded)
@@ -647,7 +757,7 @@ def main():
     value = samples_all * args.steps / dt
 
     gather_ms = gather_error = None
-    if dist and not args.no_gather:
+    if dist and args.full and not args.no_gather:
         # SURVEY §8e exchange step, after the timed steps: every peer sends its packed
         # output and (offset, length) table to rank 0 (dist.gather_packed: one RCCL
         # point-to-point transfer per peer, each on its own xGMI link). Not part of
@@ -670,22 +780,6 @@ def main():
             gather_ms = None
 
     if rank == 0:
-        st = {}
-        for p, _, _ in plans:
-            for k, v in p.stats().items():
-                st[k] = st.get(k, 0) + v
-            # task descriptors per class (128 B each, read once by their class kernel)
-            for k, v in zip(("tasks_long", "tasks_short", "tasks_tall", "tasks_tallp", "tasks_hp"), p.sine_tasks()):
-                st[k] = st.get(k, 0) + v
-            tabs, tab_samples, tab_terms = p.table_stats()  # wavetable spans (no row recurrence)
-            st["tab_spans"] = st.get("tab_spans", 0) + tabs
-            st["tab_samples"] = st.get("tab_samples", 0) + tab_samples
-            st["tab_terms"] = st.get("tab_terms", 0) + tab_terms
-        tot = {k: v[0] * v[1] for k, v in prof.items()}
-        dom = max(tot, key=tot.get) if any(tot.values()) else "sg_sine_bank"
-        roof = roofline(st, prof, args.steps, args.config, dom)
-        other = [k for k in prof if k != dom and prof[k][1] > 0]
-        rms = rms_check(plans, out, calls, args.rms_calls)
         res = {
             "metric": METRIC, "value": value, "unit": "samples/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
@@ -697,26 +791,21 @@ def main():
                        "plans_per_rank": len(plans), "failed_calls": failed_all},
             "timing": ("outputs left in HBM (--no-d2h profiling run)" if args.no_d2h else
                        "sg_execute entry to waveforms resident in pinned host memory (SURVEY 8d)"),
-            "value_device_resident": (samples_all * args.device_steps / dt_dev) if dt_dev else None,
-            "ms_per_step_device_resident": (dt_dev / args.device_steps * 1e3) if dt_dev else None,
+            "full": args.full,
             "plan_s": t_plan_max, "calls_gen_s": t_gen,
             "plan_stages": [{k: (round(v, 3) if isinstance(v, float) else v) for k, v in t.items()} for t in plan_stages],
             "value_incl_planning": samples_all / (t_plan_max + dt / args.steps),
-            "rms_error_vs_oracle": rms["max"] if rms else None,
-            "rms_check": rms,
-            "roofline": roof,
         }
-        for k in other:  # the other profiled kernel group (C5: the sine-bank classes)
-            res["roofline_" + ("sine_bank" if k == "sg_sine_bank" else "stft_ola")] = \
-                roofline(st, prof, args.steps, args.config, k)
-        if dist and not args.no_gather:
-            res["gather_ms"] = gather_ms
-            res["gather"] = ("every rank's packed outputs sent to rank 0 over RCCL point-to-point after the timed "
-                             "steps (dist.gather_timed); not part of value (DESIGN.md §7)")
-            if gather_error:
-                res["gather_error"] = gather_error
-        if not args.no_cpu_baseline and world == 1:  # the CPU leg runs at N=1 only
-            res["cpu_baseline"] = cpu_baseline(calls, args.cpu_budget)
+        if args.dump_outputs:
+            res["outputs_dumped_to"] = args.dump_outputs
+        if args.full:
+            full_results(res, args, plans, prof, out, calls, samples_all, dt_dev, world)
+            if dist and not args.no_gather:
+                res["gather_ms"] = gather_ms
+                res["gather"] = ("every rank's packed outputs sent to rank 0 over RCCL point-to-point after the "
+                                 "timed steps (dist.gather_timed); not part of value (DESIGN.md §7)")
+                if gather_error:
+                    res["gather_error"] = gather_error
         print(json.dumps(res), flush=True)
     for p, _, _ in plans:
         p.close()

@@ -6,16 +6,17 @@
 #   VARIANTS="r05" KERNELS="sg_stft_ola sg_stft_ola_noise" bash tools/gpu_lds_ab.sh TAG
 set -e
 R=${GRAFT_REPO_ROOT:-$(pwd)}
+OUT=${SG_OUT:-$R/bench_out}  # where logs and result lines go
 TAG=${1:-lds}
-mkdir -p "$R/gpurun_out"
+mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
 G="SQ_WAVE_CYCLES SQ_BUSY_CU_CYCLES SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_UNALIGNED_STALL SQ_ACTIVE_INST_LDS SQ_INSTS_VALU"
 for v in default ${VARIANTS}; do
   if [ "$v" = default ]; then unset SG_HIP_LIB; else export SG_HIP_LIB=$R/soundgen_beta_amd/lib/exp_$v.so; fi
-  SG_OVERLAP=0 timeout -s KILL 240 rocprofv3 --pmc $G --output-format csv -d "$R/gpurun_out/${TAG}_${v}_lds_1" -o run -- python3 "$R/bench.py" --config ${CFG:-c5} --steps 1 --warmup 0 --device-steps 0 --no-d2h --no-cpu-baseline --rms-calls 0 > "$R/gpurun_out/${TAG}_${v}_lds.log" 2>&1 || { tail -20 "$R/gpurun_out/${TAG}_${v}_lds.log"; exit 1; }
-  (cd "$R" && python3 tools/pmc_summary.py ${TAG}_${v}_lds ${CFG:-c5} > gpurun_out/${TAG}_${v}_lds.json)
-  python3 - "$R/gpurun_out/${TAG}_${v}_lds.json" "$v" ${KERNELS:-sg_stft_ola sg_stft_ola_noise} <<'EOF'
+  SG_OVERLAP=0 timeout -s KILL 240 rocprofv3 --pmc $G --output-format csv -d "$OUT/${TAG}_${v}_lds_1" -o run -- python3 "$R/bench.py" --full --config ${CFG:-c5} --steps 1 --warmup 0 --device-steps 0 --no-d2h --no-cpu-baseline --rms-calls 0 > "$OUT/${TAG}_${v}_lds.log" 2>&1 || { tail -20 "$OUT/${TAG}_${v}_lds.log"; exit 1; }
+  (cd "$R" && python3 tools/pmc_summary.py ${TAG}_${v}_lds ${CFG:-c5} > $OUT/${TAG}_${v}_lds.json)
+  python3 - "$OUT/${TAG}_${v}_lds.json" "$v" ${KERNELS:-sg_stft_ola sg_stft_ola_noise} <<'EOF'
 import json, sys
 d = json.load(open(sys.argv[1]))["kernels"]
 for k in sys.argv[3:]:

@@ -1,6 +1,6 @@
 """Per-wave instruction mix per kernel from a tools/gpu_imix.sh summary (pmc_summary
 JSON): each counter summed over the kernel's launches, divided by SQ_WAVES.
-    python tools/imix_summary.py gpurun_out/TAG_CFG_imix.json [kernel ...]
+    python tools/imix_summary.py TAG_CFG_imix.json [kernel ...]
 """
 import json
 import sys

@@ -8,12 +8,14 @@ import collections
 import csv
 import glob
 import json
+import os
 import sys
 
 tag = sys.argv[1]
 acc = collections.defaultdict(lambda: collections.defaultdict(list))
 passes = 0
-for path in sorted(glob.glob("gpurun_out/%s_*/run_counter_collection.csv" % tag)):
+out_dir = os.environ.get("SG_OUT", "bench_out")  # where the tools/gpu_*.sh scripts put the passes
+for path in sorted(glob.glob(os.path.join(out_dir, "%s_*" % tag, "run_counter_collection.csv"))):
     passes += 1
     for r in csv.DictReader(open(path)):
         key = "%s grid=%s" % (r["Kernel_Name"][:40], r["Grid_Size"])
