@@ -365,6 +365,56 @@ int sg_compare_sounds_batch(sg_ctx* ctx, const double* target_spec, int32_t nb, 
  * distance.only = TRUE)$normalizedDistance with the dtw package defaults
  * (|x_i - y_j|, symmetric2, / (n + m)). Host only (ABI 2). */
 int sg_dtw_symmetric2(const double* x, int64_t n, const double* y, int64_t m, double* out);
+/* ssm() parameters (R/SSM.R:63-98 formals; an additive extension of ABI 5):
+ * windowLength, step, ssmWin and kernelLen in ms, overlap in %. NaN = R's NULL
+ * for step (windowLength * (1 - overlap / 100)), maxFreq (floor(samplingRate /
+ * 2)) and nBands (100 * windowLength / 20). mfcc: the 1-based cepstral
+ * coefficients of input 0 (R's MFCC; every index in 1..nBands, max >= 2).
+ * input: 0 mfcc, 1 audiogram, 2 spectrum. norm: zeroOne per frame. simil: 0
+ * cosine, 1 cor. normalize: 1 = the numeric-vector path (tuneR::normalize:
+ * centre, / max|x|), 0 = the file path (samples used raw). */
+typedef struct sg_ssm_params {
+  double samplingRate;
+  double windowLength;
+  double overlap;
+  double step;
+  double ssmWin;
+  double maxFreq;
+  double nBands;
+  double kernelLen;
+  double kernelSD;
+  const int32_t* mfcc;
+  int32_t n_mfcc;
+  int32_t input;
+  int32_t norm;
+  int32_t simil;
+  int32_t normalize;
+} sg_ssm_params;
+/* ssm()'s integer decisions for a sound of len samples (host only, no device):
+ * the melfcc frame count, the SSM's side n (selfsim's windows), selfsim's win
+ * after its clamp to floor(n_frames / 2) and its odd-making rule, and
+ * getNovelty's kernelSize (R/SSM.R:111-119, :228-244). len <= 1 (R's
+ * length(x) > 1 test fails): n_frames = n = 0 and win is the unclamped value. */
+int sg_ssm_size(int64_t len, const sg_ssm_params* p, int32_t* n_frames, int32_t* n, int32_t* win,
+                int32_t* kernel_size);
+/* ssm(wave, ...) of one host waveform on the GPU in fp64 (R/SSM.R:63-360:
+ * melfcc, selfsim, getNovelty): ssm_out (n * n doubles, column-major; may be
+ * NULL) and novelty_out (n doubles), n from sg_ssm_size. Limits: windows of at
+ * most 4096 FFT points (SG_E_UNSUPPORTED); n * n <= 2^28 cells (n <= 16384),
+ * for a batch the sum over its calls (SG_E_UNSUPPORTED); kernelSize >= 2 and
+ * len >= 2 (SG_E_ARG). */
+int sg_ssm(sg_ctx* ctx, const double* wave, int64_t len, const sg_ssm_params* p, double* ssm_out,
+           double* novelty_out);
+/* ssm() of n_calls sounds in DEVICE memory (fp32, call c at d_wave +
+ * offsets[c], lengths[c] samples, the layout of sg_compare_sounds_batch), each
+ * normalized on the device when p->normalize, in one launch sequence. n_out[c]
+ * receives call c's n (0 for lengths[c] <= 1: skipped); its novelty goes to
+ * novelty_out + novelty_off[c] (n doubles) and, if ssm_out is not NULL, its
+ * matrix to ssm_out + ssm_off[c] (n * n doubles, column-major); both are host
+ * memory. */
+int sg_ssm_batch(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, const int64_t* lengths, int64_t n_calls,
+                 const sg_ssm_params* p, int32_t* n_out, double* novelty_out, const int64_t* novelty_off,
+                 double* ssm_out, const int64_t* ssm_off);
 /* Process-wide policy of the fp64 filter path for later sg_plan_batch calls:
  * mode 0 never, 1 when the conditioning estimate exceeds rho (default 100),
  * 2 every filtered bout. SG_E_ARG for an invalid mode or rho. */
@@ -479,6 +529,16 @@ double sg_noise_threshold(int32_t which, double nonlinBalance);
  * SG_E_UNSUPPORTED if wl is not on that path. */
 int sg_debug_wave_fft(sg_ctx* ctx, int32_t wl, int32_t inverse, int32_t nframes,
                       const float* in, float* out);
+/* Test hook, no reference counterpart: the tile map of ssm()'s Gram kernel
+ * (sg_ssm_gram, one wavefront per 16 x 16 tile on the fp64 matrix pipe). feat
+ * holds n vectors of L doubles one after another (host); out (host, n * n
+ * doubles, column-major) receives their unnormalised Gram matrix
+ * out[i + j n] = sum_k feat[i L + k] feat[j L + k]. */
+int sg_debug_ssm_gram(sg_ctx* ctx, const double* feat, int32_t L, int32_t n, double* out);
+/* Measurement hook: the device milliseconds of the 7 stages of the last sg_ssm /
+ * sg_ssm_batch run on a context with sg_set_profiling on (between events on the
+ * stream): stats, frames, feat, winstat, gram, novelty, out (7 doubles). */
+int sg_debug_ssm_kernel_ms(double* out);
 
 #ifdef __cplusplus
 }

@@ -42,6 +42,13 @@ class sg_mel_params(C.Structure):
                 ("penalizeLengthDif", C.c_int32), ("pad", C.c_int32)]
 
 
+class sg_ssm_params(C.Structure):
+    _fields_ = [("samplingRate", C.c_double), ("windowLength", C.c_double), ("overlap", C.c_double),
+                ("step", C.c_double), ("ssmWin", C.c_double), ("maxFreq", C.c_double), ("nBands", C.c_double),
+                ("kernelLen", C.c_double), ("kernelSD", C.c_double), ("mfcc", _ip), ("n_mfcc", C.c_int32),
+                ("input", C.c_int32), ("norm", C.c_int32), ("simil", C.c_int32), ("normalize", C.c_int32)]
+
+
 NORM_CB = C.CFUNCTYPE(C.c_double, C.c_void_p)
 UNIF_CB = C.CFUNCTYPE(C.c_double, C.c_void_p)
 GAMMA_CB = C.CFUNCTYPE(C.c_double, C.c_void_p, C.c_double, C.c_double)

@@ -19,18 +19,10 @@
 #include "sg_amp.h"
 #include "sg_prof.h"
 #include "sg_mel.h"
+#include "sg_ctx.h"
 
 #include <cstdio>
 #include <cstdlib>
-
-struct sg_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  hipStream_t aux = nullptr;  // finalize stream of the slice pipeline
-  std::string err;
-  bool profiling = false;
-  std::vector<sg::SgProfEvent> prof_events;
-};
 
 struct sg_plan {
   sg::Batch B;

@@ -19,6 +19,8 @@ struct MelGeom {
   std::vector<double> tw, twN;         // e^{-2 pi i t / M} (t < M/2), e^{-2 pi i k / nfft} (k < M), (re, im)
 };
 MelGeom mel_geom(const sg_mel_params& p);
+// the same with melfcc's maxfreq and nbands given (ssm() passes its own)
+MelGeom mel_geom(double sr, double windowLength, double step, double maxFreq, int nb, double throwaway);
 int mel_frames(const MelGeom& g, int64_t len);
 
 // getMelSpec of one waveform already on the device: nb x nk column-major into out

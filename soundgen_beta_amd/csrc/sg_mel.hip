@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "sg_mel.h"
+#include "sg_mel_dev.h"
 #include "sg_rmath.h"
 
 namespace {
@@ -39,11 +40,7 @@ struct MelFrame {
   int32_t seg;   // samples of the frame inside the candidate (<= winpts)
 };
 
-struct MelBand {
-  int32_t k0, n;  // first bin and count of the band's non-zero weights
-  int32_t w0;     // offset of its weights
-  int32_t pad;
-};
+using sg::MelBand;
 
 struct MelCand {
   int32_t f0, nf;  // frames [f0, f0 + nf)
@@ -82,41 +79,10 @@ __global__ __launch_bounds__(256) void sg_mel_frames(const T* __restrict__ x, co
     A[n] = make_double2(v[0], v[1]);
   }
   __syncthreads();
-  // radix-2 Stockham, forward (e^{-2 pi i / M}): Y[b 2Ns + k] = a + w b', Y[.. + Ns] = a - w b'
-  double2* X = A;
-  double2* Y = B;
-  for (int s = 0, Ns = 1; s < logM; ++s, Ns <<= 1) {
-    for (int j = threadIdx.x; j < M / 2; j += blockDim.x) {
-      const int k = j & (Ns - 1);
-      const double2 w = tw[k * (M / (2 * Ns))];
-      const double2 a = X[j], b0 = X[j + M / 2];
-      const double2 b = make_double2(b0.x * w.x - b0.y * w.y, b0.x * w.y + b0.y * w.x);
-      const int o = (j - k) * 2 + k;
-      Y[o] = make_double2(a.x + b.x, a.y + b.y);
-      Y[o + Ns] = make_double2(a.x - b.x, a.y - b.y);
-    }
-    __syncthreads();
-    double2* t = X;
-    X = Y;
-    Y = t;
-  }
-  // untangle: X_k = E_k + e^{-2 pi i k / N} O_k, E = (Z_k + conj Z_{M-k}) / 2,
-  // O = -i (Z_k - conj Z_{M-k}) / 2; power |X_k|^2 into Y (as .x)
-  double* P = reinterpret_cast<double*>(Y);
-  for (int k = threadIdx.x; k < M; k += blockDim.x) {
-    const double2 z = X[k], zc = X[(M - k) & (M - 1)];
-    const double ex = 0.5 * (z.x + zc.x), ey = 0.5 * (z.y - zc.y);
-    const double ox = 0.5 * (z.y + zc.y), oy = -0.5 * (z.x - zc.x);
-    const double2 w = twN[k];
-    const double re = ex + (w.x * ox - w.y * oy), im = ey + (w.x * oy + w.y * ox);
-    P[k] = re * re + im * im;
-  }
-  __syncthreads();
+  const double* P = sg::mel_frame_power(A, B, tw, twN, M, logM);
   double part = 0;
   for (int b = threadIdx.x; b < nb; b += blockDim.x) {
-    const MelBand bd = bands[b];
-    double acc = 0;
-    for (int i = 0; i < bd.n; ++i) acc += wts[bd.w0 + i] * P[bd.k0 + i];
+    const double acc = sg::mel_band(bands[b], wts, P);
     spec[(int64_t)blockIdx.x * nb + b] = acc;
     part += acc;
   }
@@ -296,12 +262,6 @@ __global__ __launch_bounds__(256) void sg_mel_out(const double* __restrict__ spe
     out[e] = log01(spec[(int64_t)kept[e / nb] * nb + e % nb], lo, den);
 }
 
-#define MELCHK(x)                                                                                        \
-  do {                                                                                                   \
-    hipError_t _e = (x);                                                                                 \
-    if (_e != hipSuccess) throw sg::SgError(SG_E_DEVICE, std::string(#x) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
 // Slaney mel scale (tuneR hz2mel / mel2hz, htk = FALSE)
 double hz2mel(double f) {
   const double f_sp = 200.0 / 3, brkfrq = 1000.0, brkpt = brkfrq / f_sp, logstep = std::exp(std::log(6.4) / 27);
@@ -312,63 +272,40 @@ double mel2hz(double z) {
   return z < brkpt ? f_sp * z : brkfrq * std::exp(std::log(logstep) * (z - brkpt));
 }
 
-// Device buffers of one compareSounds / getMelSpec launch sequence
-// Device buffers of one mel run, and the host copies their uploads read: an
-// async H2D copy from pageable memory may still be pending when the caller's
-// vector goes away, so upload() stages the bytes in memory this object owns.
-// The destructor frees the device buffers first (hipFree waits for the device),
-// then the staged host bytes.
-struct DevBuf {
-  std::vector<void*> p;
-  std::vector<std::vector<char>> host;
-  template <class T>
-  T* get(size_t n) {
-    void* q = nullptr;
-    MELCHK(hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)));
-    p.push_back(q);
-    return static_cast<T*>(q);
-  }
-  ~DevBuf() {
-    for (void* q : p) (void)hipFree(q);
-  }
-};
-
-template <class T>
-T* upload(DevBuf& db, const std::vector<T>& v, hipStream_t s) {
-  T* d = db.get<T>(v.size());
-  if (!v.empty()) {
-    const char* src = reinterpret_cast<const char*>(v.data());
-    db.host.emplace_back(src, src + v.size() * sizeof(T));
-    MELCHK(hipMemcpyAsync(d, db.host.back().data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
-  }
-  return d;
-}
+using sg::DevBuf;
+using sg::upload;
 
 }  // namespace
 
 namespace sg {
 
 MelGeom mel_geom(const sg_mel_params& p) {
-  MelGeom g;
-  const double sr = p.samplingRate;
-  if (!(sr > 0) || !(p.windowLength > 0)) throw SgError(SG_E_ARG, "getMelSpec: samplingRate and windowLength must be > 0");
+  if (!(p.samplingRate > 0) || !(p.windowLength > 0))
+    throw SgError(SG_E_ARG, "getMelSpec: samplingRate and windowLength must be > 0");
   const double step = std::isnan(p.step) ? p.windowLength * (1 - p.overlap / 100) : p.step;
+  // melfcc(nbands = 100 * windowLength / 20, maxfreq = samplingRate / 2)
+  return mel_geom(p.samplingRate, p.windowLength, step, std::isnan(p.maxFreq) ? p.samplingRate / 2 : p.maxFreq,
+                  (int)(100 * p.windowLength / 20), p.throwaway);
+}
+
+MelGeom mel_geom(double sr, double windowLength, double step, double maxf, int nb, double throwaway) {
+  MelGeom g;
+  if (!(sr > 0) || !(windowLength > 0)) throw SgError(SG_E_ARG, "getMelSpec: samplingRate and windowLength must be > 0");
   if (!(step > 0)) throw SgError(SG_E_ARG, "getMelSpec: step must be > 0");
   // tuneR powspec: winpts = round(wintime sr), steppts = round(steptime sr), nfft = 2^ceil(log2(winpts))
-  g.winpts = (int)r_round(p.windowLength / 1000 * sr);
+  g.winpts = (int)r_round(windowLength / 1000 * sr);
   g.steppts = (int)r_round(step / 1000 * sr);
   if (g.winpts < 2 || g.steppts < 1) throw SgError(SG_E_ARG, "getMelSpec: window shorter than 2 samples");
   g.nfft = (int)std::pow(2.0, std::ceil(std::log((double)g.winpts) / std::log(2.0)));
   if (g.nfft > 4096) throw SgError(SG_E_UNSUPPORTED, "getMelSpec: windows above 4096 points are not supported");
   g.nfreqs = g.nfft / 2;
-  g.nb = (int)(100 * p.windowLength / 20);  // melfcc(nbands = 100 * windowLength / 20)
+  g.nb = nb;
   if (g.nb < 1) throw SgError(SG_E_ARG, "getMelSpec: no mel bands");
-  g.thr = std::pow(2.0, p.throwaway / 10);
+  g.thr = std::pow(2.0, throwaway / 10);
   g.ham.resize(g.winpts);
   for (int i = 0; i < g.winpts; ++i) g.ham[i] = 0.54 - 0.46 * std::cos(2 * M_PI * i / (g.winpts - 1));
   // fft2melmx((nfreqs - 1) * 2, sr, nbands, 1, 0, maxFreq)[, 1:nfreqs] (audspec's nfft quirk)
   const int nfft2 = (g.nfreqs - 1) * 2;
-  const double maxf = std::isnan(p.maxFreq) ? sr / 2 : p.maxFreq;
   const double minmel = hz2mel(0.0), maxmel = hz2mel(maxf);
   std::vector<double> binf(g.nb + 2);
   for (int i = 0; i < g.nb + 2; ++i) binf[i] = mel2hz(minmel + (double)i / (g.nb + 1) * (maxmel - minmel));

@@ -99,6 +99,14 @@ def lib():
                               C.POINTER(C.c_int32)]
     L.sg_compare_sounds_batch.argtypes = [vp, dp, C.c_int32, C.c_int32, vp, i64p, i64p, i64,
                                           C.POINTER(_abi.sg_mel_params), C.c_int32, dp, dp]
+    if hasattr(L, "sg_ssm_size"):  # ssm(): an additive extension of ABI 5 (a host-only build lacks it)
+        i32p = C.POINTER(C.c_int32)
+        L.sg_ssm_size.argtypes = [i64, C.POINTER(_abi.sg_ssm_params), i32p, i32p, i32p, i32p]
+        L.sg_ssm.argtypes = [vp, dp, i64, C.POINTER(_abi.sg_ssm_params), dp, dp]
+        L.sg_ssm_batch.argtypes = [vp, vp, i64p, i64p, i64, C.POINTER(_abi.sg_ssm_params), i32p, dp, i64p, dp,
+                                   i64p]
+        L.sg_debug_ssm_gram.argtypes = [vp, dp, C.c_int32, C.c_int32, dp]
+        L.sg_debug_ssm_kernel_ms.argtypes = [dp]
     L.sg_rrng_create.argtypes = [C.c_int32, C.POINTER(vp)]
     L.sg_rrng_destroy.argtypes = [vp]
     L.sg_rrng_set_seed.argtypes = [vp, C.c_int32]
