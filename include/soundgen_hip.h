@@ -415,6 +415,61 @@ int sg_ssm(sg_ctx* ctx, const double* wave, int64_t len, const sg_ssm_params* p,
 int sg_ssm_batch(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, const int64_t* lengths, int64_t n_calls,
                  const sg_ssm_params* p, int32_t* n_out, double* novelty_out, const int64_t* novelty_off,
                  double* ssm_out, const int64_t* ssm_off);
+/* spectrogram() parameters (R/spectrogram.R:94-117 formals; an additive
+ * extension of ABI 5): windowLength, step and zp as in R (ms, ms, points),
+ * overlap and percentNoise in %. NaN = R's NULL for step (windowLength * (1 -
+ * overlap / 100)). smoothFreq / smoothTime: the rolling medians' k (<= 1: off;
+ * a whole odd number otherwise, SG_E_ARG if not). wn: 0 bartlett, 1 blackman, 2
+ * flattop, 3 hamming, 4 hanning, 5 rectangle, 6 gaussian. method: 0 spectrum, 1
+ * spectralDerivative. output: 0 original (|X|), 1 processed. */
+typedef struct sg_spectrogram_params {
+  double samplingRate;
+  double windowLength;
+  double step;
+  double overlap;
+  double zp;
+  double smoothFreq;
+  double smoothTime;
+  double qTime;
+  double percentNoise;
+  double noiseReduction;
+  double contrast;
+  double brightness;
+  int32_t wn;
+  int32_t method;
+  int32_t output;
+  int32_t pad;
+} sg_spectrogram_params;
+/* spectrogram()'s integer decisions for a sound of len samples (host only, no
+ * device): the window in points wl = floor(windowLength / 1000 * samplingRate /
+ * 2) * 2, the FFT length n_fft = wl + max(floor((zp - wl) / 2) * 2, 0), bins =
+ * n_fft / 2 and the frame count of getFrameBank's seq() (R/spectrogram.R:350;
+ * 0 for len <= 1 or len < wl). Limits of the device transform: wl >= 4, bins <=
+ * 2048 and bins a product of 2 and the odd primes <= 31; otherwise
+ * SG_E_UNSUPPORTED, and sg_spectrogram_size_error() names zp as the way to a
+ * supported length. */
+int sg_spectrogram_size(int64_t len, const sg_spectrogram_params* p, int32_t* wl, int32_t* n_fft, int32_t* bins,
+                        int32_t* frames);
+/* The message of the calling thread's last failed sg_spectrogram_size ("" if none). */
+const char* sg_spectrogram_size_error(void);
+/* spectrogram(wave, ...) of one host waveform on the GPU in fp64: out receives
+ * bins * frames doubles, frame after frame (R's column-major image of the bins x
+ * frames matrix it returns). Limits: those of sg_spectrogram_size; len >= wl
+ * (SG_E_ARG: R would index past the end); smoothTime <= bins and smoothFreq <=
+ * frames (SG_E_ARG, zoo::rollmedian stops); fewer than 2^31 frames in one launch
+ * sequence (SG_E_UNSUPPORTED). The rolling medians are exact for every odd k
+ * but cost O(k^2) per cell: they are meant for small k. */
+int sg_spectrogram(sg_ctx* ctx, const double* wave, int64_t len, const sg_spectrogram_params* p, double* out);
+/* spectrogram() of n_calls sounds in DEVICE memory (fp32, call c at d_wave +
+ * offsets[c], lengths[c] samples, the layout of sg_compare_sounds_batch) in one
+ * launch sequence. Call c's matrix goes to d_out + out_off[c] in DEVICE memory
+ * (bins * frames doubles as sg_spectrogram lays them out; the caller sizes d_out
+ * with sg_spectrogram_size); bins_out[c] / frames_out[c] receive its shape. A
+ * call with lengths[c] <= 1 or shorter than the window has 0 frames and writes
+ * nothing. The call returns when the stream has finished. */
+int sg_spectrogram_batch(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, const int64_t* lengths,
+                         int64_t n_calls, const sg_spectrogram_params* p, double* d_out, const int64_t* out_off,
+                         int32_t* bins_out, int32_t* frames_out);
 /* Process-wide policy of the fp64 filter path for later sg_plan_batch calls:
  * mode 0 never, 1 when the conditioning estimate exceeds rho (default 100),
  * 2 every filtered bout. SG_E_ARG for an invalid mode or rho. */
@@ -539,6 +594,13 @@ int sg_debug_ssm_gram(sg_ctx* ctx, const double* feat, int32_t L, int32_t n, dou
  * sg_ssm_batch run on a context with sg_set_profiling on (between events on the
  * stream): stats, frames, feat, winstat, gram, novelty, out (7 doubles). */
 int sg_debug_ssm_kernel_ms(double* out);
+/* Measurement hook: the device milliseconds of the 12 stages of the last
+ * sg_spectrogram / sg_spectrogram_batch run on a context with sg_set_profiling on
+ * (between events on the stream; 0 for a stage its argument switched off): stats,
+ * frames, derivative, median along bins, median along frames, frame quantile and
+ * range, log, entropy, entropy quantile, noise spectrum, subtraction, power and
+ * scale (12 doubles). */
+int sg_debug_spectrogram_kernel_ms(double* out);
 
 #ifdef __cplusplus
 }

@@ -49,6 +49,14 @@ class sg_ssm_params(C.Structure):
                 ("input", C.c_int32), ("norm", C.c_int32), ("simil", C.c_int32), ("normalize", C.c_int32)]
 
 
+class sg_spectrogram_params(C.Structure):
+    _fields_ = [("samplingRate", C.c_double), ("windowLength", C.c_double), ("step", C.c_double),
+                ("overlap", C.c_double), ("zp", C.c_double), ("smoothFreq", C.c_double), ("smoothTime", C.c_double),
+                ("qTime", C.c_double), ("percentNoise", C.c_double), ("noiseReduction", C.c_double),
+                ("contrast", C.c_double), ("brightness", C.c_double), ("wn", C.c_int32), ("method", C.c_int32),
+                ("output", C.c_int32), ("pad", C.c_int32)]
+
+
 NORM_CB = C.CFUNCTYPE(C.c_double, C.c_void_p)
 UNIF_CB = C.CFUNCTYPE(C.c_double, C.c_void_p)
 GAMMA_CB = C.CFUNCTYPE(C.c_double, C.c_void_p, C.c_double, C.c_double)

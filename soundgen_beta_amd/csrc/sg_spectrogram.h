@@ -1,0 +1,44 @@
+// sg_spectrogram.h — spectrogram() (R/spectrogram.R:94-276): host decisions
+// (sg_spectrogram.cpp) and the device launch sequence (sg_spectrogram.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <vector>
+
+#include "soundgen_hip.h"
+
+namespace sg {
+
+constexpr int kSpgStages = 12;   // sg_debug_spectrogram_kernel_ms
+constexpr int kSpgMaxBins = 2048;  // fft64's M, and the frame quantile's LDS sort
+
+// What spectrogram() decides from its arguments alone, validated
+struct SpgSetup {
+  double sr = 0, step = 0;
+  double by = 0;          // seq()'s fractional step / 1000 * samplingRate
+  int wl = 0;             // windowLength_points
+  int pad = 0;            // zpExtra / 2 zeros on either side of a frame (0 when zpExtra <= 0)
+  int N = 0, bins = 0;    // FFT length wl + 2 pad, N / 2
+  int kTime = 0, kFreq = 0;  // rolling medians along bins / along frames; 0: off
+  double qTime = 0, percentNoise = 0, noiseReduction = 0;
+  double contrast_exp = 1, brightness_exp = 1;
+  int wn = 6, deriv = 0, processed = 1;
+};
+SpgSetup spg_setup(const sg_spectrogram_params& p);
+// frames of a sound of len samples (0 for len <= 1 or len < wl), and the 0-based
+// first sample of frame i: floor(min(1 + i by, max(1, len - wl))) - 1
+int spg_frames(const SpgSetup& S, int64_t len);
+int64_t spg_frame_start(const SpgSetup& S, int64_t len, int i);
+// ftwindow_modif(wl, wn) in R's operation order
+std::vector<double> spg_window(int wl, int wn);
+
+// The launch sequence for n_calls sounds at d_x + offsets[c] (device memory, T =
+// float or double); matrices to d_out + out_off[c] (device memory). kernel_ms
+// (kSpgStages doubles or nullptr): the device time of each stage
+template <typename T>
+void spectrogram_device(const SpgSetup& S, const T* d_x, const int64_t* offsets, const int64_t* lengths,
+                        int64_t n_calls, double* d_out, const int64_t* out_off, int32_t* bins_out,
+                        int32_t* frames_out, hipStream_t s, double* kernel_ms);
+
+}  // namespace sg

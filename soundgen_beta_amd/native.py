@@ -107,6 +107,15 @@ def lib():
                                    i64p]
         L.sg_debug_ssm_gram.argtypes = [vp, dp, C.c_int32, C.c_int32, dp]
         L.sg_debug_ssm_kernel_ms.argtypes = [dp]
+    if hasattr(L, "sg_spectrogram_size"):  # spectrogram(): likewise additive, absent from a host-only build
+        i32p = C.POINTER(C.c_int32)
+        spp = C.POINTER(_abi.sg_spectrogram_params)
+        L.sg_spectrogram_size.argtypes = [i64, spp, i32p, i32p, i32p, i32p]
+        L.sg_spectrogram_size_error.argtypes = []
+        L.sg_spectrogram_size_error.restype = C.c_char_p
+        L.sg_spectrogram.argtypes = [vp, dp, i64, spp, dp]
+        L.sg_spectrogram_batch.argtypes = [vp, vp, i64p, i64p, i64, spp, vp, i64p, i32p, i32p]
+        L.sg_debug_spectrogram_kernel_ms.argtypes = [dp]
     L.sg_rrng_create.argtypes = [C.c_int32, C.POINTER(vp)]
     L.sg_rrng_destroy.argtypes = [vp]
     L.sg_rrng_set_seed.argtypes = [vp, C.c_int32]
