@@ -470,6 +470,71 @@ int sg_spectrogram(sg_ctx* ctx, const double* wave, int64_t len, const sg_spectr
 int sg_spectrogram_batch(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, const int64_t* lengths,
                          int64_t n_calls, const sg_spectrogram_params* p, double* d_out, const int64_t* out_off,
                          int32_t* bins_out, int32_t* frames_out);
+/* analyze()'s per-frame stage (R/analyze.R:233-575, R/utilities_analyze.R:22-324;
+ * an additive extension of ABI 5). The formals after analyze()'s argument repairs
+ * (:240-341; the caller makes them): silence, entropyThres, domThres and
+ * autocorThres in [0, 1]; windowLength and step in ms, step NaN = R's NULL
+ * (windowLength * (1 - overlap / 100)); zp in points; cutFreq, pitchFloor,
+ * pitchCeiling and domSmooth in Hz; nCands a whole number in [1, 8]
+ * (SG_E_UNSUPPORTED above 8); autocorSmooth NaN = R's NULL (2 * ceiling(7 *
+ * samplingRate / 44100 / 2) - 1). wn as in sg_spectrogram_params. methods: bit 0
+ * 'autocor', bit 1 'dom' (at least one; 'cep' and 'spec' are not built). */
+typedef struct sg_analyze_params {
+  double samplingRate;
+  double silence;
+  double windowLength;
+  double step;
+  double overlap;
+  double zp;
+  double cutFreq;
+  double entropyThres;
+  double pitchFloor;
+  double pitchCeiling;
+  double nCands;
+  double domThres;
+  double domSmooth;
+  double autocorThres;
+  double autocorSmooth;
+  int32_t wn;
+  int32_t methods;
+} sg_analyze_params;
+/* The stage's integer decisions for a sound of len samples (host only, no device):
+ * the window in points, its wl / 2 bins, the frame count (0 for len <= wl), the
+ * columns of a frame's row (15 + 2 nCands: ampl, entropy, HNR, dom, peakFreq,
+ * peakFreqCut, meanFreq, quartile25, quartile50, quartile75, specSlope, domCand,
+ * domCert, cond_silence, cond_entropy, autocorCand[nCands], autocorCert[nCands];
+ * NaN = R's NA, the two gates 0 / 1), and the first and last lag of the
+ * autocorrelation that getPitchAutocor reads (row j, lag j - 1, is labelled
+ * samplingRate / j; the rows with pitchFloor < label < pitchCeiling). extra (8
+ * int32 or NULL) receives rowLow, rowHigh (1-based, :466-467), the first bin
+ * (0-based) and the size of the cut band, pitchFloor_idx (1-based), domSmooth_bins,
+ * autocorSmooth and 0. All labels are decided after R's 15-significant-digit
+ * character round trip. SG_E_ARG where the reference stops (zp padding the frame, no
+ * label above 6 kHz, an empty lag range, a cut band under 2 bins) and for an even
+ * or too-wide autocorSmooth; SG_E_UNSUPPORTED for the limits of sg_spectrogram_size
+ * and nCands > 8. */
+int sg_analyze_frames_size(int64_t len, const sg_analyze_params* p, int32_t* wl, int32_t* bins, int32_t* frames,
+                           int32_t* cols, int32_t* lag_first, int32_t* lag_last, int32_t* extra);
+/* The message of the calling thread's last failed sg_analyze_frames_size /
+ * sg_analyze_frames_ampl_starts ("" if none). */
+const char* sg_analyze_frames_size_error(void);
+/* Host only: the 0-based first sample of the wl + 1 samples whose RMS is frame
+ * f's ampl, floor(seq(1, len - wl, length.out = frames)[f]) - 1 (:456-459), for
+ * f < n (n = the frame count of sg_analyze_frames_size). */
+int sg_analyze_frames_ampl_starts(int64_t len, const sg_analyze_params* p, int64_t* starts, int32_t n);
+/* The stage for one host waveform on the GPU in fp64: out receives frames * cols
+ * doubles, row after row. SG_E_ARG for len <= wl (the reference's amplitude window
+ * leaves the sound); fewer than 2^31 frames in one launch sequence. */
+int sg_analyze_frames(sg_ctx* ctx, const double* wave, int64_t len, const sg_analyze_params* p, double* out);
+/* The stage for n_calls sounds in DEVICE memory (fp32, call c at d_wave +
+ * offsets[c], lengths[c] samples) in one launch sequence. Call c's table goes to
+ * d_out + out_off[c] in DEVICE memory (frames * cols doubles; the caller sizes
+ * d_out with sg_analyze_frames_size); frames_out[c] receives its rows. A call
+ * with lengths[c] <= wl has 0 frames and writes nothing. Returns when the stream
+ * has finished. */
+int sg_analyze_frames_batch(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, const int64_t* lengths,
+                            int64_t n_calls, const sg_analyze_params* p, double* d_out, const int64_t* out_off,
+                            int32_t* frames_out);
 /* Process-wide policy of the fp64 filter path for later sg_plan_batch calls:
  * mode 0 never, 1 when the conditioning estimate exceeds rho (default 100),
  * 2 every filtered bout. SG_E_ARG for an invalid mode or rho. */
@@ -601,6 +666,12 @@ int sg_debug_ssm_kernel_ms(double* out);
  * range, log, entropy, entropy quantile, noise spectrum, subtraction, power and
  * scale (12 doubles). */
 int sg_debug_spectrogram_kernel_ms(double* out);
+/* Measurement hook: the device milliseconds of the 4 stages of the last
+ * sg_analyze_frames / sg_analyze_frames_batch run on a context with
+ * sg_set_profiling on: the spectrogram (statistics and |X| frames), the frame
+ * amplitudes, the spectral descriptives and dom, the autocorrelation and its
+ * peaks (4 doubles). */
+int sg_debug_analyze_kernel_ms(double* out);
 
 #ifdef __cplusplus
 }

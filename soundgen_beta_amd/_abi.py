@@ -57,6 +57,13 @@ class sg_spectrogram_params(C.Structure):
                 ("output", C.c_int32), ("pad", C.c_int32)]
 
 
+class sg_analyze_params(C.Structure):
+    _fields_ = [(f, C.c_double) for f in ("samplingRate", "silence", "windowLength", "step", "overlap", "zp", "cutFreq",
+                                          "entropyThres", "pitchFloor", "pitchCeiling", "nCands", "domThres",
+                                          "domSmooth", "autocorThres", "autocorSmooth")] + \
+        [("wn", C.c_int32), ("methods", C.c_int32)]
+
+
 NORM_CB = C.CFUNCTYPE(C.c_double, C.c_void_p)
 UNIF_CB = C.CFUNCTYPE(C.c_double, C.c_void_p)
 GAMMA_CB = C.CFUNCTYPE(C.c_double, C.c_void_p, C.c_double, C.c_double)

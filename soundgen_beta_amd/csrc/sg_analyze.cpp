@@ -1,0 +1,257 @@
+// sg_analyze.cpp — the host half of analyze()'s per-frame stage (R/analyze.R:233-575,
+// R/utilities_analyze.R:22-324): every integer decision (the window and frames
+// through sg_spectrogram.cpp; the frequency and lag labels after R's character
+// round trip; rowLow / rowHigh :466-467; the cut band and pitchFloor_idx,
+// utilities_analyze.R:52-53, :216; the amplitude windows :456-459; the smoothing
+// widths, utilities_analyze.R:206, :268; the lag range :262-263), the refusals, and
+// the autocorrelation filter (:403-407). sg_analyze_frames_size needs no device.
+// The numpy restatement (soundgen_beta_amd/analyze.py) makes the same decisions in
+// the same operation order, so no product and sum may fuse here.
+#pragma clang fp contract(off)
+#include "sg_analyze.h"
+
+#include <cmath>
+#include <complex>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+
+#include "sg_rmath.h"
+
+namespace sg {
+
+namespace {
+
+// as.numeric(as.character(v)): R prints 15 significant digits
+double rt15(double v) {
+  char b[48];
+  std::snprintf(b, sizeof b, "%.15g", v);
+  return std::strtod(b, nullptr);
+}
+
+// element i of seq(from, to, length.out = n): from + i by, the last one `to`
+double seq_len_at(double from, double to, int64_t n, int64_t i) {
+  if (i == 0 || n <= 1) return from;
+  if (i == n - 1) return to;
+  const double by = (to - from) / (double)(n - 1);
+  return from + (double)i * by;
+}
+
+using cd = std::complex<double>;
+
+// DFT of any length by its prime factors (decimation in time); sign -1 forward, +1 inverse (unscaled)
+void fft_any(std::vector<cd>& a, int sign) {
+  const int n = (int)a.size();
+  if (n <= 1) return;
+  int p = 2;
+  while (n % p) ++p;
+  const int m = n / p;
+  std::vector<std::vector<cd>> sub(p, std::vector<cd>(m));
+  for (int k = 0; k < m; ++k)
+    for (int r = 0; r < p; ++r) sub[r][k] = a[(size_t)k * p + r];
+  for (int r = 0; r < p; ++r) fft_any(sub[r], sign);
+  for (int q = 0; q < n; ++q) {
+    const int k = q % m;
+    cd s = 0;
+    for (int r = 0; r < p; ++r) {
+      const double ang = sign * 2.0 * M_PI * (double)(((int64_t)r * q) % n) / (double)n;
+      s += sub[r][k] * cd(std::cos(ang), std::sin(ang));
+    }
+    a[q] = s;
+  }
+}
+
+bool in01(double v) { return v >= 0 && v <= 1; }
+
+}  // namespace
+
+AnlSetup anl_setup(const sg_analyze_params& p) {
+  AnlSetup S;
+  sg_spectrogram_params q;
+  std::memset(&q, 0, sizeof q);
+  q.samplingRate = p.samplingRate;
+  q.windowLength = p.windowLength;
+  q.step = p.step;
+  q.overlap = p.overlap;
+  q.zp = 0;
+  q.contrast = .2;
+  q.percentNoise = 10;
+  q.wn = p.wn;
+  q.output = 0;
+  S.spg = spg_setup(q);
+  const double sr = S.spg.sr;
+  const int wl = S.spg.wl, bins = S.spg.bins;
+  if (!in01(p.silence) || !in01(p.entropyThres) || !in01(p.domThres) || !in01(p.autocorThres))
+    throw SgError(SG_E_ARG, "analyze: silence, entropyThres, domThres and autocorThres must lie in [0, 1]");
+  if (!(p.cutFreq > 0) || !(p.pitchFloor > 0) || !(p.pitchFloor <= p.pitchCeiling) || !(p.pitchCeiling <= sr / 2))
+    throw SgError(SG_E_ARG, "analyze: cutFreq and pitchFloor must be positive and pitchFloor <= pitchCeiling <= samplingRate / 2");
+  if (p.methods < 1 || p.methods > 3) throw SgError(SG_E_ARG, "analyze: pitchMethods must be a non-empty subset of 'autocor', 'dom'");
+  if (!(p.nCands >= 1) || p.nCands != std::floor(p.nCands)) throw SgError(SG_E_ARG, "analyze: nCands must be a whole number >= 1");
+  const double zp = std::isnan(p.zp) ? 0.0 : p.zp;
+  if (std::floor((zp - wl) / 2) * 2 > 0)
+    throw SgError(SG_E_ARG, "analyze: zp pads the " + std::to_string(wl) + "-point frame; acf() then returns " +
+                                std::to_string(wl + 1) + " values for the " + std::to_string(wl) +
+                                "-row column of autocorBank (R/analyze.R:479) and the reference stops");
+  S.silence = p.silence;
+  S.entropyThres = p.entropyThres;
+  S.domThres = p.domThres;
+  S.autocorThres = p.autocorThres;
+  S.do_autocor = p.methods & 1;
+  S.do_dom = (p.methods >> 1) & 1;
+  // Y = seq(0, samplingRate / 2 - samplingRate / wl, length.out = bins) / 1000, through rownames
+  S.freq.resize(bins);
+  const double top = (sr / 2) - (sr / wl);
+  int cut1 = -1;
+  S.cut0 = -1;
+  for (int k = 0; k < bins; ++k) {
+    const double lab = rt15(seq_len_at(0.0, top, bins, k) / 1000);
+    if (!S.rowLow && lab > 0.05) S.rowLow = k + 1;
+    if (!S.rowHigh && lab > 6) S.rowHigh = k + 1;
+    if (!S.pf_idx && lab > p.pitchFloor / 1000) S.pf_idx = k + 1;
+    S.freq[k] = 1000 * lab;
+    if (S.freq[k] > p.pitchFloor && S.freq[k] < p.cutFreq) {
+      if (S.cut0 < 0) S.cut0 = k;
+      cut1 = k;
+    }
+  }
+  if (!S.rowLow || !S.rowHigh)
+    throw SgError(SG_E_ARG, "analyze: no frequency label above 6 kHz (samplingRate / 2 must exceed 6000 Hz): rowHigh is NA and "
+                            "rowLow:rowHigh stops in the reference");
+  S.ncut = S.cut0 < 0 ? 0 : cut1 - S.cut0 + 1;
+  if (S.ncut < 2)
+    throw SgError(SG_E_ARG, "analyze: fewer than 2 bins between pitchFloor and cutFreq; lm(amp ~ freq) stops in the reference");
+  const double bin = sr / 2 / bins;
+  const double dw = 2 * std::ceil(p.domSmooth / bin / 2) - 1;
+  if (!(dw >= 1)) throw SgError(SG_E_ARG, "analyze: domSmooth must be positive");
+  S.domW = dw > 1e9 ? 1000000000 : (int)dw;
+  const double aw = std::isnan(p.autocorSmooth) ? 2 * std::ceil(7 * sr / 44100 / 2) - 1 : p.autocorSmooth;
+  if (!(aw >= 1) || aw != std::floor(aw) || aw > 1e9 || ((int64_t)aw) % 2 == 0)
+    throw SgError(SG_E_ARG, "analyze: autocorSmooth must be a whole odd number (zoo's even-width alignment is not restated)");
+  S.acW = (int)aw;
+  int j0 = 0, j1 = 0;  // rows (1-based) with pitchFloor < samplingRate / j < pitchCeiling
+  for (int j = 1; j <= wl; ++j) {
+    const double lf = rt15(sr / j);
+    if (lf > p.pitchFloor && lf < p.pitchCeiling) {
+      if (!j0) j0 = j;
+      j1 = j;
+    }
+  }
+  if (!j0) throw SgError(SG_E_ARG, "analyze: no lag between pitchFloor and pitchCeiling (max(numeric(0)) in the reference)");
+  S.lag0 = j0 - 1;
+  S.nlag = j1 - j0 + 1;
+  S.lagf.resize(S.nlag);
+  for (int i = 0; i < S.nlag; ++i) S.lagf[i] = rt15(sr / (j0 + i));
+  if (S.acW > S.nlag)
+    throw SgError(SG_E_ARG, "analyze: autocorSmooth = " + std::to_string(S.acW) + " is wider than the " +
+                                std::to_string(S.nlag) + " lags between pitchFloor and pitchCeiling");
+  if (p.nCands > kAnlMaxCands)
+    throw SgError(SG_E_UNSUPPORTED, "analyze: nCands = " + std::to_string((long long)p.nCands) + "; at most " +
+                                        std::to_string(kAnlMaxCands) + " candidates are kept");
+  S.nCands = (int)p.nCands;
+  S.cols = kAnlFixed + 2 * S.nCands;
+  double m = 0;
+  for (int k = 0; k < S.ncut; ++k) m += S.freq[S.cut0 + k];
+  m /= S.ncut;
+  S.xc.resize(S.ncut);
+  for (int k = 0; k < S.ncut; ++k) {
+    S.xc[k] = S.freq[S.cut0 + k] - m;
+    S.sxx += S.xc[k] * S.xc[k];
+  }
+  return S;
+}
+
+int anl_frames(const AnlSetup& S, int64_t len) { return len <= S.spg.wl ? 0 : spg_frames(S.spg, len); }
+
+int64_t anl_ampl_start(const AnlSetup& S, int64_t len, int frames, int f) {
+  return (int64_t)std::floor(seq_len_at(1.0, (double)(len - S.spg.wl), frames, f)) - 1;
+}
+
+std::vector<double> anl_filter(const AnlSetup& S) {
+  const int wl = S.spg.wl, N = 2 * wl;
+  const std::vector<double> w = spg_window(N, S.spg.wn);  // ftwindow_modif(2 * windowLength_points)
+  std::vector<cd> a(N);
+  for (int i = 0; i < N; ++i) a[i] = w[i];
+  fft_any(a, -1);
+  for (int i = 0; i < N; ++i) a[i] = std::norm(a[i]);  // abs(fft(filter)) ^ 2
+  fft_any(a, +1);
+  std::vector<double> f(wl);
+  double mx = 0;
+  for (int i = 0; i < wl; ++i) {
+    f[i] = std::norm(a[i]);  // abs(fft(., inverse = TRUE)) ^ 2: the reference's second squaring
+    mx = std::max(mx, f[i]);
+  }
+  std::vector<double> out(S.nlag);
+  for (int i = 0; i < S.nlag; ++i) out[i] = f[S.lag0 + i] / mx;
+  return out;
+}
+
+}  // namespace sg
+
+namespace {
+thread_local std::string g_anl_err;
+// sg_analyze_frames_size is called once per sound of a batch: the setup of the last parameters is kept
+thread_local sg_analyze_params g_last_p;
+thread_local sg::AnlSetup g_last_S;
+thread_local bool g_have = false;
+
+const sg::AnlSetup& cached_setup(const sg_analyze_params& p) {
+  if (!g_have || std::memcmp(&p, &g_last_p, sizeof p) != 0) {
+    g_have = false;
+    g_last_S = sg::anl_setup(p);
+    g_last_p = p;
+    g_have = true;
+  }
+  return g_last_S;
+}
+
+template <class F>
+int size_guard(F&& f) {
+  try {
+    f();
+    return SG_OK;
+  } catch (const sg::SgError& e) {
+    g_anl_err = e.what();
+    return e.code;
+  } catch (...) {
+    g_anl_err = "out of host memory";
+    return SG_E_NOMEM;
+  }
+}
+}  // namespace
+
+extern "C" int sg_analyze_frames_size(int64_t len, const sg_analyze_params* p, int32_t* wl, int32_t* bins, int32_t* frames,
+                                      int32_t* cols, int32_t* lag_first, int32_t* lag_last, int32_t* extra) {
+  if (!p || !wl || !bins || !frames || !cols || !lag_first || !lag_last) {
+    g_anl_err = "sg_analyze_frames_size: bad arguments";
+    return SG_E_ARG;
+  }
+  return size_guard([&]() {
+    const sg::AnlSetup& S = cached_setup(*p);
+    *wl = S.spg.wl;
+    *bins = S.spg.bins;
+    *frames = sg::anl_frames(S, len);
+    *cols = S.cols;
+    *lag_first = S.lag0;
+    *lag_last = S.lag0 + S.nlag - 1;
+    if (extra) {
+      const int32_t e[8] = {S.rowLow, S.rowHigh, S.cut0, S.ncut, S.pf_idx, S.domW, S.acW, 0};
+      std::memcpy(extra, e, sizeof e);
+    }
+  });
+}
+
+extern "C" int sg_analyze_frames_ampl_starts(int64_t len, const sg_analyze_params* p, int64_t* starts, int32_t n) {
+  if (!p || (n > 0 && !starts)) {
+    g_anl_err = "sg_analyze_frames_ampl_starts: bad arguments";
+    return SG_E_ARG;
+  }
+  return size_guard([&]() {
+    const sg::AnlSetup& S = cached_setup(*p);
+    const int frames = sg::anl_frames(S, len);
+    if (n > frames) throw sg::SgError(SG_E_ARG, "sg_analyze_frames_ampl_starts: n exceeds the frame count");
+    for (int f = 0; f < n; ++f) starts[f] = sg::anl_ampl_start(S, len, frames, f);
+  });
+}
+
+extern "C" const char* sg_analyze_frames_size_error(void) { return g_anl_err.c_str(); }

@@ -1,0 +1,49 @@
+// sg_analyze.h — the per-frame stage of analyze() (R/analyze.R:233-575,
+// R/utilities_analyze.R:22-324): host decisions (sg_analyze.cpp) and the device
+// launch sequence (sg_analyze.hip).
+#pragma once
+#include <cstdint>
+#include <vector>
+
+#include "sg_spectrogram.h"
+#include "soundgen_hip.h"
+
+namespace sg {
+
+constexpr int kAnlStages = 4;    // sg_debug_analyze_kernel_ms
+constexpr int kAnlMaxCands = 8;  // nCands
+constexpr int kAnlFixed = 15;    // columns before autocorCand / autocorCert
+// columns of a frame's row
+enum AnlCol { kAmpl = 0, kEntropy, kHNR, kDom, kPeakFreq, kPeakFreqCut, kMeanFreq, kQ25, kQ50, kQ75, kSlope, kDomCand,
+              kDomCert, kCondSilence, kCondEntropy };
+
+// What the stage decides from its arguments alone, validated. Every label has made
+// R's 15-significant-digit character round trip (spectrogram.R:176, analyze.R:484).
+struct AnlSetup {
+  SpgSetup spg;            // getFrameBank / spectrogram(output = 'original'), zp = 0
+  double silence = 0, entropyThres = 0, domThres = 0, autocorThres = 0;
+  int nCands = 1, cols = 0;
+  int do_autocor = 0, do_dom = 0;
+  int rowLow = 0, rowHigh = 0;  // 1-based, inclusive: the entropy band (:466-467)
+  int cut0 = 0, ncut = 0;       // the cut band freq > pitchFloor & freq < cutFreq: bins [cut0, cut0 + ncut)
+  int pf_idx = 0;               // pitchFloor_idx, 1-based (utilities_analyze.R:216)
+  int domW = 0, acW = 0;        // domSmooth_bins, autocorSmooth
+  int lag0 = 0, nlag = 0;       // lags [lag0, lag0 + nlag) are read by getPitchAutocor
+  std::vector<double> freq;     // 1000 * label of every bin (Hz)
+  std::vector<double> xc;       // the cut band's freq - mean(freq), for the slope
+  double sxx = 0;               // sum(xc^2)
+  std::vector<double> lagf;     // label samplingRate / j of the used rows
+};
+AnlSetup anl_setup(const sg_analyze_params& p);
+// frames of a sound of len samples: 0 for len <= wl
+int anl_frames(const AnlSetup& S, int64_t len);
+// 0-based first sample of frame f's amplitude window of wl + 1 samples
+int64_t anl_ampl_start(const AnlSetup& S, int64_t len, int frames, int f);
+// autoCorrelation_filter (:403-407) at the used lags, fp64
+std::vector<double> anl_filter(const AnlSetup& S);
+
+template <typename T>
+void analyze_device(const AnlSetup& S, const T* d_x, const int64_t* offsets, const int64_t* lengths, int64_t n_calls,
+                    double* d_out, const int64_t* out_off, int32_t* frames_out, hipStream_t s, double* kernel_ms);
+
+}  // namespace sg

@@ -1,0 +1,593 @@
+// sg_analyze.hip — the per-frame stage of analyze() on the device (R/analyze.R:233-575,
+// R/utilities_analyze.R:22-324), fp64 throughout. A frame's row of the output table
+// holds the columns of sg::AnlCol, then autocorCand[nCands] and autocorCert[nCands];
+// NaN is R's NA.
+//
+//   (spectrogram_device, output = 'original': the normalisation statistics and the
+//    |X| frames, to scratch. analyze() normalises and getFrameBank normalises again;
+//    the second pass divides by exactly 1, so it runs once.)
+//   sg_anl_ampl   :455-462 RMS of the wl + 1 normalised samples of a frame's
+//                 amplitude window; the sound's min(ampl) (an order-preserving key)
+//   sg_anl_spec   one workgroup per frame, its magnitudes in LDS: getEntropy over
+//                 rowLow:rowHigh (:466-470), the two gates (:472-473), analyzeFrame's
+//                 descriptives (utilities_analyze.R:45-69) for cond_silence frames,
+//                 getDom (:190-233) for cond_entropy frames
+//   sg_anl_acf    one workgroup per cond_entropy frame: the windowed frame rebuilt
+//                 in LDS, acf() at the lags getPitchAutocor reads (direct sums, four
+//                 consecutive lags per thread), / the filter table (:479-481), then
+//                 getPitchAutocor (:250-324) and the dom certainty (:151-159)
+// Cumulative sums run in index order: a thread sums a contiguous run, one thread
+// folds the 256 run sums in order, and the runs are rescanned from their offsets,
+// so a frame's result does not depend on the launch it is in.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "sg_analyze.h"
+#include "sg_ctx.h"
+#include "sg_mel_dev.h"
+#include "sg_rmath.h"
+
+namespace {
+
+using sg::DevBuf;
+using sg::SpgStat;
+using sg::upload;
+
+constexpr int kT = 256;
+
+struct AnlSound {
+  int64_t base, len;  // samples [base, base + len) of the input buffer
+  int64_t z0;         // first cell of its |X| frames in scratch
+  int64_t row0;       // first double of its table in the output buffer
+  int32_t nf, pad;
+};
+
+struct AnlFrame {
+  int64_t o;       // first sample of the frame within the sound
+  int64_t a;       // first sample of its amplitude window
+  int32_t snd, f;  // sound, frame within the sound
+};
+
+// the launch's constants
+struct AnlK {
+  int wl, B, cols, nCands;
+  int rowLow, rowHigh;  // 0-based, inclusive
+  int cut0, ncut, pf_idx, domW, acW, lag0, nlag;
+  int do_dom, do_autocor;
+  double silence, entropyThres, domThres, autocorThres, sxx;
+};
+
+__device__ __forceinline__ unsigned long long dkey(double v) {
+  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double dunkey(unsigned long long k) {
+  return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
+}
+
+// op 0: sum, 1: min, 2: max over the workgroup, in a fixed order; every thread gets the result
+__device__ __forceinline__ double block_reduce(double v, int op, double* red) {
+  __syncthreads();
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int o = kT / 2; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) {
+      const double a = red[threadIdx.x], b = red[threadIdx.x + o];
+      red[threadIdx.x] = op == 0 ? a + b : op == 1 ? fmin(a, b) : fmax(a, b);
+    }
+    __syncthreads();
+  }
+  return red[0];
+}
+
+// the smallest int over the workgroup
+__device__ __forceinline__ int block_min_int(int v, int* red) {
+  __syncthreads();
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int o = kT / 2; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] = min(red[threadIdx.x], red[threadIdx.x + o]);
+    __syncthreads();
+  }
+  return red[0];
+}
+
+// dst[i] = src[0] + ... + src[i] for i < n, summed in index order (see the header)
+__device__ __forceinline__ void block_cumsum(const double* src, int n, double* dst, double* red) {
+  const int run = (n + kT - 1) / kT;
+  const int i0 = min((int)threadIdx.x * run, n), i1 = min(i0 + run, n);
+  double acc = 0;
+  for (int i = i0; i < i1; ++i) acc += src[i];
+  __syncthreads();
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = 0;
+    for (int t = 0; t < kT; ++t) {
+      const double v = red[t];
+      red[t] = s;
+      s += v;
+    }
+  }
+  __syncthreads();
+  acc = red[threadIdx.x];
+  for (int i = i0; i < i1; ++i) {
+    acc += src[i];
+    dst[i] = acc;
+  }
+  __syncthreads();
+}
+
+// the first i < n with cum[i] > v (strict) or cum[i] >= v; n if none
+__device__ __forceinline__ int first_crossing(const double* cum, int n, double v, bool strict, int* redi) {
+  int best = n;
+  for (int i = threadIdx.x; i < n; i += kT)
+    if (strict ? cum[i] > v : cum[i] >= v) {
+      best = i;
+      break;
+    }
+  return block_min_int(best, redi);
+}
+
+template <typename T>
+__device__ __forceinline__ double norm_sample(const T* xc, int64_t i, const SpgStat& st) {
+  double s = (double)xc[i];
+  if (st.scaled) s = (s - st.mean) / st.sd;
+  return s / st.m;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kT) void sg_anl_ampl(const T* __restrict__ x, const AnlFrame* __restrict__ frames,
+                                                  const AnlSound* __restrict__ snds, const SpgStat* __restrict__ stat,
+                                                  int wl, int cols, double* __restrict__ out,
+                                                  unsigned long long* __restrict__ minampl) {
+  __shared__ double red[kT];
+  const AnlFrame F = frames[blockIdx.x];
+  const AnlSound S = snds[F.snd];
+  const SpgStat st = stat[F.snd];
+  const T* xc = x + S.base + F.a;  // host: F.a + wl < S.len
+  double acc = 0;
+  for (int i = threadIdx.x; i <= wl; i += kT) {
+    const double v = norm_sample(xc, i, st);
+    acc += v * v;
+  }
+  acc = block_reduce(acc, 0, red);
+  if (threadIdx.x == 0) {
+    const double a = sqrt(acc / (double)(wl + 1));
+    out[S.row0 + (int64_t)F.f * cols + sg::kAmpl] = a;
+    if (a == a) atomicMin(&minampl[F.snd], dkey(a));
+  }
+}
+
+__global__ __launch_bounds__(kT) void sg_anl_spec(const AnlFrame* __restrict__ frames, const AnlSound* __restrict__ snds,
+                                                  const double* __restrict__ Z, const double* __restrict__ freq,
+                                                  const double* __restrict__ xcut, const unsigned long long* __restrict__ minampl,
+                                                  AnlK K, double* __restrict__ out) {
+  __shared__ double fr[sg::kSpgMaxBins];
+  __shared__ double cum[sg::kSpgMaxBins];
+  __shared__ double red[kT];
+  __shared__ int redi[kT];
+  const AnlFrame F = frames[blockIdx.x];
+  const AnlSound S = snds[F.snd];
+  const int B = K.B;
+  const double* z = Z + S.z0 + (int64_t)F.f * B;
+  double* row = out + S.row0 + (int64_t)F.f * K.cols;
+  for (int b = threadIdx.x; b < B; b += kT) fr[b] = z[b];
+  __syncthreads();
+  // getEntropy(s[rowLow:rowHigh, f], 'weiner'): NA for sum == 0; x <= 0 -> 1e-10; exp(mean(log)) / mean
+  double s0 = 0, s1 = 0, sl = 0;
+  for (int b = K.rowLow + threadIdx.x; b <= K.rowHigh; b += kT) {
+    const double v = fr[b];
+    s0 += v;
+    const double y = v <= 0 ? 1e-10 : v;
+    s1 += y;
+    sl += log(y);
+  }
+  s0 = block_reduce(s0, 0, red);
+  s1 = block_reduce(s1, 0, red);
+  sl = block_reduce(sl, 0, red);
+  const double nb = (double)(K.rowHigh - K.rowLow + 1);
+  const double entropy = s0 == 0 ? NAN : exp(sl / nb) / (s1 / nb);
+  const double ampl = row[sg::kAmpl];
+  const double sil = fmax(K.silence, dunkey(minampl[F.snd]));  // silence = max(silence, min(ampl))
+  const bool c_sil = ampl > sil;
+  const bool c_ent = c_sil && entropy < K.entropyThres;  // NA entropy: not tracked
+  if (threadIdx.x == 0) {
+    row[sg::kEntropy] = entropy;
+    row[sg::kCondSilence] = c_sil ? 1.0 : 0.0;
+    row[sg::kCondEntropy] = c_ent ? 1.0 : 0.0;
+    for (int c = sg::kHNR; c <= sg::kDomCert; ++c) row[c] = NAN;
+    for (int c = sg::kAnlFixed; c < K.cols; ++c) row[c] = NAN;
+  }
+  if (!c_sil) return;  // workgroup-uniform
+  // which.max(frame): the first maximum
+  double mx = -INFINITY;
+  for (int b = threadIdx.x; b < B; b += kT) mx = fmax(mx, fr[b]);
+  mx = block_reduce(mx, 2, red);
+  int am = B;
+  for (int b = threadIdx.x; b < B; b += kT)
+    if (fr[b] == mx) {
+      am = b;
+      break;
+    }
+  am = block_min_int(am, redi);
+  // meanFreq: the first index whose cumulative sum exceeds half the total
+  block_cumsum(fr, B, cum, red);
+  const double amplitude = cum[B - 1];
+  const int imean = first_crossing(cum, B, amplitude / 2, true, redi);
+  // the cut band
+  block_cumsum(fr + K.cut0, K.ncut, cum, red);
+  const double amp_cut = cum[K.ncut - 1];
+  const int i25 = first_crossing(cum, K.ncut, 0.25 * amp_cut, false, redi);
+  const int i50 = first_crossing(cum, K.ncut, 0.5 * amp_cut, false, redi);
+  const int i75 = first_crossing(cum, K.ncut, 0.75 * amp_cut, false, redi);
+  // lm(amp ~ freq): sum((x - mean x)(y - mean y)) / sum((x - mean x)^2)
+  const double ybar = amp_cut / (double)K.ncut;
+  double sxy = 0;
+  for (int k = threadIdx.x; k < K.ncut; k += kT) sxy += xcut[k] * (fr[K.cut0 + k] - ybar);
+  sxy = block_reduce(sxy, 0, red);
+  if (threadIdx.x == 0) {
+    row[sg::kPeakFreq] = am < B ? freq[am] : NAN;
+    row[sg::kPeakFreqCut] = am < K.ncut ? freq[K.cut0 + am] : NAN;  // meanSpec_cut$freq[which.max(frame)]
+    row[sg::kMeanFreq] = imean < B ? freq[imean] : NAN;
+    row[sg::kQ25] = i25 < K.ncut ? freq[K.cut0 + i25] : NAN;
+    row[sg::kQ50] = i50 < K.ncut ? freq[K.cut0 + i50] : NAN;
+    row[sg::kQ75] = i75 < K.ncut ? freq[K.cut0 + i75] : NAN;
+    row[sg::kSlope] = sxy / K.sxx;
+  }
+  if (!c_ent || !K.do_dom) return;
+  // getDom on frame / max(frame): a centred window of domW bins whose first maximum
+  // is its middle and exceeds domThres; the first such bin (1-based) above pitchFloor_idx
+  __syncthreads();
+  for (int b = threadIdx.x; b < B; b += kT) cum[b] = fr[b] / mx;
+  __syncthreads();
+  const int h = K.domW / 2;
+  int best = B;
+  for (int c = h + threadIdx.x; c < B - h && best == B; c += kT) {
+    if (c + 1 <= K.pf_idx) continue;
+    const double v = cum[c];
+    if (!(v > K.domThres)) continue;
+    bool ok = true;
+    for (int j = c - h; j < c && ok; ++j) ok = cum[j] < v || cum[j] != cum[j];
+    for (int j = c + 1; j <= c + h && ok; ++j) ok = cum[j] <= v || cum[j] != cum[j];
+    if (ok) best = c;
+  }
+  best = block_min_int(best, redi);
+  if (threadIdx.x == 0 && best < B) {
+    row[sg::kDom] = freq[best];
+    row[sg::kDomCand] = freq[best];
+    row[sg::kDomCert] = cum[best];
+  }
+}
+
+// LDS: wl + 4 doubles (the demeaned windowed frame and 4 zeros, later the peak list), nlag
+// doubles (the corrected autocorrelation)
+template <typename T>
+__global__ __launch_bounds__(kT) void sg_anl_acf(const T* __restrict__ x, const AnlFrame* __restrict__ frames,
+                                                 const AnlSound* __restrict__ snds, const SpgStat* __restrict__ stat,
+                                                 const double* __restrict__ win, const double* __restrict__ filt,
+                                                 const double* __restrict__ lagf, AnlK K, double* __restrict__ out) {
+  extern __shared__ double lds_acf[];
+  __shared__ double red[kT];
+  __shared__ int npk;
+  double* xw = lds_acf;
+  double* amp = lds_acf + K.wl + 4;
+  const AnlFrame F = frames[blockIdx.x];
+  const AnlSound S = snds[F.snd];
+  double* row = out + S.row0 + (int64_t)F.f * K.cols;
+  if (row[sg::kCondEntropy] != 1.0) return;  // workgroup-uniform; written by sg_anl_spec
+  const SpgStat st = stat[F.snd];
+  const T* xc = x + S.base + F.o;  // host: F.o + wl <= S.len
+  const int wl = K.wl, nl = K.nlag;
+  double acc = 0;
+  if (threadIdx.x < 4) xw[wl + threadIdx.x] = 0.0;  // the zeros the lag groups run into
+  for (int i = threadIdx.x; i < wl; i += kT) {
+    const double v = norm_sample(xc, i, st) * win[i];
+    xw[i] = v;
+    acc += v;
+  }
+  const double mean = block_reduce(acc, 0, red) / (double)wl;
+  acc = 0;
+  for (int i = threadIdx.x; i < wl; i += kT) {
+    const double v = xw[i] - mean;  // acf() demeans
+    xw[i] = v;
+    acc += v * v;
+  }
+  const double c0 = block_reduce(acc, 0, red) / (double)wl;  // lag 0; the barrier inside publishes xw
+  const double se = sqrt(c0);
+  // Four consecutive lags per thread: xw[t] is a broadcast, and the window w0..w3 =
+  // xw[t + k .. t + k + 3] slides by one new value per step, so 4 multiply-adds cost 2
+  // LDS reads. Every lag's sum still runs over t in order; the shorter lags of a group
+  // run into the 4 zeros behind the frame, which add nothing.
+  for (int g = threadIdx.x; 4 * g < nl; g += kT) {
+    const int k = K.lag0 + 4 * g;
+    const int n = wl - k;  // >= 1; the terms of the group's first lag
+    const double* y = xw + k;
+    double s0 = 0, s1 = 0, s2 = 0, s3 = 0;
+    double w0 = y[0], w1 = y[1], w2 = y[2], w3 = y[3];
+    int t = 0;
+    for (; t + 4 <= n; t += 4) {  // reads up to y[n + 3] = xw[wl + 3]
+      double a = xw[t];
+      s0 += a * w0; s1 += a * w1; s2 += a * w2; s3 += a * w3;
+      w0 = y[t + 4];
+      a = xw[t + 1];
+      s0 += a * w1; s1 += a * w2; s2 += a * w3; s3 += a * w0;
+      w1 = y[t + 5];
+      a = xw[t + 2];
+      s0 += a * w2; s1 += a * w3; s2 += a * w0; s3 += a * w1;
+      w2 = y[t + 6];
+      a = xw[t + 3];
+      s0 += a * w3; s1 += a * w0; s2 += a * w1; s3 += a * w2;
+      w3 = y[t + 7];
+    }
+    for (; t < n; ++t) {  // reads up to y[n + 2]
+      const double a = xw[t];
+      s0 += a * y[t]; s1 += a * y[t + 1]; s2 += a * y[t + 2]; s3 += a * y[t + 3];
+    }
+    const double s[4] = {s0, s1, s2, s3};
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int i = 4 * g + r;
+      if (i < nl) {
+        double a = (s[r] / (double)wl) / (se * se);
+        a = a > 1.0 ? 1.0 : (a < -1.0 ? -1.0 : a);  // as acf()'s C code clamps
+        amp[i] = a / filt[i];
+      }
+    }
+  }
+  if (threadIdx.x == 0) npk = 0;
+  __syncthreads();
+  // HNR = max(a$amp); the peaks: a centred window of acW rows whose first maximum is
+  // its middle and exceeds autocorThres. The peak list is unordered; every use below
+  // is decided by (value, index), not by the list's order
+  double hn = -INFINITY;
+  for (int i = threadIdx.x; i < nl; i += kT) hn = fmax(hn, amp[i]);
+  hn = block_reduce(hn, 2, red);
+  int* pk = reinterpret_cast<int*>(xw);  // xw is dead (block_reduce's barriers are behind every read)
+  const int h = K.acW / 2;
+  for (int c = h + threadIdx.x; c < nl - h; c += kT) {
+    const double v = amp[c];
+    if (!(v > K.autocorThres)) continue;
+    bool ok = true;
+    for (int j = c - h; j < c && ok; ++j) ok = amp[j] < v || amp[j] != amp[j];
+    for (int j = c + 1; j <= c + h && ok; ++j) ok = amp[j] <= v || amp[j] != amp[j];
+    if (ok) pk[atomicAdd(&npk, 1)] = c;  // at most nl - 2 h <= wl entries
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const int P = npk;
+  double HNR = hn > -INFINITY ? hn : NAN;
+  if (P > 0) {
+    double pmax = -INFINITY;
+    for (int q = 0; q < P; ++q) pmax = fmax(pmax, amp[pk[q]]);
+    int ibest = nl;  // which(amp > 0.975 * max(amp))[1]
+    for (int q = 0; q < P; ++q)
+      if (amp[pk[q]] > 0.975 * pmax && pk[q] < ibest) ibest = pk[q];
+    const double cutf = lagf[ibest] / 1.8;  // peaks with freq > bestFreq / 1.8
+    // order(amp, decreasing = TRUE): the larger first, the earlier row on ties
+    double lastv = INFINITY;
+    int lasti = -1;
+    for (int n = 0; n < K.nCands; ++n) {
+      int bi = -1;
+      double bv = -INFINITY;
+      for (int q = 0; q < P; ++q) {
+        const int i = pk[q];
+        const double v = amp[i];
+        if (!(lagf[i] > cutf)) continue;
+        if (!(v < lastv || (v == lastv && i > lasti))) continue;  // already taken
+        if (bi < 0 || v > bv || (v == bv && i < bi)) {
+          bi = i;
+          bv = v;
+        }
+      }
+      if (bi < 0) break;
+      row[sg::kAnlFixed + n] = lagf[bi];
+      row[sg::kAnlFixed + K.nCands + n] = bv;
+      lastv = bv;
+      lasti = bi;
+    }
+  }
+  if (HNR >= 1.0) HNR = 0.9999;
+  row[sg::kHNR] = HNR;
+  if (row[sg::kDom] == row[sg::kDom] && HNR == HNR) row[sg::kDomCert] = 1.0 / (1.0 + exp(3.0 * HNR - 1.0));
+}
+
+double g_anl_ms[sg::kAnlStages];  // of the last profiled launch sequence
+
+}  // namespace
+
+namespace sg {
+
+template <typename T>
+void analyze_device(const AnlSetup& A, const T* d_x, const int64_t* offsets, const int64_t* lengths, int64_t n_calls,
+                    double* d_out, const int64_t* out_off, int32_t* frames_out, hipStream_t s, double* kernel_ms) {
+  const SpgSetup& P = A.spg;
+  const int B = P.bins, wl = P.wl;
+  std::vector<AnlSound> snds(n_calls);
+  std::vector<AnlFrame> fr;
+  std::vector<int64_t> lens(n_calls), zoff(n_calls);
+  int64_t cells = 0;
+  for (int64_t c = 0; c < n_calls; ++c) {
+    const int nf = anl_frames(A, lengths[c]);
+    lens[c] = nf ? lengths[c] : 0;  // a sound of exactly wl samples has a spectrogram frame but no analysis
+    zoff[c] = cells;
+    snds[c] = AnlSound{offsets[c], lens[c], cells, out_off[c], nf, 0};
+    frames_out[c] = nf;
+    if ((int64_t)fr.size() + nf > 2147483647LL) throw SgError(SG_E_UNSUPPORTED, "analyze: the frames of one launch exceed 2^31");
+    for (int f = 0; f < nf; ++f) {
+      const int64_t o = spg_frame_start(P, lengths[c], f), a = anl_ampl_start(A, lengths[c], nf, f);
+      if (o < 0 || o + wl > lengths[c] || a < 0 || a + wl + 1 > lengths[c])
+        throw SgError(SG_E_DEVICE, "analyze: a frame leaves its sound");
+      fr.push_back(AnlFrame{o, a, (int32_t)c, f});
+    }
+    cells += (int64_t)nf * B;
+  }
+  if (kernel_ms)
+    for (int k = 0; k < kAnlStages; ++k) kernel_ms[k] = 0;
+  const int64_t F = (int64_t)fr.size();
+  if (F == 0) return;
+  if (A.rowLow < 1 || A.rowHigh > B || A.rowLow > A.rowHigh || A.cut0 < 0 || A.cut0 + A.ncut > B || A.lag0 < 0 ||
+      A.lag0 + A.nlag > wl || B > kSpgMaxBins || A.nCands > kAnlMaxCands)
+    throw SgError(SG_E_DEVICE, "analyze: the setup leaves the frame");
+  DevBuf db;
+  double* d_Z = db.get<double>((size_t)cells);
+  SpgStat* d_stat = db.get<SpgStat>((size_t)n_calls);
+  std::vector<int32_t> b_o(n_calls), f_o(n_calls);
+  struct Stamps {
+    hipEvent_t e[kAnlStages + 1] = {};
+    ~Stamps() {
+      for (hipEvent_t v : e)
+        if (v) (void)hipEventDestroy(v);
+    }
+  } st;
+  int stage = 0;
+  auto stamp = [&]() {
+    if (!kernel_ms) return;
+    MELCHK(hipEventCreate(&st.e[stage]));
+    MELCHK(hipEventRecord(st.e[stage], s));
+    ++stage;
+  };
+  stamp();
+  spectrogram_device<T>(P, d_x, offsets, lens.data(), n_calls, d_Z, zoff.data(), b_o.data(), f_o.data(), s, nullptr,
+                        d_stat);
+  for (int64_t c = 0; c < n_calls; ++c)
+    if (f_o[c] != snds[c].nf) throw SgError(SG_E_DEVICE, "analyze: the spectrogram's frame count differs");
+  const AnlSound* d_snd = upload(db, snds, s);
+  const AnlFrame* d_fr = upload(db, fr, s);
+  const double* d_freq = upload(db, A.freq, s);
+  const double* d_xc = upload(db, A.xc, s);
+  unsigned long long kinf;
+  {
+    const double inf = INFINITY;
+    std::memcpy(&kinf, &inf, 8);
+    kinf |= 0x8000000000000000ull;  // dkey(+Inf)
+  }
+  unsigned long long* d_min = upload(db, std::vector<unsigned long long>(n_calls, kinf), s);
+  AnlK K;
+  K.wl = wl;
+  K.B = B;
+  K.cols = A.cols;
+  K.nCands = A.nCands;
+  K.rowLow = A.rowLow - 1;
+  K.rowHigh = A.rowHigh - 1;
+  K.cut0 = A.cut0;
+  K.ncut = A.ncut;
+  K.pf_idx = A.pf_idx;
+  K.domW = A.domW;
+  K.acW = A.acW;
+  K.lag0 = A.lag0;
+  K.nlag = A.nlag;
+  K.do_dom = A.do_dom;
+  K.do_autocor = A.do_autocor;
+  K.silence = A.silence;
+  K.entropyThres = A.entropyThres;
+  K.domThres = A.domThres;
+  K.autocorThres = A.autocorThres;
+  K.sxx = A.sxx;
+  const dim3 gF((unsigned)F), bT(kT);
+  stamp();  // 1: amplitudes
+  hipLaunchKernelGGL(sg_anl_ampl<T>, gF, bT, 0, s, d_x, d_fr, d_snd, d_stat, wl, A.cols, d_out, d_min);
+  MELCHK(hipGetLastError());
+  stamp();  // 2: descriptives and dom
+  hipLaunchKernelGGL(sg_anl_spec, gF, bT, 0, s, d_fr, d_snd, d_Z, d_freq, d_xc, d_min, K, d_out);
+  MELCHK(hipGetLastError());
+  stamp();  // 3: autocorrelation and its peaks
+  if (A.do_autocor) {
+    const double* d_win = upload(db, spg_window(wl, P.wn), s);
+    const double* d_filt = upload(db, anl_filter(A), s);
+    const double* d_lagf = upload(db, A.lagf, s);
+    const int lds = (wl + 4 + A.nlag) * (int)sizeof(double);
+    if (lds > 48 * 1024)
+      MELCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&sg_anl_acf<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 lds));
+    hipLaunchKernelGGL(sg_anl_acf<T>, gF, bT, (size_t)lds, s, d_x, d_fr, d_snd, d_stat, d_win, d_filt, d_lagf, K, d_out);
+    MELCHK(hipGetLastError());
+  }
+  stamp();
+  MELCHK(hipStreamSynchronize(s));
+  if (kernel_ms)
+    for (int k = 0; k + 1 < stage; ++k) {
+      float ms = 0;
+      MELCHK(hipEventElapsedTime(&ms, st.e[k], st.e[k + 1]));
+      kernel_ms[k] = ms;
+    }
+}
+
+}  // namespace sg
+
+namespace {
+
+template <class F>
+int guarded(sg_ctx* ctx, F&& f) {
+  int code;
+  std::string msg;
+  try {
+    return f();
+  } catch (const sg::SgError& e) {
+    code = e.code;
+    msg = e.what();
+  } catch (const std::bad_alloc&) {
+    code = SG_E_NOMEM;
+    msg = "out of host memory";
+  } catch (const std::exception& e) {
+    code = SG_E_ARG;
+    msg = e.what();
+  }
+  if (ctx) ctx->err = msg;
+  return code;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sg_analyze_frames(sg_ctx* ctx, const double* wave, int64_t len, const sg_analyze_params* p, double* out) {
+  return guarded(ctx, [&]() {
+    if (!ctx || !p || !wave || !out) throw sg::SgError(SG_E_ARG, "sg_analyze_frames: bad arguments");
+    const sg::AnlSetup S = sg::anl_setup(*p);
+    if (len <= S.spg.wl)
+      throw sg::SgError(SG_E_ARG, "sg_analyze_frames: the sound is not longer than the window (the reference's amplitude "
+                                  "window sound[a:(a + wl)] leaves it)");
+    MELCHK(hipSetDevice(ctx->device));
+    const int64_t cells = (int64_t)sg::anl_frames(S, len) * S.cols;
+    sg::DevBuf db;
+    double* d = db.get<double>((size_t)len);
+    double* d_o = db.get<double>((size_t)cells);
+    MELCHK(hipMemcpyAsync(d, wave, (size_t)len * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    MELCHK(hipStreamSynchronize(ctx->stream));
+    const int64_t off = 0;
+    int32_t f = 0;
+    sg::analyze_device<double>(S, d, &off, &len, 1, d_o, &off, &f, ctx->stream, ctx->profiling ? g_anl_ms : nullptr);
+    MELCHK(hipMemcpy(out, d_o, (size_t)cells * sizeof(double), hipMemcpyDeviceToHost));
+    return SG_OK;
+  });
+}
+
+int sg_analyze_frames_batch(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, const int64_t* lengths,
+                            int64_t n_calls, const sg_analyze_params* p, double* d_out, const int64_t* out_off,
+                            int32_t* frames_out) {
+  return guarded(ctx, [&]() {
+    if (!ctx || !p || n_calls < 0 || n_calls > 2147483647LL ||
+        (n_calls > 0 && (!d_wave || !offsets || !lengths || !d_out || !out_off || !frames_out)))
+      throw sg::SgError(SG_E_ARG, "sg_analyze_frames_batch: bad arguments");
+    const sg::AnlSetup S = sg::anl_setup(*p);
+    if (n_calls == 0) return SG_OK;
+    MELCHK(hipSetDevice(ctx->device));
+    sg::analyze_device<float>(S, d_wave, offsets, lengths, n_calls, d_out, out_off, frames_out, ctx->stream,
+                              ctx->profiling ? g_anl_ms : nullptr);
+    return SG_OK;
+  });
+}
+
+int sg_debug_analyze_kernel_ms(double* out) {
+  if (!out) return SG_E_ARG;
+  for (int k = 0; k < sg::kAnlStages; ++k) out[k] = g_anl_ms[k];
+  return SG_OK;
+}
+
+}  // extern "C"

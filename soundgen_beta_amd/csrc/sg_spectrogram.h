@@ -33,12 +33,19 @@ int64_t spg_frame_start(const SpgSetup& S, int64_t len, int i);
 // ftwindow_modif(wl, wn) in R's operation order
 std::vector<double> spg_window(int wl, int wn);
 
+// getFrameBank's normalisation of a sound (device): x -> ((x - mean) / sd) / m when scaled, else x / m
+struct SpgStat {
+  double mean, sd, m, mn, mx;
+  int32_t scaled, pad;
+};
+
 // The launch sequence for n_calls sounds at d_x + offsets[c] (device memory, T =
 // float or double); matrices to d_out + out_off[c] (device memory). kernel_ms
-// (kSpgStages doubles or nullptr): the device time of each stage
+// (kSpgStages doubles or nullptr): the device time of each stage. d_stat_out (device,
+// n_calls entries, or nullptr) receives every sound's normalisation statistics
 template <typename T>
 void spectrogram_device(const SpgSetup& S, const T* d_x, const int64_t* offsets, const int64_t* lengths,
                         int64_t n_calls, double* d_out, const int64_t* out_off, int32_t* bins_out,
-                        int32_t* frames_out, hipStream_t s, double* kernel_ms);
+                        int32_t* frames_out, hipStream_t s, double* kernel_ms, SpgStat* d_stat_out = nullptr);
 
 }  // namespace sg

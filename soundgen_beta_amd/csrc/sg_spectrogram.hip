@@ -68,11 +68,7 @@ struct SpgChunk {
   int32_t snd, c;
 };
 
-// getFrameBank's normalisation: x -> ((x - mean) / sd) / m when scaled, else x / m
-struct SpgStat {
-  double mean, sd, m, mn, mx;
-  int32_t scaled, pad;
-};
+using sg::SpgStat;
 
 // per sound: the smallest positive cell, the maxima after the log and after the
 // subtraction (order-preserving keys), the NaN flag, the entropies' order statistics
@@ -505,7 +501,7 @@ namespace sg {
 template <typename T>
 void spectrogram_device(const SpgSetup& S, const T* d_x, const int64_t* offsets, const int64_t* lengths,
                         int64_t n_calls, double* d_out, const int64_t* out_off, int32_t* bins_out,
-                        int32_t* frames_out, hipStream_t s, double* kernel_ms) {
+                        int32_t* frames_out, hipStream_t s, double* kernel_ms, SpgStat* d_stat_out) {
   const int B = S.bins;
   if (S.processed && S.kTime > B)  // zoo::rollmedian stops for k > length
     throw SgError(SG_E_ARG, "spectrogram: smoothTime is larger than the " + std::to_string(B) + " bins of a frame");
@@ -588,6 +584,8 @@ void spectrogram_device(const SpgSetup& S, const T* d_x, const int64_t* offsets,
     hipLaunchKernelGGL(sg_spg_stats_fold, dim3((NS + 63) / 64), dim3(64), 0, s, d_part, d_snd, (int)n_calls, pass, d_stat);
     MELCHK(hipGetLastError());
   }
+  if (d_stat_out)  // for a caller that goes on with the normalised samples (sg_analyze.hip)
+    MELCHK(hipMemcpyAsync(d_stat_out, d_stat, (size_t)n_calls * sizeof(SpgStat), hipMemcpyDeviceToDevice, s));
   stamp();  // 1: frames
   hipLaunchKernelGGL(sg_spg_roots, dim3((unsigned)((S.N + kT - 1) / kT)), bT, 0, s, d_TN, S.N);
   MELCHK(hipGetLastError());
@@ -681,9 +679,9 @@ void spectrogram_device(const SpgSetup& S, const T* d_x, const int64_t* offsets,
 }
 
 template void spectrogram_device<float>(const SpgSetup&, const float*, const int64_t*, const int64_t*, int64_t, double*,
-                                        const int64_t*, int32_t*, int32_t*, hipStream_t, double*);
+                                        const int64_t*, int32_t*, int32_t*, hipStream_t, double*, SpgStat*);
 template void spectrogram_device<double>(const SpgSetup&, const double*, const int64_t*, const int64_t*, int64_t,
-                                         double*, const int64_t*, int32_t*, int32_t*, hipStream_t, double*);
+                                         double*, const int64_t*, int32_t*, int32_t*, hipStream_t, double*, SpgStat*);
 
 }  // namespace sg
 

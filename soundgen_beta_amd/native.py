@@ -116,6 +116,16 @@ def lib():
         L.sg_spectrogram.argtypes = [vp, dp, i64, spp, dp]
         L.sg_spectrogram_batch.argtypes = [vp, vp, i64p, i64p, i64, spp, vp, i64p, i32p, i32p]
         L.sg_debug_spectrogram_kernel_ms.argtypes = [dp]
+    if hasattr(L, "sg_analyze_frames_size"):  # analyze()'s per-frame stage: likewise additive
+        i32p = C.POINTER(C.c_int32)
+        app = C.POINTER(_abi.sg_analyze_params)
+        L.sg_analyze_frames_size.argtypes = [i64, app, i32p, i32p, i32p, i32p, i32p, i32p, i32p]
+        L.sg_analyze_frames_size_error.argtypes = []
+        L.sg_analyze_frames_size_error.restype = C.c_char_p
+        L.sg_analyze_frames_ampl_starts.argtypes = [i64, app, i64p, C.c_int32]
+        L.sg_analyze_frames.argtypes = [vp, dp, i64, app, dp]
+        L.sg_analyze_frames_batch.argtypes = [vp, vp, i64p, i64p, i64, app, vp, i64p, i32p]
+        L.sg_debug_analyze_kernel_ms.argtypes = [dp]
     L.sg_rrng_create.argtypes = [C.c_int32, C.POINTER(vp)]
     L.sg_rrng_destroy.argtypes = [vp]
     L.sg_rrng_set_seed.argtypes = [vp, C.c_int32]
