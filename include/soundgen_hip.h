@@ -535,6 +535,56 @@ int sg_analyze_frames(sg_ctx* ctx, const double* wave, int64_t len, const sg_ana
 int sg_analyze_frames_batch(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, const int64_t* lengths,
                             int64_t n_calls, const sg_analyze_params* p, double* d_out, const int64_t* out_off,
                             int32_t* frames_out);
+/* pitch_candidates: analyze()'s per-frame stage with all four pitch trackers (an
+ * additive extension of ABI 5): sg_analyze_frames plus the cepstral tracker
+ * (getPitchCep, R/utilities_analyze.R:337-407) and the spectral one (getPitchSpec,
+ * :424-558, a modified BaNa). a: as for sg_analyze_frames, except a.methods: bit 0
+ * 'autocor', bit 1 'dom', bit 2 'cep', bit 3 'spec' (at least one). The formals
+ * after analyze()'s repairs (:343-363; the caller makes them): cepThres, specThres,
+ * specPeak and specSinglePeakCert in [0, 1]; specMerge (semitones) >= 0; specSmooth
+ * in Hz; cepZp in points; cepSmooth NaN = R's NULL (2 * ceiling(31 * samplingRate /
+ * 44100 / 2) - 1). specHNRslope is accepted and unused: analyze() passes HNR = NULL
+ * (:134), so the peak threshold is specPeak. */
+typedef struct sg_pitch_params {
+  sg_analyze_params a;
+  double cepThres;
+  double cepSmooth;
+  double cepZp;
+  double specThres;
+  double specPeak;
+  double specSinglePeakCert;
+  double specHNRslope;
+  double specSmooth;
+  double specMerge;
+} sg_pitch_params;
+/* The integer decisions for a sound of len samples (host only, no device): the
+ * frame count (0 for len <= wl), the columns of a row (15 + 6 nCands: the 15 of
+ * sg_analyze_frames_size, then autocorCand, autocorCert, cepCand, cepCert, specCand,
+ * specCert, nCands each) and, in extra (24 int32 or NULL): wl, bins, lag_first,
+ * lag_last, rowLow, rowHigh, the cut band's first bin and size, pitchFloor_idx,
+ * domSmooth_bins, autocorSmooth (as sg_analyze_frames_size gives them), then L =
+ * length(frameZP) (bins + 2 floor((cepZp - bins) / 2) for cepZp >= bins, else bins),
+ * the effective cepSmooth (* round(cepZp / bins) when padded), l = L %/% 2, the first
+ * row (0-based) and the number of rows of the cepstrum with pitchFloor < samplingRate
+ * / k / 2 * (L / bins) < pitchCeiling, getPitchSpec's width 2 * ceiling((specSmooth /
+ * bin + 1) * 20 / bin / 2) - 1, and zeros. The refusals of sg_analyze_frames_size
+ * hold whatever a.methods is. Where 'cep' is asked for: SG_E_ARG for an even
+ * effective cepSmooth (zoo's even-width alignment is not restated) and for an empty
+ * cepstral band (the reference's rollapply gets an empty series); SG_E_UNSUPPORTED
+ * when L cannot be transformed: L even needs L / 2, L odd needs L itself, 31-smooth
+ * and <= 2048. Where 'spec' is asked for: SG_E_ARG for a width below 1. A smoothing
+ * window wider than its band is not refused: it finds no peak, as in zoo. Errors
+ * through sg_analyze_frames_size_error. */
+int sg_pitch_candidates_size(int64_t len, const sg_pitch_params* p, int32_t* frames, int32_t* cols, int32_t* extra);
+/* Host only: the labels (Hz) of the n = extra[15] rows of the cepstral band. */
+int sg_pitch_candidates_cep_labels(const sg_pitch_params* p, double* labels, int32_t n);
+/* sg_analyze_frames / sg_analyze_frames_batch with rows of 15 + 6 nCands columns.
+ * With a.methods within bits 0..1 the shared columns equal sg_analyze_frames' bit
+ * for bit; the columns of a method not asked for are NaN. */
+int sg_pitch_candidates(sg_ctx* ctx, const double* wave, int64_t len, const sg_pitch_params* p, double* out);
+int sg_pitch_candidates_batch(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, const int64_t* lengths,
+                              int64_t n_calls, const sg_pitch_params* p, double* d_out, const int64_t* out_off,
+                              int32_t* frames_out);
 /* Process-wide policy of the fp64 filter path for later sg_plan_batch calls:
  * mode 0 never, 1 when the conditioning estimate exceeds rho (default 100),
  * 2 every filtered bout. SG_E_ARG for an invalid mode or rho. */
@@ -672,6 +722,10 @@ int sg_debug_spectrogram_kernel_ms(double* out);
  * amplitudes, the spectral descriptives and dom, the autocorrelation and its
  * peaks (4 doubles). */
 int sg_debug_analyze_kernel_ms(double* out);
+/* The same for the last sg_pitch_candidates / sg_pitch_candidates_batch run: the 4
+ * stages above, then the cepstrum and its peaks, then the spectral peaks and the
+ * BaNa candidates (6 doubles; 0 for a stage that was not launched). */
+int sg_debug_pitch_kernel_ms(double* out);
 
 #ifdef __cplusplus
 }

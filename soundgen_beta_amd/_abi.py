@@ -64,6 +64,12 @@ class sg_analyze_params(C.Structure):
         [("wn", C.c_int32), ("methods", C.c_int32)]
 
 
+class sg_pitch_params(C.Structure):
+    _fields_ = [("a", sg_analyze_params)] + \
+        [(f, C.c_double) for f in ("cepThres", "cepSmooth", "cepZp", "specThres", "specPeak", "specSinglePeakCert",
+                                   "specHNRslope", "specSmooth", "specMerge")]
+
+
 NORM_CB = C.CFUNCTYPE(C.c_double, C.c_void_p)
 UNIF_CB = C.CFUNCTYPE(C.c_double, C.c_void_p)
 GAMMA_CB = C.CFUNCTYPE(C.c_double, C.c_void_p, C.c_double, C.c_double)

@@ -26,9 +26,12 @@ What is returned is the stage's output BEFORE the pathfinder, so:
       (:702) comes after the pathfinder and is not applied;
     * quartile25 / 50 / 75 are NOT blanked for unvoiced frames (:689 comes after
       the pathfinder).
-Differences from the reference's defaults: pitchMethods accepts a non-empty subset
-of ('autocor', 'dom'); the reference's default also has 'spec', and 'cep' exists:
-both raise NotImplementedError here (they and the pathfinder are the next step).
+Differences from the reference's defaults: analyze_frames*' pitchMethods accepts a
+non-empty subset of ('autocor', 'dom'); the reference's default also has 'spec', and
+'cep' exists: both raise NotImplementedError there. pitch_candidates* (at the end of
+this module) run all four: getPitchCep (R/utilities_analyze.R:337-407) and getPitchSpec
+(:424-558) restated likewise and on the GPU (sg_anl_cep, sg_anl_bana), plus
+pitch_matrices (the pathfinder's inputs, R/analyze.R:578-591). The pathfinder is not built.
 Formants (phonTools is not in the reference tree), plots, summary and savePath are
 out of scope.
 
@@ -547,3 +550,426 @@ def analyze_frames_batch(data, offsets, lengths, samplingRate, silence=0.04, win
     h = out.cpu().numpy()
     return [_table(h[ooff[i]:ooff[i + 1]].reshape(frames[i], cols), s["nCands"], int(lens[i]), samplingRate, s["step"])
             for i in range(nc)]
+
+
+# ------------------------------------------------- pitch_candidates: 'cep' and 'spec'
+ALL_PITCH_METHODS = ("autocor", "cep", "spec", "dom")
+PITCH_DEFAULT_METHODS = ("autocor", "spec", "dom")  # analyze()'s default (R/analyze.R:191)
+PITCH_KEYS = ("cepCand", "cepCert", "specCand", "specCert")
+# BaNaRatios (R/sysdata.rda): a ratio of two spectral peaks strictly inside (value_low,
+# value_high) says the lower peak is harmonic number divide_lower_by. After Ba, Yang,
+# Demirkol & Heinzelman (2012), "BaNa: A hybrid approach for noise resilient pitch
+# detection", IEEE Statistical Signal Processing Workshop. Rows in the data frame's order.
+BANA_RATIOS = ((1.9, 2.1, 1.0), (2.8, 3.2, 1.0), (1.42, 1.59, 2.0), (3.8, 4.2, 1.0), (1.29, 1.42, 3.0),
+               (4.8, 5.2, 1.0), (2.4, 2.6, 2.0), (1.59, 1.8, 3.0), (1.15, 1.29, 4.0))
+PITCH_SOURCES = ("dom", "autocor", "cep", "spec")  # pitch_matrices' source codes index this
+
+
+def hz_to_semitones(h):
+    """HzToSemitones(), R/utilities_math.R:16-18."""
+    return math.log2(h / 16.3516) * 12
+
+
+def cep_layout(B, samplingRate, pitchFloor, pitchCeiling, cepSmooth, cepZp):
+    """What getPitchCep decides before it sees the frame (R/utilities_analyze.R:346-367)
+    for a B-bin frame: (L, pad, effective cepSmooth, l, first row 0-based, labels of the
+    rows with pitchFloor < freq < pitchCeiling)."""
+    if cepSmooth is None:                                                     # :346-348
+        cepSmooth = 2 * math.ceil(31 * samplingRate / 44100 / 2) - 1
+    if cepZp < B:                                                             # :350-351
+        pad = 0
+    else:
+        pad = int((cepZp - B) / 2)                                            # :353 rep(0, x) truncates x
+        cepSmooth = cepSmooth * round(cepZp / B)                              # :355 R's round: half to even
+    L = B + 2 * pad
+    l = L // 2                                                                # :361
+    lab = [samplingRate / k / 2 * (L / B) for k in range(1, l + 1)]           # :364
+    rows = [i for i, f in enumerate(lab) if f > pitchFloor and f < pitchCeiling]  # :367
+    first = rows[0] if rows else 0
+    return L, pad, cepSmooth, l, first, np.array([lab[i] for i in rows], float)
+
+
+def get_pitch_cep(frame, samplingRate, pitchFloor, pitchCeiling, cepThres, cepSmooth, cepZp, nCands, _trace=None):
+    """getPitchCep(), R/utilities_analyze.R:337-407, on frame / max(frame): (candidates,
+    certainties), best first; ([], []) where the reference makes NULL or one all-NA row
+    (idx[1:0] for no peak, :386). _trace (a dict) receives the band and the comparisons
+    (a, b) behind the discrete decisions."""
+    frame = np.asarray(frame, float)
+    B = len(frame)
+    L, pad, cepSmooth, l, first, freq = cep_layout(B, samplingRate, pitchFloor, pitchCeiling, cepSmooth, cepZp)
+    frameZP = np.concatenate([np.zeros(pad), frame, np.zeros(pad)])           # :350-354
+    cepstrum = np.abs(np.fft.fft(frameZP))                                    # :359
+    cepstrum = cepstrum / cepstrum.max()                                      # :360 over all L values
+    cep = cepstrum[first:first + len(freq)]                                   # :362-367 row i holds cepstrum[i]
+    idx = [i - 1 for i in roll_central_max(cep, int(cepSmooth), cepThres)]    # :371-377
+    if _trace is not None:
+        _trace.update(band=cep, width=int(cepSmooth), order=[], rule18=[])
+    if not idx:
+        return [], []
+    absCepPeak = idx[int(np.argmax(cep[idx]))]                                # :379 which.max: the first maximum
+    keep = [i for i in idx if freq[i] > freq[absCepPeak] / 1.8]               # :381
+    keep.sort(key=lambda i: -cep[i])                                          # :385 order(): stable, earlier first
+    if _trace is not None:
+        o = sorted(cep[idx])
+        _trace["order"] = [(o[i], o[i + 1]) for i in range(len(o) - 1)]
+        _trace["rule18"] = [(freq[i], freq[absCepPeak] / 1.8) for i in idx]
+    keep = keep[:nCands]                                                      # :386
+    cand = [float(freq[i]) for i in keep]
+    cert = [float(cep[i] / (1 + 5 / (1 + math.exp(2 - .25 * hz_to_semitones(freq[i] / pitchFloor)))))
+            for i in keep]                                                    # :400-401, after the ordering
+    return cand, cert
+
+
+def bana_candidates(peaks, pitchFloor, pitchCeiling, specSinglePeakCert, specThres, specMerge, nCands, _trace=None):
+    """getPitchSpec() from its peak table on, R/utilities_analyze.R:461-555. peaks: the
+    frequencies (Hz) of ALL the frame's peaks, ascending. (candidates, certainties)."""
+    tr = _trace if _trace is not None else {}
+    for k in ("ratio", "range", "merge", "thres"):
+        tr.setdefault(k, [])
+    peaks = [float(v) for v in peaks]
+    if len(peaks) == 0:
+        return [], []
+    if len(peaks) == 1:                                                       # :461-472
+        tr["range"] += [(peaks[0], pitchCeiling), (peaks[0], pitchFloor)]
+        if not (peaks[0] < pitchCeiling and peaks[0] > pitchFloor):
+            return [], []
+        pitchCand, pitchAmpl = [peaks[0]], [specSinglePeakCert]
+    else:
+        peaks = peaks[:5]                                                     # :475
+        n = len(peaks)
+        pitchCand = []
+        for i in range(2, n + 1):                                             # :487-496, kept where A > B
+            for j in range(1, n):
+                if not i > j:
+                    continue
+                ratio = peaks[i - 1] / peaks[j - 1]                           # :492
+                for low, high, div in BANA_RATIOS:                            # :503-506 both borders exclusive
+                    tr["ratio"] += [(ratio, low), (ratio, high)]
+                    if ratio > low and ratio < high:
+                        pitchCand.append(peaks[j - 1] / div)
+        for c in pitchCand:
+            tr["range"] += [(c, pitchFloor), (c, pitchCeiling)]
+        pitchCand = sorted(c for c in pitchCand if c > pitchFloor and c < pitchCeiling)  # :511-512
+        if not pitchCand:
+            return [], []
+        specAmplIdx = [1] * len(pitchCand)
+        c = 0
+        while c + 1 < len(pitchCand):                                         # :521-536
+            dist = abs(math.log2(pitchCand[c] / pitchCand[c + 1]))
+            tr["merge"].append((dist, specMerge / 12))
+            if dist < specMerge / 12:
+                specAmplIdx[c] += 1
+                pitchCand[c] = (pitchCand[c] + pitchCand[c + 1]) / 2          # mean(c(running value, next))
+                del pitchCand[c + 1], specAmplIdx[c + 1]
+            else:
+                c += 1
+        pitchAmpl = [specSinglePeakCert + (1 / (1 + math.exp(-(a - 1))) - 0.5) * 2 * (1 - specSinglePeakCert)
+                     for a in specAmplIdx]                                    # :537-539
+        o = sorted(range(len(pitchCand)), key=lambda i: -pitchAmpl[i])        # :544-547 order(): stable
+        pitchCand, pitchAmpl = [pitchCand[i] for i in o], [pitchAmpl[i] for i in o]
+        tr["idx"] = [specAmplIdx[i] for i in o]
+    tr["thres"] += [(a, specThres) for a in pitchAmpl]
+    keep = [i for i in range(len(pitchCand)) if pitchAmpl[i] > specThres][:nCands]  # :550-555
+    return [pitchCand[i] for i in keep], [pitchAmpl[i] for i in keep]
+
+
+def spec_width(specSmooth, bin):
+    """getPitchSpec's rolling width (R/utilities_analyze.R:438)."""
+    return 2 * math.ceil((specSmooth / bin + 1) * 20 / bin / 2) - 1
+
+
+def get_pitch_spec(frame, freq, bin, pitchFloor, pitchCeiling, specSmooth, specPeak, specSinglePeakCert, specThres,
+                   specMerge, nCands, specHNRslope=None, _trace=None):
+    """getPitchSpec(), R/utilities_analyze.R:424-558, on frame / max(frame) with HNR = NULL
+    as analyze() passes it (:134: the threshold is specPeak, specHNRslope unused). freq:
+    1000 * the round-tripped labels (:458). (candidates, certainties), best first."""
+    width = int(spec_width(specSmooth, bin))                                  # :438
+    idx = roll_central_max(frame, width, specPeak)                            # :440-457
+    if _trace is not None:
+        _trace.update(width=width, npeaks=len(idx))
+    return bana_candidates([freq[i - 1] for i in idx], pitchFloor, pitchCeiling, specSinglePeakCert, specThres,
+                           specMerge, nCands, _trace)
+
+
+def repair_pitch(samplingRate, duration=None, pitchMethods=PITCH_DEFAULT_METHODS, cepThres=0.3, cepSmooth=None,
+                 cepZp=0, specThres=0.3, specPeak=0.35, specSinglePeakCert=0.4, specHNRslope=0.8, specSmooth=150,
+                 specMerge=1, **kw):
+    """repair() plus the repairs of R/analyze.R:343-363, with R's warnings; pitchMethods:
+    a non-empty subset of ('autocor', 'cep', 'spec', 'dom')."""
+    if isinstance(pitchMethods, str):
+        pitchMethods = (pitchMethods,)
+    pitchMethods = tuple(pitchMethods)
+    for m in pitchMethods:
+        if m not in ALL_PITCH_METHODS:
+            raise ValueError("pitchMethods must be a subset of %s" % (ALL_PITCH_METHODS,))
+    if not pitchMethods:
+        raise ValueError("pitchMethods must not be empty")
+    s = repair(samplingRate, duration, pitchMethods=PITCH_METHODS, **kw)
+    s["pitchMethods"] = pitchMethods
+    if not _num(cepThres) or cepThres < 0 or cepThres > 1:                    # :343-346
+        cepThres = 0.3
+        warnings.warn('"cepThres" must be between 0 and 1; defaulting to 0.3')
+    if not _num(specThres) or specThres < 0 or specThres > 1:                 # :347-350
+        specThres = 0.3
+        warnings.warn('"specThres" must be between 0 and 1; defaulting to 0.3')
+    if not _num(specPeak) or specPeak < 0 or specPeak > 1:                    # :351-354
+        specPeak = 0.35
+        warnings.warn('"specPeak" must be between 0 and 1; defaulting to 0.35')
+    if not _num(specSinglePeakCert) or specSinglePeakCert < 0 or specSinglePeakCert > 1:  # :355-359
+        specSinglePeakCert = 0.4
+        warnings.warn('"specSinglePeakCert" must be between 0 and 1; defaulting to 0.4')
+    if not _num(specMerge) or specMerge < 0:                                  # :360-363
+        specMerge = 1
+        warnings.warn('"specMerge" must be non-negative; defaulting to 1 semitone')
+    if cepSmooth is not None and not _num(cepSmooth):
+        cepSmooth = None  # !is.numeric(cepSmooth): the default (utilities_analyze.R:346)
+    if not _num(cepZp) or not _num(specSmooth):
+        raise ValueError("cepZp and specSmooth must be numbers")
+    if not _num(specHNRslope):
+        specHNRslope = 0.8  # unused: analyze() passes HNR = NULL
+    s.update(cepThres=cepThres, cepSmooth=cepSmooth, cepZp=cepZp, specThres=specThres, specPeak=specPeak,
+             specSinglePeakCert=specSinglePeakCert, specHNRslope=specHNRslope, specSmooth=specSmooth,
+             specMerge=specMerge)
+    return s
+
+
+PITCH_SIZE_KEYS = ("wl", "bins", "lag_first", "lag_last", "rowLow", "rowHigh", "cut0", "ncut", "pitchFloor_idx",
+                   "domSmooth_bins", "autocorSmooth", "cepL", "cepSmooth", "cepl", "cep0", "ncep", "specWidth")
+
+
+def _transformable(L):
+    M = L if L % 2 else L // 2
+    if M < 1 or M > 2048:
+        return False
+    for p in (2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31):
+        while M % p == 0:
+            M //= p
+    return M == 1
+
+
+def pitch_decisions(length, s):
+    """frame_decisions() plus every integer decision of the two trackers for the
+    repaired settings s (repair_pitch()'s dict): what sg_pitch_candidates_size makes
+    bit-equal. cepf: the labels of the cepstral band."""
+    d = frame_decisions(length, dict(s, pitchMethods=PITCH_METHODS))
+    sr, B = s["samplingRate"], d["bins"]
+    L, pad, cw, l, first, cepf = cep_layout(B, sr, s["pitchFloor"], s["pitchCeiling"], s["cepSmooth"], s["cepZp"])
+    sw = spec_width(s["specSmooth"], sr / 2 / B)
+    whole = cw == int(cw) and 1 <= cw <= 1e9
+    d.update(cols=NFIXED + 6 * s["nCands"], cepL=L, cepSmooth=int(cw) if whole else 0, cepl=l, cep0=first, ncep=len(cepf),
+             specWidth=min(int(sw), 1000000000) if sw >= 1 else 0, cepf=cepf)
+    if "cep" in s["pitchMethods"]:
+        if not _transformable(L):
+            raise native.SoundgenError(-4, "analyze: the cepstrum's %d-point transform is not supported (%s must be at "
+                                       "most 2048 with no prime factor above 31); R's fft() takes any length"
+                                       % (L, "L" if L % 2 else "L / 2"))
+        if not whole or int(cw) % 2 == 0:
+            raise ValueError("analyze: the effective cepSmooth (cepSmooth * round(cepZp / bins) when cepZp pads the "
+                             "frame) must be a whole odd number (zoo's even-width alignment is not restated)")
+        if len(cepf) == 0:
+            raise ValueError("analyze: no row of the cepstrum between pitchFloor and pitchCeiling (rollapply gets an "
+                             "empty series in the reference)")
+    if "spec" in s["pitchMethods"] and sw < 1:
+        raise ValueError("analyze: specSmooth gives getPitchSpec's rolling window a width below 1 (rollapply stops in "
+                         "the reference)")
+    return d
+
+
+def _pitch_args(a):
+    """The formals of pitch_candidates*() as the keyword arguments of repair_pitch()."""
+    return {k: a[k] for k in ("silence", "windowLength", "step", "overlap", "wn", "zp", "cutFreq", "pitchMethods",
+                              "entropyThres", "pitchFloor", "pitchCeiling", "nCands", "domThres", "domSmooth",
+                              "autocorThres", "autocorSmooth", "cepThres", "cepSmooth", "cepZp", "specThres", "specPeak",
+                              "specSinglePeakCert", "specHNRslope", "specSmooth", "specMerge")}
+
+
+def pitch_candidates_numpy(x, samplingRate=None, silence=0.04, windowLength=50, step=None, overlap=50, wn="gaussian",
+                           zp=0, cutFreq=6000, pitchMethods=PITCH_DEFAULT_METHODS, entropyThres=0.6, pitchFloor=75,
+                           pitchCeiling=3500, nCands=1, domThres=0.1, domSmooth=220, autocorThres=0.7,
+                           autocorSmooth=None, cepThres=0.3, cepSmooth=None, cepZp=0, specThres=0.3, specPeak=0.35,
+                           specSinglePeakCert=0.4, specHNRslope=0.8, specSmooth=150, specMerge=1, _probe=None):
+    """analyze_frames_numpy() with all four pitch trackers of analyzeFrame()
+    (R/utilities_analyze.R:71-144): the host restatement pitch_candidates() is compared
+    against. Returns analyze_frames_numpy()'s dict plus cepCand, cepCert, specCand and
+    specCert (frames x nCands, NaN for NA and for a method not asked for).
+    _probe: receives analyze_frames_numpy()'s intermediates and, per tracked frame,
+    the traces of get_pitch_cep / get_pitch_spec (`cep`, `spec`).
+
+    Not built (sequential host logic over these candidates): the prior
+    (R/analyze.R:593-612), findVoicedSegments and the pathfinder, and the pitchAutocor /
+    pitchCep / pitchSpec columns (:659-667), which hinge on what as.numeric does with
+    zero-length list elements and cannot be settled without R."""
+    sound, sr = _input(x, samplingRate)
+    s = repair_pitch(sr, len(sound) / sr, **_pitch_args(locals()))
+    d = pitch_decisions(len(sound), s)
+    base = [m for m in s["pitchMethods"] if m in PITCH_METHODS]
+    probe = {} if _probe is None else _probe
+    kw = {k: s[k] for k in ("silence", "windowLength", "step", "wn", "zp", "cutFreq", "entropyThres", "pitchFloor",
+                            "pitchCeiling", "nCands", "domThres", "domSmooth", "autocorThres", "autocorSmooth")}
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")  # repair_pitch() has warned already
+        # the shared columns; with neither 'autocor' nor 'dom' the stage runs with 'dom' and its columns are blanked
+        t = analyze_frames_numpy(sound, sr, pitchMethods=tuple(base) or ("dom",), _probe=probe, **kw)
+    if not base:
+        for k in ("dom", "domCand", "domCert"):
+            t[k] = np.full_like(t[k], math.nan)
+    nC, frames = s["nCands"], len(t["ampl"])
+    for k in PITCH_KEYS:
+        t[k] = np.full((frames, nC), math.nan)
+    probe.update(d=d, s=s, cep={}, spec={})
+    freq, bin_ = probe["freq"], sr / 2 / d["bins"]
+    for f in np.nonzero(t["cond_entropy"] == 1)[0]:
+        normed = probe["normed"][int(f)]                                      # utilities_analyze.R:72
+        if "cep" in s["pitchMethods"]:                                        # :116-126
+            tr = probe["cep"][int(f)] = {}
+            cand, cert = get_pitch_cep(normed, sr, s["pitchFloor"], s["pitchCeiling"], s["cepThres"], s["cepSmooth"],
+                                       s["cepZp"], nC, tr)
+            t["cepCand"][f, :len(cand)], t["cepCert"][f, :len(cert)] = cand, cert
+        if "spec" in s["pitchMethods"]:                                       # :129-144
+            tr = probe["spec"][int(f)] = {}
+            cand, cert = get_pitch_spec(normed, freq, bin_, s["pitchFloor"], s["pitchCeiling"], s["specSmooth"],
+                                        s["specPeak"], s["specSinglePeakCert"], s["specThres"], s["specMerge"], nC,
+                                        s["specHNRslope"], tr)
+            t["specCand"][f, :len(cand)], t["specCert"][f, :len(cert)] = cand, cert
+    return t
+
+
+def _pitch_params(s):
+    from . import _abi
+    m = s["pitchMethods"]
+    P = _abi.sg_pitch_params()
+    P.a = _params(dict(s, pitchMethods=()))
+    P.a.methods = sum(b for k, b in (("autocor", 1), ("dom", 2), ("cep", 4), ("spec", 8)) if k in m)
+    c = s["cepSmooth"]
+    P.cepThres, P.cepSmooth, P.cepZp = float(s["cepThres"]), math.nan if c is None else float(c), float(s["cepZp"])
+    P.specThres, P.specPeak, P.specSinglePeakCert = float(s["specThres"]), float(s["specPeak"]), float(s["specSinglePeakCert"])
+    P.specHNRslope, P.specSmooth, P.specMerge = float(s["specHNRslope"]), float(s["specSmooth"]), float(s["specMerge"])
+    return P
+
+
+def pitch_decisions_native(length, s):
+    """sg_pitch_candidates_size and sg_pitch_candidates_cep_labels (host only): the library's pitch_decisions()."""
+    L = native.lib()
+    P = _pitch_params(s)
+    frames, cols = C.c_int32(), C.c_int32()
+    extra = (C.c_int32 * 24)()
+    rc = L.sg_pitch_candidates_size(int(length), C.byref(P), C.byref(frames), C.byref(cols), extra)
+    if rc < 0:
+        _raise(rc, L.sg_analyze_frames_size_error().decode())
+    d = dict(zip(PITCH_SIZE_KEYS, extra))
+    d.update(frames=frames.value, cols=cols.value)
+    lab = np.zeros(max(d["ncep"], 1))
+    rc = L.sg_pitch_candidates_cep_labels(C.byref(P), lab.ctypes.data_as(C.POINTER(C.c_double)), d["ncep"])
+    if rc < 0:
+        _raise(rc, L.sg_analyze_frames_size_error().decode())
+    d["cepf"] = lab[:d["ncep"]]
+    return d
+
+
+def _pitch_table(m, nC, length, sr, step):
+    t = _table(m, nC, length, sr, step)
+    for i, k in enumerate(PITCH_KEYS):
+        t[k] = m[:, NFIXED + (2 + i) * nC:NFIXED + (3 + i) * nC].copy()
+    return t
+
+
+def pitch_candidates(x, samplingRate=None, silence=0.04, windowLength=50, step=None, overlap=50, wn="gaussian", zp=0,
+                     cutFreq=6000, pitchMethods=PITCH_DEFAULT_METHODS, entropyThres=0.6, pitchFloor=75,
+                     pitchCeiling=3500, nCands=1, domThres=0.1, domSmooth=220, autocorThres=0.7, autocorSmooth=None,
+                     cepThres=0.3, cepSmooth=None, cepZp=0, specThres=0.3, specPeak=0.35, specSinglePeakCert=0.4,
+                     specHNRslope=0.8, specSmooth=150, specMerge=1, device=0):
+    """The per-frame stage of analyze() with all four pitch trackers on the GPU
+    (sg_pitch_candidates, fp64): analyze_frames()'s dict plus cepCand, cepCert
+    (getPitchCep, R/utilities_analyze.R:337-407), specCand and specCert (getPitchSpec,
+    :424-558), frames x nCands, NaN for NA and for a method not asked for. pitchMethods:
+    a non-empty subset of ('autocor', 'cep', 'spec', 'dom'); the default is analyze()'s.
+    With pitchMethods within ('autocor', 'dom') the shared keys equal analyze_frames()'
+    bit for bit. Not built: see pitch_candidates_numpy()."""
+    sound, sr = _input(x, samplingRate)
+    s = repair_pitch(sr, len(sound) / sr, **_pitch_args(locals()))
+    d = pitch_decisions_native(len(sound), s)
+    if len(sound) <= d["wl"]:
+        raise _too_short(len(sound), d["wl"])
+    ctx = native.default_context(device)
+    sound = np.ascontiguousarray(sound)
+    out = np.zeros(d["frames"] * d["cols"])
+    dp = C.POINTER(C.c_double)
+    P = _pitch_params(s)
+    _check(native.lib().sg_pitch_candidates(ctx.ptr, sound.ctypes.data_as(dp), len(sound), C.byref(P),
+                                            out.ctypes.data_as(dp)), ctx.ptr)
+    return _pitch_table(out.reshape(d["frames"], d["cols"]), s["nCands"], len(sound), sr, s["step"])
+
+
+def pitch_candidates_batch(data, offsets, lengths, samplingRate, silence=0.04, windowLength=50, step=None, overlap=50,
+                           wn="gaussian", zp=0, cutFreq=6000, pitchMethods=PITCH_DEFAULT_METHODS, entropyThres=0.6,
+                           pitchFloor=75, pitchCeiling=3500, nCands=1, domThres=0.1, domSmooth=220, autocorThres=0.7,
+                           autocorSmooth=None, cepThres=0.3, cepSmooth=None, cepZp=0, specThres=0.3, specPeak=0.35,
+                           specSinglePeakCert=0.4, specHNRslope=0.8, specSmooth=150, specMerge=1, to_host=False,
+                           device=0):
+    """pitch_candidates(call i, samplingRate, ...) for a batch of sounds already in HBM,
+    laid out and returned as analyze_frames_batch() does (sg_pitch_candidates_batch, one
+    launch sequence, tables left in HBM). A row has 15 + 6 nCands columns: `columns`
+    names the fixed ones, then nCands each of autocorCand, autocorCert, cepCand,
+    cepCert, specCand, specCert. to_host=True returns the list of per-call dicts
+    pitch_candidates() returns."""
+    import torch
+    s = repair_pitch(samplingRate, None, **_pitch_args(locals()))
+    L = native.lib()
+    P = _pitch_params(s)
+    offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64))
+    nc, nC = len(offs), s["nCands"]
+    fr, cl = C.c_int32(), C.c_int32()
+    frames = []
+    for n in lens:  # the setup of the last parameters is cached in the library: one cheap call per sound
+        rc = L.sg_pitch_candidates_size(int(n), C.byref(P), C.byref(fr), C.byref(cl), None)
+        if rc < 0:
+            _raise(rc, L.sg_analyze_frames_size_error().decode())
+        frames.append(fr.value)
+    cols = NFIXED + 6 * nC
+    ooff = np.concatenate([[0], np.cumsum([f * cols for f in frames])]).astype(np.int64)
+    ctx = native.default_context(device)
+    out = torch.empty(max(int(ooff[-1]), 1), dtype=torch.float64, device=data.device)
+    fo = np.zeros(max(nc, 1), dtype=np.int32)
+    i64p, i32p = C.POINTER(C.c_int64), C.POINTER(C.c_int32)
+    torch.cuda.synchronize(data.device)  # the library runs on its own stream
+    _check(L.sg_pitch_candidates_batch(ctx.ptr, C.c_void_p(data.data_ptr()), offs.ctypes.data_as(i64p),
+                                       lens.ctypes.data_as(i64p), nc, C.byref(P), C.c_void_p(out.data_ptr()),
+                                       ooff.ctypes.data_as(i64p), fo.ctypes.data_as(i32p)), ctx.ptr)
+    if [int(f) for f in fo[:nc]] != frames:
+        raise native.SoundgenError(-1, "sg_pitch_candidates_batch: frame counts disagree with sg_pitch_candidates_size")
+    if not to_host:
+        names = sum((((k,) * nC) for k in ("autocorCand", "autocorCert") + PITCH_KEYS), ())
+        return dict(out=out, offsets=ooff[:-1].copy(), frames=frames, cols=cols, columns=COLUMNS + names)
+    h = out.cpu().numpy()
+    return [_pitch_table(h[ooff[i]:ooff[i + 1]].reshape(frames[i], cols), nC, int(lens[i]), samplingRate, s["step"])
+            for i in range(nc)]
+
+
+def pitch_matrices(table):
+    """The pathfinder's inputs of R/analyze.R:578-591 from a pitch_candidates() table
+    (host only): (pitchCands, pitchCert, pitchSource, names), each rows x frames with
+    rows = max(1, the largest number of candidates a frame has), NaN-filled (pitchSource:
+    small ints indexing `names`, -1 where there is no candidate). A frame's non-NA
+    candidates are packed in the order analyzeFrame() rbinds them: dom, autocor[.],
+    cep[.], spec[.].
+
+    Known difference: the reference's 1:0 quirks (idx[1:0], pitchSpec_array[1:0, ]) can
+    leave an extra all-NA row in a frame's pitch_array; such rows carry no candidate
+    (:589-591 blank them) but can add an all-NA row to the matrices. They are not
+    reproduced. The prior (:593-612) and everything after it is not built."""
+    frames = len(table["ampl"])
+    per = []
+    for f in range(frames):
+        rows = [(table["domCand"][f], table["domCert"][f], 0)]
+        for src, key in ((1, "autocor"), (2, "cep"), (3, "spec")):
+            if key + "Cand" in table:
+                rows += [(c, a, src) for c, a in zip(table[key + "Cand"][f], table[key + "Cert"][f])]
+        per.append([r for r in rows if not math.isnan(r[0])])
+    n = max([len(p) for p in per] + [1])
+    cands, cert = np.full((n, frames), math.nan), np.full((n, frames), math.nan)
+    source = np.full((n, frames), -1, dtype=np.int8)
+    for f, p in enumerate(per):
+        for i, (c, a, src) in enumerate(p):
+            cands[i, f], cert[i, f], source[i, f] = c, a, src
+    return cands, cert, source, PITCH_SOURCES

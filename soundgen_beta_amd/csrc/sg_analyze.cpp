@@ -5,6 +5,9 @@
 // utilities_analyze.R:52-53, :216; the amplitude windows :456-459; the smoothing
 // widths, utilities_analyze.R:206, :268; the lag range :262-263), the refusals, and
 // the autocorrelation filter (:403-407). sg_analyze_frames_size needs no device.
+// pitch_setup adds the decisions of getPitchCep (utilities_analyze.R:346-367: the
+// padded length, the effective cepSmooth, the band and its labels) and getPitchSpec
+// (:438: the width) for sg_pitch_candidates_size, which needs no device either.
 // The numpy restatement (soundgen_beta_amd/analyze.py) makes the same decisions in
 // the same operation order, so no product and sum may fuse here.
 #pragma clang fp contract(off)
@@ -66,7 +69,10 @@ bool in01(double v) { return v >= 0 && v <= 1; }
 
 }  // namespace
 
-AnlSetup anl_setup(const sg_analyze_params& p) {
+namespace {
+
+// anl_setup for the methods in `allowed` (bit 0 'autocor', 1 'dom', 2 'cep', 3 'spec')
+AnlSetup anl_setup_m(const sg_analyze_params& p, int allowed) {
   AnlSetup S;
   sg_spectrogram_params q;
   std::memset(&q, 0, sizeof q);
@@ -86,7 +92,9 @@ AnlSetup anl_setup(const sg_analyze_params& p) {
     throw SgError(SG_E_ARG, "analyze: silence, entropyThres, domThres and autocorThres must lie in [0, 1]");
   if (!(p.cutFreq > 0) || !(p.pitchFloor > 0) || !(p.pitchFloor <= p.pitchCeiling) || !(p.pitchCeiling <= sr / 2))
     throw SgError(SG_E_ARG, "analyze: cutFreq and pitchFloor must be positive and pitchFloor <= pitchCeiling <= samplingRate / 2");
-  if (p.methods < 1 || p.methods > 3) throw SgError(SG_E_ARG, "analyze: pitchMethods must be a non-empty subset of 'autocor', 'dom'");
+  if (p.methods < 1 || (p.methods & ~allowed))
+    throw SgError(SG_E_ARG, allowed == 3 ? "analyze: pitchMethods must be a non-empty subset of 'autocor', 'dom'"
+                                         : "analyze: pitchMethods must be a non-empty subset of 'autocor', 'dom', 'cep', 'spec'");
   if (!(p.nCands >= 1) || p.nCands != std::floor(p.nCands)) throw SgError(SG_E_ARG, "analyze: nCands must be a whole number >= 1");
   const double zp = std::isnan(p.zp) ? 0.0 : p.zp;
   if (std::floor((zp - wl) / 2) * 2 > 0)
@@ -158,6 +166,87 @@ AnlSetup anl_setup(const sg_analyze_params& p) {
     S.xc[k] = S.freq[S.cut0 + k] - m;
     S.sxx += S.xc[k] * S.xc[k];
   }
+  return S;
+}
+
+// every prime factor of n is <= 31 (the radices of fft64)
+bool smooth31(int n) {
+  for (int p : {2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31})
+    while (n % p == 0) n /= p;
+  return n == 1;
+}
+
+}  // namespace
+
+AnlSetup anl_setup(const sg_analyze_params& p) { return anl_setup_m(p, 3); }
+
+PitchSetup pitch_setup(const sg_pitch_params& p) {
+  PitchSetup S;
+  static_cast<AnlSetup&>(S) = anl_setup_m(p.a, 15);
+  const double sr = S.spg.sr;
+  const int B = S.spg.bins;
+  if (!in01(p.cepThres) || !in01(p.specThres) || !in01(p.specPeak) || !in01(p.specSinglePeakCert))
+    throw SgError(SG_E_ARG, "analyze: cepThres, specThres, specPeak and specSinglePeakCert must lie in [0, 1]");
+  if (!(p.specMerge >= 0)) throw SgError(SG_E_ARG, "analyze: specMerge must be non-negative");
+  if (std::isnan(p.specSmooth) || std::isnan(p.cepZp)) throw SgError(SG_E_ARG, "analyze: specSmooth and cepZp must be numbers");
+  S.do_cep = (p.a.methods >> 2) & 1;
+  S.do_spec = (p.a.methods >> 3) & 1;
+  S.cols = kAnlFixed + 6 * S.nCands;
+  S.pitchFloor = p.a.pitchFloor;
+  S.pitchCeiling = p.a.pitchCeiling;
+  S.cepThres = p.cepThres;
+  S.specThres = p.specThres;
+  S.specPeak = p.specPeak;
+  S.specSinglePeakCert = p.specSinglePeakCert;
+  S.specMerge = p.specMerge;
+  // getPitchCep :346-356
+  double cw = std::isnan(p.cepSmooth) ? 2 * std::ceil(31 * sr / 44100 / 2) - 1 : p.cepSmooth;
+  double Ld = B;
+  if (!(p.cepZp < B)) {
+    const double pad = std::trunc((p.cepZp - B) / 2);  // rep(0, x) truncates x
+    if (pad > 1e6) throw SgError(SG_E_UNSUPPORTED, "analyze: cepZp is too large");
+    S.cepPad = (int)pad;
+    Ld = B + 2 * pad;
+    cw = cw * std::nearbyint(p.cepZp / B);  // R's round(): half to even
+  }
+  S.cepL = (int)Ld;
+  S.cepl = S.cepL / 2;
+  S.cepW = cw >= 1 && cw <= 1e9 && cw == std::floor(cw) ? (int)cw : 0;
+  // :361-367 freq = samplingRate / (1:l) / 2 * (length(frameZP) / length(frame))
+  const double scale = Ld / (double)B;
+  int k0 = 0, k1 = 0;
+  for (int k = 1; k <= S.cepl; ++k) {
+    const double f = sr / k / 2 * scale;
+    if (f > p.a.pitchFloor && f < p.a.pitchCeiling) {
+      if (!k0) k0 = k;
+      k1 = k;
+    }
+  }
+  S.cep0 = k0 ? k0 - 1 : 0;
+  S.ncep = k0 ? k1 - k0 + 1 : 0;
+  S.cepf.resize(S.ncep);
+  for (int i = 0; i < S.ncep; ++i) S.cepf[i] = sr / (k0 + i) / 2 * scale;
+  // getPitchSpec :438
+  const double bin = sr / 2 / B;
+  const double sw = 2 * std::ceil((p.specSmooth / bin + 1) * 20 / bin / 2) - 1;
+  S.specW = sw > 1e9 ? 1000000000 : sw >= 1 ? (int)sw : 0;
+  if (S.do_cep) {
+    // the transform first: a cepZp beyond it is unsupported whatever cepSmooth it implies
+    const int L = S.cepL, M = L % 2 ? L : L / 2;
+    if (M < 1 || M > kSpgMaxBins || !smooth31(M))
+      throw SgError(SG_E_UNSUPPORTED, "analyze: the cepstrum's " + std::to_string(L) + "-point transform is not supported (" +
+                                          (L % 2 ? "L" : "L / 2") + " = " + std::to_string(M) +
+                                          " must be at most 2048 with no prime factor above 31); R's fft() takes any length");
+    if (!S.cepW || S.cepW % 2 == 0)
+      throw SgError(SG_E_ARG, "analyze: the effective cepSmooth (cepSmooth * round(cepZp / bins) when cepZp pads the frame) "
+                              "must be a whole odd number (zoo's even-width alignment is not restated)");
+    if (!S.ncep)
+      throw SgError(SG_E_ARG, "analyze: no row of the cepstrum between pitchFloor and pitchCeiling (rollapply gets an empty "
+                              "series in the reference)");
+  }
+  if (S.do_spec && !S.specW)
+    throw SgError(SG_E_ARG, "analyze: specSmooth gives getPitchSpec's rolling window a width below 1 (rollapply stops in the "
+                            "reference)");
   return S;
 }
 
@@ -251,6 +340,52 @@ extern "C" int sg_analyze_frames_ampl_starts(int64_t len, const sg_analyze_param
     const int frames = sg::anl_frames(S, len);
     if (n > frames) throw sg::SgError(SG_E_ARG, "sg_analyze_frames_ampl_starts: n exceeds the frame count");
     for (int f = 0; f < n; ++f) starts[f] = sg::anl_ampl_start(S, len, frames, f);
+  });
+}
+
+namespace {
+thread_local sg_pitch_params g_last_pp;
+thread_local sg::PitchSetup g_last_PS;
+thread_local bool g_have_p = false;
+
+const sg::PitchSetup& cached_pitch_setup(const sg_pitch_params& p) {
+  if (!g_have_p || std::memcmp(&p, &g_last_pp, sizeof p) != 0) {
+    g_have_p = false;
+    g_last_PS = sg::pitch_setup(p);
+    g_last_pp = p;
+    g_have_p = true;
+  }
+  return g_last_PS;
+}
+}  // namespace
+
+extern "C" int sg_pitch_candidates_size(int64_t len, const sg_pitch_params* p, int32_t* frames, int32_t* cols,
+                                        int32_t* extra) {
+  if (!p || !frames || !cols) {
+    g_anl_err = "sg_pitch_candidates_size: bad arguments";
+    return SG_E_ARG;
+  }
+  return size_guard([&]() {
+    const sg::PitchSetup& S = cached_pitch_setup(*p);
+    *frames = sg::anl_frames(S, len);
+    *cols = S.cols;
+    if (extra) {
+      const int32_t e[24] = {S.spg.wl, S.spg.bins, S.lag0, S.lag0 + S.nlag - 1, S.rowLow, S.rowHigh, S.cut0, S.ncut,
+                             S.pf_idx, S.domW, S.acW, S.cepL, S.cepW, S.cepl, S.cep0, S.ncep, S.specW};
+      std::memcpy(extra, e, sizeof e);
+    }
+  });
+}
+
+extern "C" int sg_pitch_candidates_cep_labels(const sg_pitch_params* p, double* labels, int32_t n) {
+  if (!p || (n > 0 && !labels)) {
+    g_anl_err = "sg_pitch_candidates_cep_labels: bad arguments";
+    return SG_E_ARG;
+  }
+  return size_guard([&]() {
+    const sg::PitchSetup& S = cached_pitch_setup(*p);
+    if (n > S.ncep) throw sg::SgError(SG_E_ARG, "sg_pitch_candidates_cep_labels: n exceeds the band");
+    for (int i = 0; i < n; ++i) labels[i] = S.cepf[i];
   });
 }
 

@@ -42,8 +42,28 @@ int64_t anl_ampl_start(const AnlSetup& S, int64_t len, int frames, int f);
 // autoCorrelation_filter (:403-407) at the used lags, fp64
 std::vector<double> anl_filter(const AnlSetup& S);
 
+// pitch_candidates: the stage plus the cepstral and the spectral (BaNa) tracker
+// (getPitchCep, R/utilities_analyze.R:337-407; getPitchSpec, :424-558). A row then has
+// kAnlFixed + 6 nCands columns: autocorCand, autocorCert, cepCand, cepCert, specCand, specCert.
+constexpr int kPitchStages = 6;  // sg_debug_pitch_kernel_ms: the four of analyze_frames, cepstrum, BaNa
+struct PitchSetup : AnlSetup {
+  int do_cep = 0, do_spec = 0;
+  double pitchFloor = 0, pitchCeiling = 0;
+  double cepThres = 0, specThres = 0, specPeak = 0, specSinglePeakCert = 0, specMerge = 0;
+  int cepL = 0;            // length(frameZP): bins + 2 floor((cepZp - bins) / 2), or bins
+  int cepPad = 0;          // zeros on either side of the frame
+  int cepW = 0;            // the effective cepSmooth (after * round(cepZp / bins))
+  int cepl = 0;            // L %/% 2 rows of the cepstrum are labelled
+  int cep0 = 0, ncep = 0;  // rows [cep0, cep0 + ncep) (0-based: quefrency cep0 + 1 ...) lie in (pitchFloor, pitchCeiling)
+  std::vector<double> cepf;  // their labels samplingRate / k / 2 * (L / bins)
+  int specW = 0;           // getPitchSpec's width
+};
+PitchSetup pitch_setup(const sg_pitch_params& p);
+
+// pitch: nullptr for analyze_frames (S is then a plain AnlSetup), else S itself
 template <typename T>
 void analyze_device(const AnlSetup& S, const T* d_x, const int64_t* offsets, const int64_t* lengths, int64_t n_calls,
-                    double* d_out, const int64_t* out_off, int32_t* frames_out, hipStream_t s, double* kernel_ms);
+                    double* d_out, const int64_t* out_off, int32_t* frames_out, hipStream_t s, double* kernel_ms,
+                    const PitchSetup* pitch = nullptr);
 
 }  // namespace sg

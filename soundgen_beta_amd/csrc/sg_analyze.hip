@@ -16,6 +16,13 @@
 //                 in LDS, acf() at the lags getPitchAutocor reads (direct sums, four
 //                 consecutive lags per thread), / the filter table (:479-481), then
 //                 getPitchAutocor (:250-324) and the dom certainty (:151-159)
+// pitch_candidates (sg_pitch_candidates*) runs the same sequence on rows that also hold
+// cepCand, cepCert, specCand, specCert (nCands each) and adds, each only if its method
+// is asked for, one workgroup per cond_entropy frame:
+//   sg_anl_cep    getPitchCep (utilities_analyze.R:337-407): frame / max zero-padded,
+//                 a second transform through fft64, |C_k| / max, the peaks, the 1.8 rule
+//   sg_anl_bana   getPitchSpec (:424-558): the five lowest spectral peaks, then
+//                 sg::bana_candidates (sg_bana.h) in one thread
 // Cumulative sums run in index order: a thread sums a contiguous run, one thread
 // folds the 256 run sums in order, and the runs are rescanned from their offsets,
 // so a frame's result does not depend on the launch it is in.
@@ -28,7 +35,9 @@
 #include <vector>
 
 #include "sg_analyze.h"
+#include "sg_bana.h"
 #include "sg_ctx.h"
+#include "sg_fft64_dev.h"
 #include "sg_mel_dev.h"
 #include "sg_rmath.h"
 
@@ -39,6 +48,7 @@ using sg::SpgStat;
 using sg::upload;
 
 constexpr int kT = 256;
+static_assert(SG_F64_THREADS == kT, "fft64 strides by SG_F64_THREADS");
 
 struct AnlSound {
   int64_t base, len;  // samples [base, base + len) of the input buffer
@@ -397,7 +407,190 @@ __global__ __launch_bounds__(kT) void sg_anl_acf(const T* __restrict__ x, const 
   if (row[sg::kDom] == row[sg::kDom] && HNR == HNR) row[sg::kDomCert] = 1.0 / (1.0 + exp(3.0 * HNR - 1.0));
 }
 
+// the constants of the two trackers pitch_candidates adds
+struct PitchK {
+  int B, cols, nCands;
+  int L, M, odd, pad;  // the cepstrum's transform: L points, as M = L / 2 packed pairs (L even) or M = L complex points
+  int l, c0, nc, cepW, specW;
+  double cepThres, specPeak;
+  sg::BanaPars bana;  // carries pitchFloor
+};
+
+__global__ __launch_bounds__(kT) void sg_anl_roots(double2* __restrict__ TN, int N) {
+  const int t = blockIdx.x * kT + threadIdx.x;
+  if (t < N) TN[t] = root64(t, N);
+}
+
+// getPitchCep (R/utilities_analyze.R:337-407) for one cond_entropy frame: abs(fft(c(zp,
+// frame / max(frame), zp))) / its maximum, the rows with pitchFloor < label < pitchCeiling,
+// the peaks, the 1.8 rule, the order, the discount. Row i (1-based) of the reference's
+// table holds DFT bin i - 1 and is labelled samplingRate / i / 2 * (L / B); cepf holds
+// the labels of the band's rows, which are bins [c0, c0 + nc).
+// LDS: two M-point buffers, fft64's 32 radix roots, l + 1 doubles (|C_k|, k <= L / 2:
+// by conjugate symmetry they hold the maximum over all L bins)
+__global__ __launch_bounds__(kT) void sg_anl_cep(const AnlFrame* __restrict__ frames, const AnlSound* __restrict__ snds,
+                                                 const double* __restrict__ Z, const double2* __restrict__ TN,
+                                                 const double* __restrict__ cepf, PitchK K, double* __restrict__ out) {
+  extern __shared__ double2 lds_cep[];
+  __shared__ double red[kT];
+  __shared__ int npk;
+  const int M = K.M, B = K.B, nl = K.nc;
+  double2* a = lds_cep;
+  double2* b = a + M;
+  double2* rt = b + M;
+  double* cep = reinterpret_cast<double*>(rt + 32);
+  const AnlFrame F = frames[blockIdx.x];
+  const AnlSound S = snds[F.snd];
+  double* row = out + S.row0 + (int64_t)F.f * K.cols;
+  if (row[sg::kCondEntropy] != 1.0) return;  // workgroup-uniform; written by sg_anl_spec
+  const double* z = Z + S.z0 + (int64_t)F.f * B;
+  double mx = -INFINITY;
+  for (int i = threadIdx.x; i < B; i += kT) mx = fmax(mx, z[i]);
+  mx = block_reduce(mx, 2, red);
+  if (K.odd) {
+    for (int n = threadIdx.x; n < M; n += kT) {
+      const int j = n - K.pad;
+      a[n] = make_double2(j >= 0 && j < B ? z[j] / mx : 0.0, 0.0);
+    }
+  } else {
+    for (int n = threadIdx.x; n < M; n += kT) {
+      const int j = 2 * n - K.pad;
+      a[n] = make_double2(j >= 0 && j < B ? z[j] / mx : 0.0, j + 1 >= 0 && j + 1 < B ? z[j + 1] / mx : 0.0);
+    }
+  }
+  if (threadIdx.x == 0) npk = 0;
+  __syncthreads();
+  fft64(a, b, M, TN, rt, false);
+  if (K.odd) {
+    for (int k = threadIdx.x; k <= K.l; k += kT) cep[k] = hypot(a[k].x, a[k].y);
+  } else {
+    // X_k = E_k + W_L^k O_k as in sg_spg_frames; X_M = Re Z_0 - Im Z_0
+    for (int k = threadIdx.x; k <= M; k += kT) {
+      if (k == M) {
+        cep[k] = fabs(a[0].x - a[0].y);
+        continue;
+      }
+      const double2 p = a[k], q = a[k == 0 ? 0 : M - k], w = TN[k];
+      const double2 e = make_double2(0.5 * (p.x + q.x), 0.5 * (p.y - q.y));
+      const double2 o = make_double2(0.5 * (p.y + q.y), -0.5 * (p.x - q.x));
+      const double re = e.x + (o.x * w.x - o.y * w.y), im = e.y + (o.x * w.y + o.y * w.x);
+      cep[k] = hypot(re, im);
+    }
+  }
+  __syncthreads();
+  double cm = -INFINITY;
+  for (int k = threadIdx.x; k <= K.l; k += kT) cm = fmax(cm, cep[k]);
+  cm = block_reduce(cm, 2, red);
+  double* amp = cep + K.c0;  // host: c0 + nc <= l
+  for (int i = threadIdx.x; i < nl; i += kT) amp[i] = amp[i] / cm;
+  __syncthreads();
+  // the peaks, as in sg_anl_acf: an unordered list, every use decided by (value, index)
+  int* pk = reinterpret_cast<int*>(lds_cep);  // a and b are dead
+  const int h = K.cepW / 2;
+  for (int c = h + threadIdx.x; c < nl - h; c += kT) {
+    const double v = amp[c];
+    if (!(v > K.cepThres)) continue;
+    bool ok = true;
+    for (int j = c - h; j < c && ok; ++j) ok = amp[j] < v || amp[j] != amp[j];
+    for (int j = c + 1; j <= c + h && ok; ++j) ok = amp[j] <= v || amp[j] != amp[j];
+    if (ok) pk[atomicAdd(&npk, 1)] = c;  // at most nc <= l <= 2 M entries of 4 bytes in 32 M bytes
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const int P = npk;
+  if (P == 0) return;
+  // absCepPeak = idx[which.max(cep[idx])]: the first maximum in index order
+  double pmax = -INFINITY;
+  int ibest = nl;
+  for (int q = 0; q < P; ++q) {
+    const int i = pk[q];
+    const double v = amp[i];
+    if (v > pmax || (v == pmax && i < ibest)) {
+      pmax = v;
+      ibest = i;
+    }
+  }
+  const double cutf = cepf[ibest] / 1.8;
+  double lastv = INFINITY;
+  int lasti = -1;
+  const int c1 = sg::kAnlFixed + 2 * K.nCands;
+  for (int n = 0; n < K.nCands; ++n) {  // order(cep, decreasing = TRUE): the earlier row on ties
+    int bi = -1;
+    double bv = -INFINITY;
+    for (int q = 0; q < P; ++q) {
+      const int i = pk[q];
+      const double v = amp[i];
+      if (!(cepf[i] > cutf)) continue;
+      if (!(v < lastv || (v == lastv && i > lasti))) continue;  // already taken
+      if (bi < 0 || v > bv || (v == bv && i < bi)) {
+        bi = i;
+        bv = v;
+      }
+    }
+    if (bi < 0) break;
+    const double cand = cepf[bi];
+    // :400-401 the discount, after the ordering; HzToSemitones(h) = log2(h / 16.3516) * 12
+    const double st = log2((cand / K.bana.pitchFloor) / 16.3516) * 12;
+    const double den = __dadd_rn(1.0, 5 / __dadd_rn(1.0, exp(__dsub_rn(2.0, __dmul_rn(.25, st)))));
+    row[c1 + n] = cand;
+    row[c1 + K.nCands + n] = bv / den;
+    lastv = bv;
+    lasti = bi;
+  }
+}
+
+// getPitchSpec (R/utilities_analyze.R:424-558) for one cond_entropy frame: the peaks
+// of frame / max(frame) in centred windows of specW bins above specPeak (HNR = NULL,
+// :134), the five lowest of them found in index order, then sg::bana_candidates
+__global__ __launch_bounds__(kT) void sg_anl_bana(const AnlFrame* __restrict__ frames, const AnlSound* __restrict__ snds,
+                                                  const double* __restrict__ Z, const double* __restrict__ freq,
+                                                  PitchK K, double* __restrict__ out) {
+  __shared__ double fr[sg::kSpgMaxBins];
+  __shared__ double red[kT];
+  __shared__ int redi[kT];
+  const int B = K.B;
+  const AnlFrame F = frames[blockIdx.x];
+  const AnlSound S = snds[F.snd];
+  double* row = out + S.row0 + (int64_t)F.f * K.cols;
+  if (row[sg::kCondEntropy] != 1.0) return;  // workgroup-uniform
+  const double* z = Z + S.z0 + (int64_t)F.f * B;
+  double mx = -INFINITY;
+  for (int i = threadIdx.x; i < B; i += kT) mx = fmax(mx, z[i]);
+  mx = block_reduce(mx, 2, red);
+  for (int i = threadIdx.x; i < B; i += kT) fr[i] = z[i] / mx;
+  __syncthreads();
+  const int h = K.specW / 2;
+  int pidx[sg::kBanaPeaks];
+  int np = 0, last = -1;
+  for (int r = 0; r < sg::kBanaPeaks; ++r) {  // the lowest peak above the last one found
+    int best = B;
+    for (int c = h + threadIdx.x; c < B - h && best == B; c += kT) {
+      if (c <= last) continue;
+      const double v = fr[c];
+      if (!(v > K.specPeak)) continue;
+      bool ok = true;
+      for (int j = c - h; j < c && ok; ++j) ok = fr[j] < v || fr[j] != fr[j];
+      for (int j = c + 1; j <= c + h && ok; ++j) ok = fr[j] <= v || fr[j] != fr[j];
+      if (ok) best = c;
+    }
+    best = block_min_int(best, redi);  // every thread gets it: the loop is workgroup-uniform
+    if (best == B) break;
+    pidx[np++] = best;
+    last = best;
+  }
+  if (threadIdx.x != 0 || np == 0) return;
+  double pf[sg::kBanaPeaks], cand[sg::kAnlMaxCands], cert[sg::kAnlMaxCands];
+  for (int i = 0; i < sg::kBanaPeaks; ++i) pf[i] = i < np ? freq[pidx[i]] : 0.0;
+  const int m = sg::bana_candidates(pf, np, K.bana, cand, cert);
+  const int c1 = sg::kAnlFixed + 4 * K.nCands;
+  for (int n = 0; n < m; ++n) {
+    row[c1 + n] = cand[n];
+    row[c1 + K.nCands + n] = cert[n];
+  }
+}
+
 double g_anl_ms[sg::kAnlStages];  // of the last profiled launch sequence
+double g_pitch_ms[sg::kPitchStages];
 
 }  // namespace
 
@@ -405,8 +598,10 @@ namespace sg {
 
 template <typename T>
 void analyze_device(const AnlSetup& A, const T* d_x, const int64_t* offsets, const int64_t* lengths, int64_t n_calls,
-                    double* d_out, const int64_t* out_off, int32_t* frames_out, hipStream_t s, double* kernel_ms) {
+                    double* d_out, const int64_t* out_off, int32_t* frames_out, hipStream_t s, double* kernel_ms,
+                    const PitchSetup* pitch) {
   const SpgSetup& P = A.spg;
+  const int nstages = pitch ? kPitchStages : kAnlStages;
   const int B = P.bins, wl = P.wl;
   std::vector<AnlSound> snds(n_calls);
   std::vector<AnlFrame> fr;
@@ -428,18 +623,25 @@ void analyze_device(const AnlSetup& A, const T* d_x, const int64_t* offsets, con
     cells += (int64_t)nf * B;
   }
   if (kernel_ms)
-    for (int k = 0; k < kAnlStages; ++k) kernel_ms[k] = 0;
+    for (int k = 0; k < nstages; ++k) kernel_ms[k] = 0;
   const int64_t F = (int64_t)fr.size();
   if (F == 0) return;
   if (A.rowLow < 1 || A.rowHigh > B || A.rowLow > A.rowHigh || A.cut0 < 0 || A.cut0 + A.ncut > B || A.lag0 < 0 ||
       A.lag0 + A.nlag > wl || B > kSpgMaxBins || A.nCands > kAnlMaxCands)
     throw SgError(SG_E_DEVICE, "analyze: the setup leaves the frame");
+  if (pitch && pitch->do_cep) {
+    const PitchSetup& Q = *pitch;
+    const int M = Q.cepL % 2 ? Q.cepL : Q.cepL / 2;
+    if (Q.cepL != B + 2 * Q.cepPad || Q.cepPad < 0 || M < 1 || M > kSpgMaxBins || Q.cepl != Q.cepL / 2 || Q.cep0 < 0 ||
+        Q.ncep < 1 || Q.cep0 + Q.ncep > Q.cepl || (int)Q.cepf.size() != Q.ncep || Q.cepW < 1)
+      throw SgError(SG_E_DEVICE, "analyze: the cepstrum's setup leaves the frame");
+  }
   DevBuf db;
   double* d_Z = db.get<double>((size_t)cells);
   SpgStat* d_stat = db.get<SpgStat>((size_t)n_calls);
   std::vector<int32_t> b_o(n_calls), f_o(n_calls);
   struct Stamps {
-    hipEvent_t e[kAnlStages + 1] = {};
+    hipEvent_t e[kPitchStages + 1] = {};
     ~Stamps() {
       for (hipEvent_t v : e)
         if (v) (void)hipEventDestroy(v);
@@ -508,7 +710,45 @@ void analyze_device(const AnlSetup& A, const T* d_x, const int64_t* offsets, con
     hipLaunchKernelGGL(sg_anl_acf<T>, gF, bT, (size_t)lds, s, d_x, d_fr, d_snd, d_stat, d_win, d_filt, d_lagf, K, d_out);
     MELCHK(hipGetLastError());
   }
-  stamp();
+  stamp();  // 4: the cepstrum and its peaks
+  if (pitch) {
+    const PitchSetup& Q = *pitch;
+    PitchK X;
+    X.B = B;
+    X.cols = A.cols;
+    X.nCands = A.nCands;
+    X.L = Q.cepL;
+    X.odd = Q.cepL % 2;
+    X.M = X.odd ? Q.cepL : Q.cepL / 2;
+    X.pad = Q.cepPad;
+    X.l = Q.cepl;
+    X.c0 = Q.cep0;
+    X.nc = Q.ncep;
+    X.cepW = Q.cepW;
+    X.specW = Q.specW;
+    X.cepThres = Q.cepThres;
+    X.specPeak = Q.specPeak;
+    X.bana = BanaPars{Q.pitchFloor, Q.pitchCeiling, Q.specSinglePeakCert, Q.specThres, Q.specMerge, A.nCands};
+    if (Q.do_cep) {
+      const int N = X.odd ? 2 * X.M : X.L;  // fft64 reads W_N^t, t < 2 M
+      double2* d_TN = db.get<double2>((size_t)N);
+      const double* d_cepf = upload(db, Q.cepf, s);
+      hipLaunchKernelGGL(sg_anl_roots, dim3((unsigned)((N + kT - 1) / kT)), bT, 0, s, d_TN, N);
+      MELCHK(hipGetLastError());
+      const int lds = (2 * X.M + 32) * (int)sizeof(double2) + (X.l + 1) * (int)sizeof(double);
+      if (lds > 48 * 1024)
+        MELCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&sg_anl_cep), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   lds));
+      hipLaunchKernelGGL(sg_anl_cep, gF, bT, (size_t)lds, s, d_fr, d_snd, d_Z, d_TN, d_cepf, X, d_out);
+      MELCHK(hipGetLastError());
+    }
+    stamp();  // 5: the spectral peaks and the BaNa candidates
+    if (Q.do_spec) {
+      hipLaunchKernelGGL(sg_anl_bana, gF, bT, 0, s, d_fr, d_snd, d_Z, d_freq, X, d_out);
+      MELCHK(hipGetLastError());
+    }
+    stamp();
+  }
   MELCHK(hipStreamSynchronize(s));
   if (kernel_ms)
     for (int k = 0; k + 1 < stage; ++k) {
@@ -582,6 +822,50 @@ int sg_analyze_frames_batch(sg_ctx* ctx, const float* d_wave, const int64_t* off
                               ctx->profiling ? g_anl_ms : nullptr);
     return SG_OK;
   });
+}
+
+int sg_pitch_candidates(sg_ctx* ctx, const double* wave, int64_t len, const sg_pitch_params* p, double* out) {
+  return guarded(ctx, [&]() {
+    if (!ctx || !p || !wave || !out) throw sg::SgError(SG_E_ARG, "sg_pitch_candidates: bad arguments");
+    const sg::PitchSetup S = sg::pitch_setup(*p);
+    if (len <= S.spg.wl)
+      throw sg::SgError(SG_E_ARG, "sg_pitch_candidates: the sound is not longer than the window (the reference's amplitude "
+                                  "window sound[a:(a + wl)] leaves it)");
+    MELCHK(hipSetDevice(ctx->device));
+    const int64_t cells = (int64_t)sg::anl_frames(S, len) * S.cols;
+    sg::DevBuf db;
+    double* d = db.get<double>((size_t)len);
+    double* d_o = db.get<double>((size_t)cells);
+    MELCHK(hipMemcpyAsync(d, wave, (size_t)len * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    MELCHK(hipStreamSynchronize(ctx->stream));
+    const int64_t off = 0;
+    int32_t f = 0;
+    sg::analyze_device<double>(S, d, &off, &len, 1, d_o, &off, &f, ctx->stream, ctx->profiling ? g_pitch_ms : nullptr, &S);
+    MELCHK(hipMemcpy(out, d_o, (size_t)cells * sizeof(double), hipMemcpyDeviceToHost));
+    return SG_OK;
+  });
+}
+
+int sg_pitch_candidates_batch(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, const int64_t* lengths,
+                              int64_t n_calls, const sg_pitch_params* p, double* d_out, const int64_t* out_off,
+                              int32_t* frames_out) {
+  return guarded(ctx, [&]() {
+    if (!ctx || !p || n_calls < 0 || n_calls > 2147483647LL ||
+        (n_calls > 0 && (!d_wave || !offsets || !lengths || !d_out || !out_off || !frames_out)))
+      throw sg::SgError(SG_E_ARG, "sg_pitch_candidates_batch: bad arguments");
+    const sg::PitchSetup S = sg::pitch_setup(*p);
+    if (n_calls == 0) return SG_OK;
+    MELCHK(hipSetDevice(ctx->device));
+    sg::analyze_device<float>(S, d_wave, offsets, lengths, n_calls, d_out, out_off, frames_out, ctx->stream,
+                              ctx->profiling ? g_pitch_ms : nullptr, &S);
+    return SG_OK;
+  });
+}
+
+int sg_debug_pitch_kernel_ms(double* out) {
+  if (!out) return SG_E_ARG;
+  for (int k = 0; k < sg::kPitchStages; ++k) out[k] = g_pitch_ms[k];
+  return SG_OK;
 }
 
 int sg_debug_analyze_kernel_ms(double* out) {

@@ -126,6 +126,14 @@ def lib():
         L.sg_analyze_frames.argtypes = [vp, dp, i64, app, dp]
         L.sg_analyze_frames_batch.argtypes = [vp, vp, i64p, i64p, i64, app, vp, i64p, i32p]
         L.sg_debug_analyze_kernel_ms.argtypes = [dp]
+    if hasattr(L, "sg_pitch_candidates_size"):  # the cepstral and spectral trackers: likewise additive
+        i32p = C.POINTER(C.c_int32)
+        ppp = C.POINTER(_abi.sg_pitch_params)
+        L.sg_pitch_candidates_size.argtypes = [i64, ppp, i32p, i32p, i32p]
+        L.sg_pitch_candidates_cep_labels.argtypes = [ppp, dp, C.c_int32]
+        L.sg_pitch_candidates.argtypes = [vp, dp, i64, ppp, dp]
+        L.sg_pitch_candidates_batch.argtypes = [vp, vp, i64p, i64p, i64, ppp, vp, i64p, i32p]
+        L.sg_debug_pitch_kernel_ms.argtypes = [dp]
     L.sg_rrng_create.argtypes = [C.c_int32, C.POINTER(vp)]
     L.sg_rrng_destroy.argtypes = [vp]
     L.sg_rrng_set_seed.argtypes = [vp, C.c_int32]
