@@ -483,6 +483,50 @@ def _check(rc, ctx):
         _raise(rc, native.lib().sg_last_error(ctx).decode())
 
 
+def _run(sound, sr, s, decisions, params, table, entry, device):
+    """analyze_frames() and pitch_candidates() behind their repairs: `decisions` is the
+    stage's *_decisions_native, `params` builds the C struct, `table` the dict, `entry`
+    names the C entry point."""
+    d = decisions(len(sound), s)
+    if len(sound) <= d["wl"]:
+        raise _too_short(len(sound), d["wl"])
+    ctx = native.default_context(device)
+    sound = np.ascontiguousarray(sound)
+    out = np.zeros(d["frames"] * d["cols"])
+    dp = C.POINTER(C.c_double)
+    P = params(s)
+    _check(getattr(native.lib(), entry)(ctx.ptr, sound.ctypes.data_as(dp), len(sound), C.byref(P),
+                                        out.ctypes.data_as(dp)), ctx.ptr)
+    return table(out.reshape(d["frames"], d["cols"]), s["nCands"], len(sound), sr, s["step"])
+
+
+def _run_batch(data, offsets, lengths, samplingRate, s, frames_of, params, table, cand_keys, entry, to_host, device):
+    """The *_batch forms likewise: frames_of(length, P) is the stage's frame count of a
+    sound, cand_keys name the nCands-wide column groups behind the fixed columns, and
+    the C entry points are entry + "_batch" and (in the text of the cross-check) entry + "_size"."""
+    L = native.lib()
+    P = params(s)
+    offs, lens, nc, p_offs, p_lens = native.batch_layout(offsets, lengths)
+    nC = s["nCands"]
+    frames = [frames_of(int(n), P) for n in lens]
+    cols = NFIXED + len(cand_keys) * nC
+    ooff, p_ooff = native.out_offsets([f * cols for f in frames])
+    ctx = native.default_context(device)
+    fo = np.zeros(max(nc, 1), dtype=np.int32)
+    out = native.device_out(data, ooff[-1])
+    _check(getattr(L, entry + "_batch")(ctx.ptr, C.c_void_p(data.data_ptr()), p_offs, p_lens, nc, C.byref(P),
+                                        C.c_void_p(out.data_ptr()), p_ooff,
+                                        fo.ctypes.data_as(C.POINTER(C.c_int32))), ctx.ptr)
+    if [int(f) for f in fo[:nc]] != frames:
+        raise native.SoundgenError(-1, "%s_batch: frame counts disagree with %s_size" % (entry, entry))
+    if not to_host:
+        return dict(out=out, offsets=ooff[:-1].copy(), frames=frames, cols=cols,
+                    columns=COLUMNS + sum(((k,) * nC for k in cand_keys), ()))
+    h = out.cpu().numpy()
+    return [table(h[ooff[i]:ooff[i + 1]].reshape(frames[i], cols), nC, int(lens[i]), samplingRate, s["step"])
+            for i in range(nc)]
+
+
 def analyze_frames(x, samplingRate=None, silence=0.04, windowLength=50, step=None, overlap=50, wn="gaussian", zp=0,
                    cutFreq=6000, pitchMethods=PITCH_METHODS, entropyThres=0.6, pitchFloor=75, pitchCeiling=3500,
                    nCands=1, domThres=0.1, domSmooth=220, autocorThres=0.7, autocorSmooth=None, device=0):
@@ -495,17 +539,7 @@ def analyze_frames(x, samplingRate=None, silence=0.04, windowLength=50, step=Non
     sound, sr = _input(x, samplingRate)
     s = repair(sr, len(sound) / sr, silence, windowLength, step, overlap, wn, zp, cutFreq, pitchMethods, entropyThres,
                pitchFloor, pitchCeiling, nCands, domThres, domSmooth, autocorThres, autocorSmooth)
-    d = frame_decisions_native(len(sound), s)
-    if len(sound) <= d["wl"]:
-        raise _too_short(len(sound), d["wl"])
-    ctx = native.default_context(device)
-    sound = np.ascontiguousarray(sound)
-    out = np.zeros(d["frames"] * d["cols"])
-    dp = C.POINTER(C.c_double)
-    P = _params(s)
-    _check(native.lib().sg_analyze_frames(ctx.ptr, sound.ctypes.data_as(dp), len(sound), C.byref(P),
-                                          out.ctypes.data_as(dp)), ctx.ptr)
-    return _table(out.reshape(d["frames"], d["cols"]), s["nCands"], len(sound), sr, s["step"])
+    return _run(sound, sr, s, frame_decisions_native, _params, _table, "sg_analyze_frames", device)
 
 
 def analyze_frames_batch(data, offsets, lengths, samplingRate, silence=0.04, windowLength=50, step=None, overlap=50,
@@ -522,34 +556,10 @@ def analyze_frames_batch(data, offsets, lengths, samplingRate, silence=0.04, win
     than the window has 0 frames and writes nothing. The repairs that need a sound's
     duration (windowLength, step) are not made. to_host=True returns the list of
     per-call dicts analyze_frames returns."""
-    import torch
     s = repair(samplingRate, None, silence, windowLength, step, overlap, wn, zp, cutFreq, pitchMethods, entropyThres,
                pitchFloor, pitchCeiling, nCands, domThres, domSmooth, autocorThres, autocorSmooth)
-    L = native.lib()
-    P = _params(s)
-    offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
-    lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64))
-    nc = len(offs)
-    ds = [frame_decisions_native(int(n), s) for n in lens]
-    cols = NFIXED + 2 * s["nCands"]
-    frames = [d["frames"] for d in ds]
-    ooff = np.concatenate([[0], np.cumsum([f * cols for f in frames])]).astype(np.int64)
-    ctx = native.default_context(device)
-    out = torch.empty(max(int(ooff[-1]), 1), dtype=torch.float64, device=data.device)
-    fo = np.zeros(max(nc, 1), dtype=np.int32)
-    i64p, i32p = C.POINTER(C.c_int64), C.POINTER(C.c_int32)
-    torch.cuda.synchronize(data.device)  # the library runs on its own stream
-    _check(L.sg_analyze_frames_batch(ctx.ptr, C.c_void_p(data.data_ptr()), offs.ctypes.data_as(i64p),
-                                     lens.ctypes.data_as(i64p), nc, C.byref(P), C.c_void_p(out.data_ptr()),
-                                     ooff.ctypes.data_as(i64p), fo.ctypes.data_as(i32p)), ctx.ptr)
-    if [int(f) for f in fo[:nc]] != frames:
-        raise native.SoundgenError(-1, "sg_analyze_frames_batch: frame counts disagree with sg_analyze_frames_size")
-    if not to_host:
-        return dict(out=out, offsets=ooff[:-1].copy(), frames=frames, cols=cols,
-                    columns=COLUMNS + ("autocorCand",) * s["nCands"] + ("autocorCert",) * s["nCands"])
-    h = out.cpu().numpy()
-    return [_table(h[ooff[i]:ooff[i + 1]].reshape(frames[i], cols), s["nCands"], int(lens[i]), samplingRate, s["step"])
-            for i in range(nc)]
+    return _run_batch(data, offsets, lengths, samplingRate, s, lambda n, P: frame_decisions_native(n, s)["frames"],
+                      _params, _table, ("autocorCand", "autocorCert"), "sg_analyze_frames", to_host, device)
 
 
 # ------------------------------------------------- pitch_candidates: 'cep' and 'spec'
@@ -866,6 +876,17 @@ def pitch_decisions_native(length, s):
     return d
 
 
+def _pitch_frames_native(length, P):
+    """sg_pitch_candidates_size's frame count alone: the setup of the last parameters is
+    cached in the library, so this is one cheap call per sound of a batch."""
+    L = native.lib()
+    fr, cl = C.c_int32(), C.c_int32()
+    rc = L.sg_pitch_candidates_size(int(length), C.byref(P), C.byref(fr), C.byref(cl), None)
+    if rc < 0:
+        _raise(rc, L.sg_analyze_frames_size_error().decode())
+    return fr.value
+
+
 def _pitch_table(m, nC, length, sr, step):
     t = _table(m, nC, length, sr, step)
     for i, k in enumerate(PITCH_KEYS):
@@ -887,17 +908,7 @@ def pitch_candidates(x, samplingRate=None, silence=0.04, windowLength=50, step=N
     bit for bit. Not built: see pitch_candidates_numpy()."""
     sound, sr = _input(x, samplingRate)
     s = repair_pitch(sr, len(sound) / sr, **_pitch_args(locals()))
-    d = pitch_decisions_native(len(sound), s)
-    if len(sound) <= d["wl"]:
-        raise _too_short(len(sound), d["wl"])
-    ctx = native.default_context(device)
-    sound = np.ascontiguousarray(sound)
-    out = np.zeros(d["frames"] * d["cols"])
-    dp = C.POINTER(C.c_double)
-    P = _pitch_params(s)
-    _check(native.lib().sg_pitch_candidates(ctx.ptr, sound.ctypes.data_as(dp), len(sound), C.byref(P),
-                                            out.ctypes.data_as(dp)), ctx.ptr)
-    return _pitch_table(out.reshape(d["frames"], d["cols"]), s["nCands"], len(sound), sr, s["step"])
+    return _run(sound, sr, s, pitch_decisions_native, _pitch_params, _pitch_table, "sg_pitch_candidates", device)
 
 
 def pitch_candidates_batch(data, offsets, lengths, samplingRate, silence=0.04, windowLength=50, step=None, overlap=50,
@@ -912,38 +923,9 @@ def pitch_candidates_batch(data, offsets, lengths, samplingRate, silence=0.04, w
     names the fixed ones, then nCands each of autocorCand, autocorCert, cepCand,
     cepCert, specCand, specCert. to_host=True returns the list of per-call dicts
     pitch_candidates() returns."""
-    import torch
     s = repair_pitch(samplingRate, None, **_pitch_args(locals()))
-    L = native.lib()
-    P = _pitch_params(s)
-    offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
-    lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64))
-    nc, nC = len(offs), s["nCands"]
-    fr, cl = C.c_int32(), C.c_int32()
-    frames = []
-    for n in lens:  # the setup of the last parameters is cached in the library: one cheap call per sound
-        rc = L.sg_pitch_candidates_size(int(n), C.byref(P), C.byref(fr), C.byref(cl), None)
-        if rc < 0:
-            _raise(rc, L.sg_analyze_frames_size_error().decode())
-        frames.append(fr.value)
-    cols = NFIXED + 6 * nC
-    ooff = np.concatenate([[0], np.cumsum([f * cols for f in frames])]).astype(np.int64)
-    ctx = native.default_context(device)
-    out = torch.empty(max(int(ooff[-1]), 1), dtype=torch.float64, device=data.device)
-    fo = np.zeros(max(nc, 1), dtype=np.int32)
-    i64p, i32p = C.POINTER(C.c_int64), C.POINTER(C.c_int32)
-    torch.cuda.synchronize(data.device)  # the library runs on its own stream
-    _check(L.sg_pitch_candidates_batch(ctx.ptr, C.c_void_p(data.data_ptr()), offs.ctypes.data_as(i64p),
-                                       lens.ctypes.data_as(i64p), nc, C.byref(P), C.c_void_p(out.data_ptr()),
-                                       ooff.ctypes.data_as(i64p), fo.ctypes.data_as(i32p)), ctx.ptr)
-    if [int(f) for f in fo[:nc]] != frames:
-        raise native.SoundgenError(-1, "sg_pitch_candidates_batch: frame counts disagree with sg_pitch_candidates_size")
-    if not to_host:
-        names = sum((((k,) * nC) for k in ("autocorCand", "autocorCert") + PITCH_KEYS), ())
-        return dict(out=out, offsets=ooff[:-1].copy(), frames=frames, cols=cols, columns=COLUMNS + names)
-    h = out.cpu().numpy()
-    return [_pitch_table(h[ooff[i]:ooff[i + 1]].reshape(frames[i], cols), nC, int(lens[i]), samplingRate, s["step"])
-            for i in range(nc)]
+    return _run_batch(data, offsets, lengths, samplingRate, s, _pitch_frames_native, _pitch_params, _pitch_table,
+                      ("autocorCand", "autocorCert") + PITCH_KEYS, "sg_pitch_candidates", to_host, device)
 
 
 def pitch_matrices(table):

@@ -30,15 +30,14 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstring>
 #include <string>
 #include <vector>
 
 #include "sg_analyze.h"
 #include "sg_bana.h"
-#include "sg_ctx.h"
+#include "sg_dev64.h"
 #include "sg_fft64_dev.h"
-#include "sg_mel_dev.h"
+#include "sg_launch.h"
 #include "sg_rmath.h"
 
 namespace {
@@ -71,29 +70,6 @@ struct AnlK {
   int do_dom, do_autocor;
   double silence, entropyThres, domThres, autocorThres, sxx;
 };
-
-__device__ __forceinline__ unsigned long long dkey(double v) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double dunkey(unsigned long long k) {
-  return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
-}
-
-// op 0: sum, 1: min, 2: max over the workgroup, in a fixed order; every thread gets the result
-__device__ __forceinline__ double block_reduce(double v, int op, double* red) {
-  __syncthreads();
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int o = kT / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) {
-      const double a = red[threadIdx.x], b = red[threadIdx.x + o];
-      red[threadIdx.x] = op == 0 ? a + b : op == 1 ? fmin(a, b) : fmax(a, b);
-    }
-    __syncthreads();
-  }
-  return red[0];
-}
 
 // the smallest int over the workgroup
 __device__ __forceinline__ int block_min_int(int v, int* red) {
@@ -166,7 +142,7 @@ __global__ __launch_bounds__(kT) void sg_anl_ampl(const T* __restrict__ x, const
     const double v = norm_sample(xc, i, st);
     acc += v * v;
   }
-  acc = block_reduce(acc, 0, red);
+  acc = block_reduce<kT>(acc, 0, red);
   if (threadIdx.x == 0) {
     const double a = sqrt(acc / (double)(wl + 1));
     out[S.row0 + (int64_t)F.f * cols + sg::kAmpl] = a;
@@ -198,9 +174,9 @@ __global__ __launch_bounds__(kT) void sg_anl_spec(const AnlFrame* __restrict__ f
     s1 += y;
     sl += log(y);
   }
-  s0 = block_reduce(s0, 0, red);
-  s1 = block_reduce(s1, 0, red);
-  sl = block_reduce(sl, 0, red);
+  s0 = block_reduce<kT>(s0, 0, red);
+  s1 = block_reduce<kT>(s1, 0, red);
+  sl = block_reduce<kT>(sl, 0, red);
   const double nb = (double)(K.rowHigh - K.rowLow + 1);
   const double entropy = s0 == 0 ? NAN : exp(sl / nb) / (s1 / nb);
   const double ampl = row[sg::kAmpl];
@@ -218,7 +194,7 @@ __global__ __launch_bounds__(kT) void sg_anl_spec(const AnlFrame* __restrict__ f
   // which.max(frame): the first maximum
   double mx = -INFINITY;
   for (int b = threadIdx.x; b < B; b += kT) mx = fmax(mx, fr[b]);
-  mx = block_reduce(mx, 2, red);
+  mx = block_reduce<kT>(mx, 2, red);
   int am = B;
   for (int b = threadIdx.x; b < B; b += kT)
     if (fr[b] == mx) {
@@ -240,7 +216,7 @@ __global__ __launch_bounds__(kT) void sg_anl_spec(const AnlFrame* __restrict__ f
   const double ybar = amp_cut / (double)K.ncut;
   double sxy = 0;
   for (int k = threadIdx.x; k < K.ncut; k += kT) sxy += xcut[k] * (fr[K.cut0 + k] - ybar);
-  sxy = block_reduce(sxy, 0, red);
+  sxy = block_reduce<kT>(sxy, 0, red);
   if (threadIdx.x == 0) {
     row[sg::kPeakFreq] = am < B ? freq[am] : NAN;
     row[sg::kPeakFreqCut] = am < K.ncut ? freq[K.cut0 + am] : NAN;  // meanSpec_cut$freq[which.max(frame)]
@@ -301,14 +277,14 @@ __global__ __launch_bounds__(kT) void sg_anl_acf(const T* __restrict__ x, const 
     xw[i] = v;
     acc += v;
   }
-  const double mean = block_reduce(acc, 0, red) / (double)wl;
+  const double mean = block_reduce<kT>(acc, 0, red) / (double)wl;
   acc = 0;
   for (int i = threadIdx.x; i < wl; i += kT) {
     const double v = xw[i] - mean;  // acf() demeans
     xw[i] = v;
     acc += v * v;
   }
-  const double c0 = block_reduce(acc, 0, red) / (double)wl;  // lag 0; the barrier inside publishes xw
+  const double c0 = block_reduce<kT>(acc, 0, red) / (double)wl;  // lag 0; the barrier inside publishes xw
   const double se = sqrt(c0);
   // Four consecutive lags per thread: xw[t] is a broadcast, and the window w0..w3 =
   // xw[t + k .. t + k + 3] slides by one new value per step, so 4 multiply-adds cost 2
@@ -357,7 +333,7 @@ __global__ __launch_bounds__(kT) void sg_anl_acf(const T* __restrict__ x, const 
   // is decided by (value, index), not by the list's order
   double hn = -INFINITY;
   for (int i = threadIdx.x; i < nl; i += kT) hn = fmax(hn, amp[i]);
-  hn = block_reduce(hn, 2, red);
+  hn = block_reduce<kT>(hn, 2, red);
   int* pk = reinterpret_cast<int*>(xw);  // xw is dead (block_reduce's barriers are behind every read)
   const int h = K.acW / 2;
   for (int c = h + threadIdx.x; c < nl - h; c += kT) {
@@ -416,11 +392,6 @@ struct PitchK {
   sg::BanaPars bana;  // carries pitchFloor
 };
 
-__global__ __launch_bounds__(kT) void sg_anl_roots(double2* __restrict__ TN, int N) {
-  const int t = blockIdx.x * kT + threadIdx.x;
-  if (t < N) TN[t] = root64(t, N);
-}
-
 // getPitchCep (R/utilities_analyze.R:337-407) for one cond_entropy frame: abs(fft(c(zp,
 // frame / max(frame), zp))) / its maximum, the rows with pitchFloor < label < pitchCeiling,
 // the peaks, the 1.8 rule, the order, the discount. Row i (1-based) of the reference's
@@ -446,7 +417,7 @@ __global__ __launch_bounds__(kT) void sg_anl_cep(const AnlFrame* __restrict__ fr
   const double* z = Z + S.z0 + (int64_t)F.f * B;
   double mx = -INFINITY;
   for (int i = threadIdx.x; i < B; i += kT) mx = fmax(mx, z[i]);
-  mx = block_reduce(mx, 2, red);
+  mx = block_reduce<kT>(mx, 2, red);
   if (K.odd) {
     for (int n = threadIdx.x; n < M; n += kT) {
       const int j = n - K.pad;
@@ -480,7 +451,7 @@ __global__ __launch_bounds__(kT) void sg_anl_cep(const AnlFrame* __restrict__ fr
   __syncthreads();
   double cm = -INFINITY;
   for (int k = threadIdx.x; k <= K.l; k += kT) cm = fmax(cm, cep[k]);
-  cm = block_reduce(cm, 2, red);
+  cm = block_reduce<kT>(cm, 2, red);
   double* amp = cep + K.c0;  // host: c0 + nc <= l
   for (int i = threadIdx.x; i < nl; i += kT) amp[i] = amp[i] / cm;
   __syncthreads();
@@ -556,7 +527,7 @@ __global__ __launch_bounds__(kT) void sg_anl_bana(const AnlFrame* __restrict__ f
   const double* z = Z + S.z0 + (int64_t)F.f * B;
   double mx = -INFINITY;
   for (int i = threadIdx.x; i < B; i += kT) mx = fmax(mx, z[i]);
-  mx = block_reduce(mx, 2, red);
+  mx = block_reduce<kT>(mx, 2, red);
   for (int i = threadIdx.x; i < B; i += kT) fr[i] = z[i] / mx;
   __syncthreads();
   const int h = K.specW / 2;
@@ -601,7 +572,6 @@ void analyze_device(const AnlSetup& A, const T* d_x, const int64_t* offsets, con
                     double* d_out, const int64_t* out_off, int32_t* frames_out, hipStream_t s, double* kernel_ms,
                     const PitchSetup* pitch) {
   const SpgSetup& P = A.spg;
-  const int nstages = pitch ? kPitchStages : kAnlStages;
   const int B = P.bins, wl = P.wl;
   std::vector<AnlSound> snds(n_calls);
   std::vector<AnlFrame> fr;
@@ -622,8 +592,8 @@ void analyze_device(const AnlSetup& A, const T* d_x, const int64_t* offsets, con
     }
     cells += (int64_t)nf * B;
   }
-  if (kernel_ms)
-    for (int k = 0; k < nstages; ++k) kernel_ms[k] = 0;
+  StageClock clk(s, kernel_ms, pitch ? kPitchStages : kAnlStages);
+  clk.zero();
   const int64_t F = (int64_t)fr.size();
   if (F == 0) return;
   if (A.rowLow < 1 || A.rowHigh > B || A.rowLow > A.rowHigh || A.cut0 < 0 || A.cut0 + A.ncut > B || A.lag0 < 0 ||
@@ -640,21 +610,7 @@ void analyze_device(const AnlSetup& A, const T* d_x, const int64_t* offsets, con
   double* d_Z = db.get<double>((size_t)cells);
   SpgStat* d_stat = db.get<SpgStat>((size_t)n_calls);
   std::vector<int32_t> b_o(n_calls), f_o(n_calls);
-  struct Stamps {
-    hipEvent_t e[kPitchStages + 1] = {};
-    ~Stamps() {
-      for (hipEvent_t v : e)
-        if (v) (void)hipEventDestroy(v);
-    }
-  } st;
-  int stage = 0;
-  auto stamp = [&]() {
-    if (!kernel_ms) return;
-    MELCHK(hipEventCreate(&st.e[stage]));
-    MELCHK(hipEventRecord(st.e[stage], s));
-    ++stage;
-  };
-  stamp();
+  clk.stamp();
   spectrogram_device<T>(P, d_x, offsets, lens.data(), n_calls, d_Z, zoff.data(), b_o.data(), f_o.data(), s, nullptr,
                         d_stat);
   for (int64_t c = 0; c < n_calls; ++c)
@@ -663,13 +619,7 @@ void analyze_device(const AnlSetup& A, const T* d_x, const int64_t* offsets, con
   const AnlFrame* d_fr = upload(db, fr, s);
   const double* d_freq = upload(db, A.freq, s);
   const double* d_xc = upload(db, A.xc, s);
-  unsigned long long kinf;
-  {
-    const double inf = INFINITY;
-    std::memcpy(&kinf, &inf, 8);
-    kinf |= 0x8000000000000000ull;  // dkey(+Inf)
-  }
-  unsigned long long* d_min = upload(db, std::vector<unsigned long long>(n_calls, kinf), s);
+  unsigned long long* d_min = upload(db, std::vector<unsigned long long>(n_calls, dkey(INFINITY)), s);
   AnlK K;
   K.wl = wl;
   K.B = B;
@@ -692,25 +642,25 @@ void analyze_device(const AnlSetup& A, const T* d_x, const int64_t* offsets, con
   K.autocorThres = A.autocorThres;
   K.sxx = A.sxx;
   const dim3 gF((unsigned)F), bT(kT);
-  stamp();  // 1: amplitudes
+  clk.stamp();  // 1: amplitudes
   hipLaunchKernelGGL(sg_anl_ampl<T>, gF, bT, 0, s, d_x, d_fr, d_snd, d_stat, wl, A.cols, d_out, d_min);
-  MELCHK(hipGetLastError());
-  stamp();  // 2: descriptives and dom
+  HIPCHK(hipGetLastError());
+  clk.stamp();  // 2: descriptives and dom
   hipLaunchKernelGGL(sg_anl_spec, gF, bT, 0, s, d_fr, d_snd, d_Z, d_freq, d_xc, d_min, K, d_out);
-  MELCHK(hipGetLastError());
-  stamp();  // 3: autocorrelation and its peaks
+  HIPCHK(hipGetLastError());
+  clk.stamp();  // 3: autocorrelation and its peaks
   if (A.do_autocor) {
     const double* d_win = upload(db, spg_window(wl, P.wn), s);
     const double* d_filt = upload(db, anl_filter(A), s);
     const double* d_lagf = upload(db, A.lagf, s);
     const int lds = (wl + 4 + A.nlag) * (int)sizeof(double);
     if (lds > 48 * 1024)
-      MELCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&sg_anl_acf<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&sg_anl_acf<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                  lds));
     hipLaunchKernelGGL(sg_anl_acf<T>, gF, bT, (size_t)lds, s, d_x, d_fr, d_snd, d_stat, d_win, d_filt, d_lagf, K, d_out);
-    MELCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
   }
-  stamp();  // 4: the cepstrum and its peaks
+  clk.stamp();  // 4: the cepstrum and its peaks
   if (pitch) {
     const PitchSetup& Q = *pitch;
     PitchK X;
@@ -733,53 +683,54 @@ void analyze_device(const AnlSetup& A, const T* d_x, const int64_t* offsets, con
       const int N = X.odd ? 2 * X.M : X.L;  // fft64 reads W_N^t, t < 2 M
       double2* d_TN = db.get<double2>((size_t)N);
       const double* d_cepf = upload(db, Q.cepf, s);
-      hipLaunchKernelGGL(sg_anl_roots, dim3((unsigned)((N + kT - 1) / kT)), bT, 0, s, d_TN, N);
-      MELCHK(hipGetLastError());
+      fill_roots64(d_TN, N, s);
       const int lds = (2 * X.M + 32) * (int)sizeof(double2) + (X.l + 1) * (int)sizeof(double);
       if (lds > 48 * 1024)
-        MELCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&sg_anl_cep), hipFuncAttributeMaxDynamicSharedMemorySize,
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&sg_anl_cep), hipFuncAttributeMaxDynamicSharedMemorySize,
                                    lds));
       hipLaunchKernelGGL(sg_anl_cep, gF, bT, (size_t)lds, s, d_fr, d_snd, d_Z, d_TN, d_cepf, X, d_out);
-      MELCHK(hipGetLastError());
+      HIPCHK(hipGetLastError());
     }
-    stamp();  // 5: the spectral peaks and the BaNa candidates
+    clk.stamp();  // 5: the spectral peaks and the BaNa candidates
     if (Q.do_spec) {
       hipLaunchKernelGGL(sg_anl_bana, gF, bT, 0, s, d_fr, d_snd, d_Z, d_freq, X, d_out);
-      MELCHK(hipGetLastError());
+      HIPCHK(hipGetLastError());
     }
-    stamp();
+    clk.stamp();
   }
-  MELCHK(hipStreamSynchronize(s));
-  if (kernel_ms)
-    for (int k = 0; k + 1 < stage; ++k) {
-      float ms = 0;
-      MELCHK(hipEventElapsedTime(&ms, st.e[k], st.e[k + 1]));
-      kernel_ms[k] = ms;
-    }
+  HIPCHK(hipStreamSynchronize(s));
+  clk.finish();
 }
 
 }  // namespace sg
 
 namespace {
 
-template <class F>
-int guarded(sg_ctx* ctx, F&& f) {
-  int code;
-  std::string msg;
-  try {
-    return f();
-  } catch (const sg::SgError& e) {
-    code = e.code;
-    msg = e.what();
-  } catch (const std::bad_alloc&) {
-    code = SG_E_NOMEM;
-    msg = "out of host memory";
-  } catch (const std::exception& e) {
-    code = SG_E_ARG;
-    msg = e.what();
-  }
-  if (ctx) ctx->err = msg;
-  return code;
+using sg::guarded;
+
+// The single-sound and the batch entry point of analyze_frames (pitch == nullptr, ms =
+// g_anl_ms) and of pitch_candidates (pitch == &S, ms = g_pitch_ms), behind their
+// argument checks
+int frames_single(sg_ctx* ctx, const sg::AnlSetup& S, const sg::PitchSetup* pitch, double* ms, const double* wave,
+                  int64_t len, double* out) {
+  HIPCHK(hipSetDevice(ctx->device));
+  const int64_t cells = (int64_t)sg::anl_frames(S, len) * S.cols;
+  sg::single_sound(ctx, wave, len, cells, out, [&](const double* d, double* d_o) {
+    const int64_t off = 0;
+    int32_t f = 0;
+    sg::analyze_device<double>(S, d, &off, &len, 1, d_o, &off, &f, ctx->stream, ctx->profiling ? ms : nullptr, pitch);
+  });
+  return SG_OK;
+}
+
+int frames_batch(sg_ctx* ctx, const sg::AnlSetup& S, const sg::PitchSetup* pitch, double* ms, const float* d_wave,
+                 const int64_t* offsets, const int64_t* lengths, int64_t n_calls, double* d_out, const int64_t* out_off,
+                 int32_t* frames_out) {
+  if (n_calls == 0) return SG_OK;
+  HIPCHK(hipSetDevice(ctx->device));
+  sg::analyze_device<float>(S, d_wave, offsets, lengths, n_calls, d_out, out_off, frames_out, ctx->stream,
+                            ctx->profiling ? ms : nullptr, pitch);
+  return SG_OK;
 }
 
 }  // namespace
@@ -793,18 +744,7 @@ int sg_analyze_frames(sg_ctx* ctx, const double* wave, int64_t len, const sg_ana
     if (len <= S.spg.wl)
       throw sg::SgError(SG_E_ARG, "sg_analyze_frames: the sound is not longer than the window (the reference's amplitude "
                                   "window sound[a:(a + wl)] leaves it)");
-    MELCHK(hipSetDevice(ctx->device));
-    const int64_t cells = (int64_t)sg::anl_frames(S, len) * S.cols;
-    sg::DevBuf db;
-    double* d = db.get<double>((size_t)len);
-    double* d_o = db.get<double>((size_t)cells);
-    MELCHK(hipMemcpyAsync(d, wave, (size_t)len * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    MELCHK(hipStreamSynchronize(ctx->stream));
-    const int64_t off = 0;
-    int32_t f = 0;
-    sg::analyze_device<double>(S, d, &off, &len, 1, d_o, &off, &f, ctx->stream, ctx->profiling ? g_anl_ms : nullptr);
-    MELCHK(hipMemcpy(out, d_o, (size_t)cells * sizeof(double), hipMemcpyDeviceToHost));
-    return SG_OK;
+    return frames_single(ctx, S, nullptr, g_anl_ms, wave, len, out);
   });
 }
 
@@ -816,11 +756,7 @@ int sg_analyze_frames_batch(sg_ctx* ctx, const float* d_wave, const int64_t* off
         (n_calls > 0 && (!d_wave || !offsets || !lengths || !d_out || !out_off || !frames_out)))
       throw sg::SgError(SG_E_ARG, "sg_analyze_frames_batch: bad arguments");
     const sg::AnlSetup S = sg::anl_setup(*p);
-    if (n_calls == 0) return SG_OK;
-    MELCHK(hipSetDevice(ctx->device));
-    sg::analyze_device<float>(S, d_wave, offsets, lengths, n_calls, d_out, out_off, frames_out, ctx->stream,
-                              ctx->profiling ? g_anl_ms : nullptr);
-    return SG_OK;
+    return frames_batch(ctx, S, nullptr, g_anl_ms, d_wave, offsets, lengths, n_calls, d_out, out_off, frames_out);
   });
 }
 
@@ -831,18 +767,7 @@ int sg_pitch_candidates(sg_ctx* ctx, const double* wave, int64_t len, const sg_p
     if (len <= S.spg.wl)
       throw sg::SgError(SG_E_ARG, "sg_pitch_candidates: the sound is not longer than the window (the reference's amplitude "
                                   "window sound[a:(a + wl)] leaves it)");
-    MELCHK(hipSetDevice(ctx->device));
-    const int64_t cells = (int64_t)sg::anl_frames(S, len) * S.cols;
-    sg::DevBuf db;
-    double* d = db.get<double>((size_t)len);
-    double* d_o = db.get<double>((size_t)cells);
-    MELCHK(hipMemcpyAsync(d, wave, (size_t)len * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    MELCHK(hipStreamSynchronize(ctx->stream));
-    const int64_t off = 0;
-    int32_t f = 0;
-    sg::analyze_device<double>(S, d, &off, &len, 1, d_o, &off, &f, ctx->stream, ctx->profiling ? g_pitch_ms : nullptr, &S);
-    MELCHK(hipMemcpy(out, d_o, (size_t)cells * sizeof(double), hipMemcpyDeviceToHost));
-    return SG_OK;
+    return frames_single(ctx, S, &S, g_pitch_ms, wave, len, out);
   });
 }
 
@@ -854,11 +779,7 @@ int sg_pitch_candidates_batch(sg_ctx* ctx, const float* d_wave, const int64_t* o
         (n_calls > 0 && (!d_wave || !offsets || !lengths || !d_out || !out_off || !frames_out)))
       throw sg::SgError(SG_E_ARG, "sg_pitch_candidates_batch: bad arguments");
     const sg::PitchSetup S = sg::pitch_setup(*p);
-    if (n_calls == 0) return SG_OK;
-    MELCHK(hipSetDevice(ctx->device));
-    sg::analyze_device<float>(S, d_wave, offsets, lengths, n_calls, d_out, out_off, frames_out, ctx->stream,
-                              ctx->profiling ? g_pitch_ms : nullptr, &S);
-    return SG_OK;
+    return frames_batch(ctx, S, &S, g_pitch_ms, d_wave, offsets, lengths, n_calls, d_out, out_off, frames_out);
   });
 }
 

@@ -19,7 +19,7 @@
 #include "sg_amp.h"
 #include "sg_prof.h"
 #include "sg_mel.h"
-#include "sg_ctx.h"
+#include "sg_launch.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -42,25 +42,7 @@ int set_err(sg_ctx* ctx, int code, const std::string& m) {
   return code;
 }
 
-#define HIPCHK(x)                                                                         \
-  do {                                                                                    \
-    hipError_t _e = (x);                                                                  \
-    if (_e != hipSuccess)                                                                 \
-      throw sg::SgError(SG_E_DEVICE, std::string(#x) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
-template <class F>
-int guarded(sg_ctx* ctx, F&& f) {
-  try {
-    return f();
-  } catch (const sg::SgError& e) {
-    return set_err(ctx, e.code, e.what());
-  } catch (const std::bad_alloc&) {
-    return set_err(ctx, SG_E_NOMEM, "out of host memory");
-  } catch (const std::exception& e) {
-    return set_err(ctx, SG_E_ARG, e.what());
-  }
-}
+using sg::guarded;
 
 // Rolls a Batch back to a checkpoint when planning one call fails.
 struct Checkpoint {

@@ -1,5 +1,7 @@
 // sg_ctx.h -- the device context behind the C ABI's sg_ctx handle (sg_api.cpp
-// owns its life cycle; sg_ssm.hip's entry points use its stream and error text).
+// owns its life cycle; every entry point, in sg_api.cpp and in the .hip files of
+// the analysis features, uses its stream and, through guarded() of sg_launch.h,
+// its error text).
 #pragma once
 #include <hip/hip_runtime.h>
 

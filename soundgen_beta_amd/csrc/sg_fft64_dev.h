@@ -13,7 +13,8 @@
 //
 // Roots: TN[t] = W_N^t = exp(-2 pi i t / N), t < N = 2M, an fp64 table in global
 // memory (L2-resident), every entry root64(t, N) -- sg_roots64 fills one per
-// window length of a plan, sg_spg_roots one per spectrogram launch.
+// window length of a plan, sg_spg_roots (fill_roots64, sg_spectrogram.h) one per
+// spectrogram launch and one per launch of the cepstral tracker.
 #pragma once
 #include <hip/hip_runtime.h>
 

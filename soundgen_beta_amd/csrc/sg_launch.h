@@ -1,0 +1,138 @@
+// sg_launch.h — what every host-side launch sequence of the analysis features
+// (sg_mel.hip, sg_ssm.hip, sg_spectrogram.hip, sg_analyze.hip) and the C entry
+// points (theirs and sg_api.cpp's) share: the HIP error check, the buffers of a
+// launch sequence, the exception-to-code mapping of an entry point, the per-stage
+// device clock and the single-sound round trip. Host code that needs the HIP runtime.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "sg_ctx.h"
+#include "sg_rmath.h"
+#include "soundgen_hip.h"
+
+#define HIPCHK(x)                                                                                        \
+  do {                                                                                                   \
+    hipError_t _e = (x);                                                                                 \
+    if (_e != hipSuccess) throw sg::SgError(SG_E_DEVICE, std::string(#x) + ": " + hipGetErrorString(_e)); \
+  } while (0)
+
+namespace sg {
+
+// Device buffers of one launch sequence, and the host copies their uploads read: an
+// async H2D copy from pageable memory may still be pending when the caller's
+// vector goes away, so upload() stages the bytes in memory this object owns.
+// The destructor frees the device buffers first (hipFree waits for the device),
+// then the staged host bytes.
+struct DevBuf {
+  std::vector<void*> p;
+  std::vector<std::vector<char>> host;
+  template <class T>
+  T* get(size_t n) {
+    void* q = nullptr;
+    HIPCHK(hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)));
+    p.push_back(q);
+    return static_cast<T*>(q);
+  }
+  ~DevBuf() {
+    for (void* q : p) (void)hipFree(q);
+  }
+};
+
+template <class T>
+T* upload(DevBuf& db, const std::vector<T>& v, hipStream_t s) {
+  T* d = db.get<T>(v.size());
+  if (!v.empty()) {
+    const char* src = reinterpret_cast<const char*>(v.data());
+    db.host.emplace_back(src, src + v.size() * sizeof(T));
+    HIPCHK(hipMemcpyAsync(d, db.host.back().data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
+  }
+  return d;
+}
+
+// The body of a C entry point: f()'s value, or the code of what it throws with
+// the text left in ctx (when there is one) for sg_last_error
+template <class F>
+int guarded(sg_ctx* ctx, F&& f) {
+  int code;
+  std::string msg;
+  try {
+    return f();
+  } catch (const SgError& e) {
+    code = e.code;
+    msg = e.what();
+  } catch (const std::bad_alloc&) {
+    code = SG_E_NOMEM;
+    msg = "out of host memory";
+  } catch (const std::exception& e) {
+    code = SG_E_ARG;
+    msg = e.what();
+  }
+  if (ctx) ctx->err = msg;
+  return code;
+}
+
+// The device time of each stage of a launch sequence, between events on its stream
+// (profiling only; ms == nullptr: every call is a no-op). stamp() at each stage
+// boundary, in stage order; finish() once the stream is synchronised: ms[k] = the
+// time between stamps k and k + 1, 0 for the stages that were not reached.
+class StageClock {
+ public:
+  StageClock(hipStream_t s, double* ms, int nstages) : s_(s), ms_(ms), n_(nstages) {
+    if (ms_) e_.reserve((size_t)n_ + 1);
+  }
+  StageClock(const StageClock&) = delete;
+  StageClock& operator=(const StageClock&) = delete;
+  ~StageClock() {
+    for (hipEvent_t v : e_) (void)hipEventDestroy(v);
+  }
+  void zero() {
+    for (int k = 0; ms_ && k < n_; ++k) ms_[k] = 0;
+  }
+  void stamp() {
+    if (!ms_) return;
+    hipEvent_t v;
+    HIPCHK(hipEventCreate(&v));
+    e_.push_back(v);
+    HIPCHK(hipEventRecord(v, s_));
+  }
+  void finish() {
+    zero();
+    for (int k = 0; k + 1 < (int)e_.size() && k < n_; ++k) {
+      float ms = 0;
+      HIPCHK(hipEventElapsedTime(&ms, e_[k], e_[k + 1]));
+      ms_[k] = ms;
+    }
+  }
+
+ private:
+  hipStream_t s_;
+  double* ms_;
+  int n_;
+  std::vector<hipEvent_t> e_;
+};
+
+// len doubles of host memory into a buffer of db, complete on return
+inline double* upload_sound(DevBuf& db, const double* wave, int64_t len, hipStream_t s) {
+  double* d = db.get<double>((size_t)len);
+  HIPCHK(hipMemcpyAsync(d, wave, (size_t)len * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return d;
+}
+
+// One sound from host memory through a launch sequence that leaves `cells` doubles
+// on the device: run(d_wave, d_out), then d_out to out
+template <class F>
+void single_sound(sg_ctx* ctx, const double* wave, int64_t len, int64_t cells, double* out, F&& run) {
+  DevBuf db;
+  const double* d = upload_sound(db, wave, len, ctx->stream);
+  double* d_o = db.get<double>((size_t)cells);
+  run(d, d_o);
+  HIPCHK(hipMemcpy(out, d_o, (size_t)cells * sizeof(double), hipMemcpyDeviceToHost));
+}
+
+}  // namespace sg

@@ -28,6 +28,8 @@
 #include <string>
 #include <vector>
 
+#include "sg_dev64.h"
+#include "sg_launch.h"
 #include "sg_mel.h"
 #include "sg_mel_dev.h"
 #include "sg_rmath.h"
@@ -140,12 +142,6 @@ __global__ __launch_bounds__(256) void sg_mel_cand(const MelCand* __restrict__ c
     mn[blockIdx.x] = rmn[0];
     mx[blockIdx.x] = rmx[0];
   }
-}
-
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
 }
 
 // log01 of one kept column (melfcc + soundgen's log01: log(v - min + 1) / log(max - min + 1))
@@ -404,11 +400,11 @@ void mel_run(MelRun& r, const MelGeom& g, const T* d_x, const int64_t* offsets, 
   if (r.F > 0) {
     hipLaunchKernelGGL(sg_mel_frames<T>, dim3((unsigned)r.F), dim3(256), (size_t)2 * M * sizeof(double2), s, d_x, d_fr,
                        d_ham, d_tw, d_twN, d_bands, d_w, g.winpts, M, logM, g.nb, r.spec, colmean);
-    MELCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
   }
   hipLaunchKernelGGL(sg_mel_cand, dim3((unsigned)n), dim3(256), 0, s, r.cands, r.spec, colmean, g.thr, g.nb, r.kept,
                      r.nkept, r.mn, r.mx);
-  MELCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
 }
 
 }  // namespace
@@ -419,8 +415,8 @@ void mel_spec_device(const MelGeom& g, const double* d_x, int64_t len, std::vect
   const int64_t off = 0;
   mel_run<double>(r, g, d_x, &off, &len, 1, s);
   int32_t nk = 0;
-  MELCHK(hipMemcpyAsync(&nk, r.nkept, sizeof nk, hipMemcpyDeviceToHost, s));
-  MELCHK(hipStreamSynchronize(s));
+  HIPCHK(hipMemcpyAsync(&nk, r.nkept, sizeof nk, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
   *nk_out = nk;
   out.assign((size_t)nk * g.nb, 0.0);
   if (nk == 0) return;
@@ -428,9 +424,9 @@ void mel_spec_device(const MelGeom& g, const double* d_x, int64_t len, std::vect
   const int64_t tot = (int64_t)nk * g.nb;
   hipLaunchKernelGGL(sg_mel_out, dim3((unsigned)std::min<int64_t>((tot + 255) / 256, 4096)), dim3(256), 0, s, r.spec,
                      r.kept, nk, g.nb, r.mn, r.mx, d_out);
-  MELCHK(hipGetLastError());
-  MELCHK(hipMemcpyAsync(out.data(), d_out, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost, s));
-  MELCHK(hipStreamSynchronize(s));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out.data(), d_out, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
 }
 
 void compare_sounds_device(const MelGeom& g, const double* tspec, int ncT, const float* d_x, const int64_t* offsets,
@@ -456,13 +452,13 @@ void compare_sounds_device(const MelGeom& g, const double* tspec, int ncT, const
   if (J > 0) {
     hipLaunchKernelGGL(sg_mel_compare, dim3((unsigned)J), dim3(64), (size_t)5 * g.nb * sizeof(double), s, d_jc, d_jj,
                        d_t, ncT, g.nb, r.spec, r.kept, r.cands, r.nkept, r.mn, r.mx, (methods & 8) ? 1 : 0, d_sims);
-    MELCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
   }
   std::vector<double> sims((size_t)J * 4);
   std::vector<int32_t> nk(n);
-  if (J) MELCHK(hipMemcpyAsync(sims.data(), d_sims, sims.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-  MELCHK(hipMemcpyAsync(nk.data(), r.nkept, nk.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  MELCHK(hipStreamSynchronize(s));
+  if (J) HIPCHK(hipMemcpyAsync(sims.data(), d_sims, sims.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(nk.data(), r.nkept, nk.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
   // compareSounds' reduction (R/matchPars.R:378-416): per method the column
   // values' sum with NAs dropped over the column count (penalizeLengthDif), else
   // their mean; the summary is the mean over the methods that are not NA

@@ -1,16 +1,11 @@
 // sg_mel_dev.h — what sg_mel.hip (compareSounds) and sg_ssm.hip (ssm) share on
 // the device side of tuneR's melfcc front end: the zero-padded real FFT of one
-// windowed frame in LDS and its power spectrum, and the buffers of a launch
-// sequence. Included by .hip files only.
+// windowed frame in LDS and its power spectrum, and a mel band of it. Included by
+// .hip files only.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <string>
-#include <vector>
-
-#include "sg_rmath.h"
-#include "soundgen_hip.h"
+#include <cstdint>
 
 namespace sg {
 
@@ -63,43 +58,6 @@ __device__ __forceinline__ double mel_band(const MelBand bd, const double* __res
   double acc = 0;
   for (int i = 0; i < bd.n; ++i) acc += wts[bd.w0 + i] * P[bd.k0 + i];
   return acc;
-}
-
-#define MELCHK(x)                                                                                        \
-  do {                                                                                                   \
-    hipError_t _e = (x);                                                                                 \
-    if (_e != hipSuccess) throw sg::SgError(SG_E_DEVICE, std::string(#x) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
-// Device buffers of one launch sequence, and the host copies their uploads read: an
-// async H2D copy from pageable memory may still be pending when the caller's
-// vector goes away, so upload() stages the bytes in memory this object owns.
-// The destructor frees the device buffers first (hipFree waits for the device),
-// then the staged host bytes.
-struct DevBuf {
-  std::vector<void*> p;
-  std::vector<std::vector<char>> host;
-  template <class T>
-  T* get(size_t n) {
-    void* q = nullptr;
-    MELCHK(hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)));
-    p.push_back(q);
-    return static_cast<T*>(q);
-  }
-  ~DevBuf() {
-    for (void* q : p) (void)hipFree(q);
-  }
-};
-
-template <class T>
-T* upload(DevBuf& db, const std::vector<T>& v, hipStream_t s) {
-  T* d = db.get<T>(v.size());
-  if (!v.empty()) {
-    const char* src = reinterpret_cast<const char*>(v.data());
-    db.host.emplace_back(src, src + v.size() * sizeof(T));
-    MELCHK(hipMemcpyAsync(d, db.host.back().data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
-  }
-  return d;
 }
 
 }  // namespace sg

@@ -39,6 +39,10 @@ struct SpgStat {
   int32_t scaled, pad;
 };
 
+// TN[t] = W_N^t = root64(t, N), t < N (device memory): a table of roots as fft64
+// (sg_fft64_dev.h) reads it, filled on stream s (the kernel sg_spg_roots)
+void fill_roots64(double2* d_TN, int N, hipStream_t s);
+
 // The launch sequence for n_calls sounds at d_x + offsets[c] (device memory, T =
 // float or double); matrices to d_out + out_off[c] (device memory). kernel_ms
 // (kSpgStages doubles or nullptr): the device time of each stage. d_stat_out (device,

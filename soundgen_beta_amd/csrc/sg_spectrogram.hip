@@ -10,7 +10,8 @@
 //   sg_spg_stats      getFrameBank's normalisation (:345-348): sum, min and max per
 //                     chunk of 64 Ki samples, then the squared deviations for
 //                     scale(); sg_spg_stats_fold folds a sound's chunks in a fixed order
-//   sg_spg_roots      W_N^t of the launch's frame length (the table fft64 reads)
+//   sg_spg_roots      W_N^t, t < N: a table fft64 reads (fill_roots64: the launch's frame
+//                     length here, the cepstrum's transform in sg_analyze.hip)
 //   sg_spg_frames     one workgroup per frame: normalisation on the fly, the window
 //                     (host table, R's operation order), zero padding, the packed real
 //                     transform through fft64, the untangling, |X_k| for k < N / 2
@@ -33,14 +34,12 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstring>
-#include <memory>
 #include <string>
 #include <vector>
 
-#include "sg_ctx.h"
+#include "sg_dev64.h"
 #include "sg_fft64_dev.h"
-#include "sg_mel_dev.h"
+#include "sg_launch.h"
 #include "sg_rmath.h"
 #include "sg_spectrogram.h"
 
@@ -78,32 +77,9 @@ struct SpgRange {
   int32_t nan, nvalid;
 };
 
-__device__ __forceinline__ unsigned long long dkey(double v) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double dunkey(unsigned long long k) {
-  return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
-}
-
 constexpr int kT = 256;  // threads of every workgroup here (SG_F64_THREADS for the frames)
 static_assert(SG_F64_THREADS == kT, "fft64 strides by SG_F64_THREADS");
 constexpr int kStatChunk = 1 << 16;
-
-// op 0: sum, 1: min, 2: max over the workgroup, in a fixed order; every thread gets the result
-__device__ __forceinline__ double block_reduce(double v, int op, double* red) {
-  __syncthreads();
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int o = kT / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) {
-      const double a = red[threadIdx.x], b = red[threadIdx.x + o];
-      red[threadIdx.x] = op == 0 ? a + b : op == 1 ? fmin(a, b) : fmax(a, b);
-    }
-    __syncthreads();
-  }
-  return red[0];
-}
 
 // quantile(type 7) from the two order statistics at floor / ceiling of index = 1 + (n - 1) p
 __device__ __forceinline__ double q7(double xlo, double xhi, int n, double p) {
@@ -134,9 +110,9 @@ __global__ __launch_bounds__(kT) void sg_spg_stats(const T* __restrict__ x, cons
       lo = fmin(lo, v);
       hi = fmax(hi, v);
     }
-    acc = block_reduce(acc, 0, red);
-    lo = block_reduce(lo, 1, red);
-    hi = block_reduce(hi, 2, red);
+    acc = block_reduce<kT>(acc, 0, red);
+    lo = block_reduce<kT>(lo, 1, red);
+    hi = block_reduce<kT>(hi, 2, red);
     if (threadIdx.x == 0) {
       part[3 * (int64_t)blockIdx.x] = acc;
       part[3 * (int64_t)blockIdx.x + 1] = lo;
@@ -149,7 +125,7 @@ __global__ __launch_bounds__(kT) void sg_spg_stats(const T* __restrict__ x, cons
       const double d = (double)xc[i] - mean;
       acc += d * d;
     }
-    acc = block_reduce(acc, 0, red);
+    acc = block_reduce<kT>(acc, 0, red);
     if (threadIdx.x == 0) part[3 * (int64_t)blockIdx.x] = acc;
   }
 }
@@ -335,8 +311,8 @@ __global__ __launch_bounds__(kT) void sg_spg_prep(const SpgFrame* __restrict__ f
     if (v > 0) lo = fmin(lo, v);
     bad |= isnan(v) ? 1 : 0;
   }
-  lo = block_reduce(lo, 1, red);
-  const double nb = block_reduce((double)bad, 2, red);
+  lo = block_reduce<kT>(lo, 1, red);
+  const double nb = block_reduce<kT>((double)bad, 2, red);
   if (threadIdx.x == 0) {
     if (lo < INFINITY) atomicMin(&range[F.snd].minpos, dkey(lo));
     if (nb > 0) atomicOr(&range[F.snd].nan, 1);
@@ -360,7 +336,7 @@ __global__ __launch_bounds__(kT) void sg_spg_log(const SpgFrame* __restrict__ fr
     r[b] = v;
     hi = fmax(hi, v);
   }
-  hi = block_reduce(hi, 2, red);
+  hi = block_reduce<kT>(hi, 2, red);
   if (threadIdx.x == 0 && hi > -INFINITY) atomicMax(&range[F.snd].max1, dkey(hi));
 }
 
@@ -381,9 +357,9 @@ __global__ __launch_bounds__(kT) void sg_spg_entropy(const SpgFrame* __restrict_
     s1 += y;
     sl += log(y);
   }
-  s0 = block_reduce(s0, 0, red);
-  s1 = block_reduce(s1, 0, red);
-  sl = block_reduce(sl, 0, red);
+  s0 = block_reduce<kT>(s0, 0, red);
+  s1 = block_reduce<kT>(s1, 0, red);
+  sl = block_reduce<kT>(sl, 0, red);
   if (threadIdx.x == 0) entr[S.f0 + F.f] = s0 == 0 ? NAN : exp(sl / (double)B) / (s1 / (double)B);
 }
 
@@ -465,7 +441,7 @@ __global__ __launch_bounds__(kT) void sg_spg_sub(const SpgFrame* __restrict__ fr
     r[b] = v;
     hi = fmax(hi, v);
   }
-  hi = block_reduce(hi, 2, red);
+  hi = block_reduce<kT>(hi, 2, red);
   if (threadIdx.x == 0 && hi > -INFINITY) atomicMax(&range[F.snd].max2, dkey(hi));
 }
 
@@ -497,6 +473,11 @@ double g_spg_ms[sg::kSpgStages];  // of the last profiled launch sequence
 }  // namespace
 
 namespace sg {
+
+void fill_roots64(double2* d_TN, int N, hipStream_t s) {
+  hipLaunchKernelGGL(sg_spg_roots, dim3((unsigned)((N + kT - 1) / kT)), dim3(kT), 0, s, d_TN, N);
+  HIPCHK(hipGetLastError());
+}
 
 template <typename T>
 void spectrogram_device(const SpgSetup& S, const T* d_x, const int64_t* offsets, const int64_t* lengths,
@@ -538,8 +519,8 @@ void spectrogram_device(const SpgSetup& S, const T* d_x, const int64_t* offsets,
     cells += (int64_t)nf * B;
     nfmax = std::max(nfmax, nf);
   }
-  if (kernel_ms)
-    for (int k = 0; k < kSpgStages; ++k) kernel_ms[k] = 0;
+  StageClock clk(s, kernel_ms, kSpgStages);
+  clk.zero();
   const int64_t F = (int64_t)fr.size();
   if (F == 0) return;
   const unsigned NS = (unsigned)n_calls;
@@ -548,54 +529,31 @@ void spectrogram_device(const SpgSetup& S, const T* d_x, const int64_t* offsets,
   const SpgFrame* d_fr = upload(db, fr, s);
   const SpgChunk* d_ch = upload(db, chunks, s);
   const double* d_win = upload(db, spg_window(S.wl, S.wn), s);
-  const double inf = INFINITY;
-  unsigned long long kinf, kninf;
-  {  // dkey on the host: the keys of +Inf (no positive cell yet) and -Inf (no maximum yet)
-    unsigned long long bits;
-    std::memcpy(&bits, &inf, 8);
-    kinf = bits | 0x8000000000000000ull;
-    const double ninf = -INFINITY;
-    std::memcpy(&bits, &ninf, 8);
-    kninf = ~bits;
-  }
+  // the keys of +Inf (no positive cell yet) and -Inf (no maximum yet)
+  const unsigned long long kinf = dkey(INFINITY), kninf = dkey(-INFINITY);
   SpgRange* d_range = upload(db, std::vector<SpgRange>(n_calls, SpgRange{kinf, kninf, kninf, 0.0, 0.0, 0, 0}), s);
   SpgStat* d_stat = upload(db, std::vector<SpgStat>(n_calls, SpgStat{0, 1, 1, 0, 0, 0, 0}), s);
   double* d_part = db.get<double>(3 * chunks.size());
   double2* d_TN = db.get<double2>((size_t)S.N);
-  struct Stamps {
-    hipEvent_t e[kSpgStages + 1] = {};
-    ~Stamps() {
-      for (hipEvent_t v : e)
-        if (v) (void)hipEventDestroy(v);
-    }
-  } st;
-  int stage = 0;
-  auto stamp = [&]() {  // one per stage boundary, in stage order
-    if (!kernel_ms) return;
-    MELCHK(hipEventCreate(&st.e[stage]));
-    MELCHK(hipEventRecord(st.e[stage], s));
-    ++stage;
-  };
   const dim3 gF((unsigned)F), bT(kT);
-  stamp();
+  clk.stamp();
   for (int pass = 0; pass < 2; ++pass) {
     hipLaunchKernelGGL(sg_spg_stats<T>, dim3((unsigned)chunks.size()), bT, 0, s, d_x, d_ch, d_snd, d_stat, pass, d_part);
-    MELCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(sg_spg_stats_fold, dim3((NS + 63) / 64), dim3(64), 0, s, d_part, d_snd, (int)n_calls, pass, d_stat);
-    MELCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
   }
   if (d_stat_out)  // for a caller that goes on with the normalised samples (sg_analyze.hip)
-    MELCHK(hipMemcpyAsync(d_stat_out, d_stat, (size_t)n_calls * sizeof(SpgStat), hipMemcpyDeviceToDevice, s));
-  stamp();  // 1: frames
-  hipLaunchKernelGGL(sg_spg_roots, dim3((unsigned)((S.N + kT - 1) / kT)), bT, 0, s, d_TN, S.N);
-  MELCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(d_stat_out, d_stat, (size_t)n_calls * sizeof(SpgStat), hipMemcpyDeviceToDevice, s));
+  clk.stamp();  // 1: frames
+  fill_roots64(d_TN, S.N, s);
   const int lds = (2 * B + 32) * (int)sizeof(double2);
   if (lds > 48 * 1024)
-    MELCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&sg_spg_frames<T>),
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&sg_spg_frames<T>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   hipLaunchKernelGGL(sg_spg_frames<T>, gF, bT, (size_t)lds, s, d_x, d_fr, d_snd, d_stat, d_win, d_TN, S.wl, S.pad, B,
                      d_out);
-  MELCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   if (S.processed) {
     // cur: where the matrices are (0: the output buffer, 1: the work buffer)
     double* bufs[2] = {d_out, nullptr};
@@ -604,78 +562,71 @@ void spectrogram_device(const SpgSetup& S, const T* d_x, const int64_t* offsets,
       if (!bufs[1]) bufs[1] = db.get<double>((size_t)cells);
       return 1 - cur;
     };
-    stamp();  // 2: derivative
+    clk.stamp();  // 2: derivative
     if (S.deriv) {
       const int o = other();
       hipLaunchKernelGGL(sg_spg_deriv, gF, bT, 0, s, d_fr, d_snd, bufs[cur], cur, bufs[o], o, B);
-      MELCHK(hipGetLastError());
+      HIPCHK(hipGetLastError());
       cur = o;
     }
-    stamp();  // 3: median along bins
+    clk.stamp();  // 3: median along bins
     if (S.kTime > 1) {
       const int o = other();
       hipLaunchKernelGGL(sg_spg_medbins, gF, bT, 0, s, d_fr, d_snd, bufs[cur], cur, bufs[o], o, B, S.kTime);
-      MELCHK(hipGetLastError());
+      HIPCHK(hipGetLastError());
       cur = o;
     }
-    stamp();  // 4: median along frames
+    clk.stamp();  // 4: median along frames
     if (S.kFreq > 1) {
       const int o = other();
       hipLaunchKernelGGL(sg_spg_medframes, gF, bT, 0, s, d_fr, d_snd, bufs[cur], cur, bufs[o], o, B, S.kFreq);
-      MELCHK(hipGetLastError());
+      HIPCHK(hipGetLastError());
       cur = o;
     }
-    stamp();  // 5: frame quantile, smallest positive cell
+    clk.stamp();  // 5: frame quantile, smallest positive cell
     hipLaunchKernelGGL(sg_spg_prep, gF, bT, 0, s, d_fr, d_snd, bufs[cur], cur, B, S.qTime > 0 ? S.qTime : 0.0, d_range);
-    MELCHK(hipGetLastError());
-    stamp();  // 6: log
+    HIPCHK(hipGetLastError());
+    clk.stamp();  // 6: log
     hipLaunchKernelGGL(sg_spg_log, gF, bT, 0, s, d_fr, d_snd, bufs[cur], cur, B, d_range);
-    MELCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     const bool nr = S.noiseReduction > 0;
     double* d_entr = nullptr;
     double* d_noise = nullptr;
     int32_t* d_nsel = nullptr;
     const double p = 1 - S.percentNoise / 100;
-    stamp();  // 7: entropy
+    clk.stamp();  // 7: entropy
     if (nr) {
       d_entr = db.get<double>((size_t)F);
       d_noise = db.get<double>((size_t)n_calls * B);
       d_nsel = db.get<int32_t>((size_t)n_calls);
       hipLaunchKernelGGL(sg_spg_entropy, gF, bT, 0, s, d_fr, d_snd, bufs[cur], cur, B, d_entr);
-      MELCHK(hipGetLastError());
+      HIPCHK(hipGetLastError());
     }
-    stamp();  // 8: entropy quantile
+    clk.stamp();  // 8: entropy quantile
     if (nr) {
       hipLaunchKernelGGL(sg_spg_entq, dim3((unsigned)((nfmax + kT - 1) / kT), NS), bT, 0, s, d_snd, d_entr, p, d_range);
-      MELCHK(hipGetLastError());
+      HIPCHK(hipGetLastError());
     }
-    stamp();  // 9: noise spectrum
+    clk.stamp();  // 9: noise spectrum
     if (nr) {
       hipLaunchKernelGGL(sg_spg_noise, dim3((unsigned)((B + kT - 1) / kT), NS), bT, 0, s, d_snd, d_entr, d_range, p,
                          bufs[cur], cur, B, d_noise, d_nsel);
-      MELCHK(hipGetLastError());
+      HIPCHK(hipGetLastError());
     }
-    stamp();  // 10: subtraction
+    clk.stamp();  // 10: subtraction
     if (nr) {
       hipLaunchKernelGGL(sg_spg_sub, gF, bT, 0, s, d_fr, d_snd, bufs[cur], cur, B, S.noiseReduction, d_noise, d_nsel,
                          d_range);
-      MELCHK(hipGetLastError());
+      HIPCHK(hipGetLastError());
     }
-    stamp();  // 11: power and scale, into the output buffer
+    clk.stamp();  // 11: power and scale, into the output buffer
     hipLaunchKernelGGL(sg_spg_final, gF, bT, 0, s, d_fr, d_snd, bufs[cur], cur, d_out, 0, B, S.contrast_exp,
                        S.brightness_exp, nr ? 1 : 0, d_range);
-    MELCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
   }
-  stamp();
-  MELCHK(hipStreamSynchronize(s));
-  if (kernel_ms) {
-    // 'original' stops after the frames: stamps 0, 1, 2; 'processed' records all 13
-    for (int k = 0; k + 1 < stage; ++k) {
-      float ms = 0;
-      MELCHK(hipEventElapsedTime(&ms, st.e[k], st.e[k + 1]));
-      kernel_ms[k] = ms;
-    }
-  }
+  clk.stamp();
+  HIPCHK(hipStreamSynchronize(s));
+  clk.finish();  // 'original' stops after the frames: stamps 0, 1, 2; 'processed' records all 13
 }
 
 template void spectrogram_device<float>(const SpgSetup&, const float*, const int64_t*, const int64_t*, int64_t, double*,
@@ -687,29 +638,7 @@ template void spectrogram_device<double>(const SpgSetup&, const double*, const i
 
 // The C entry points that touch the device live here, not in sg_api.cpp: the
 // host-only sanitizer build links sg_api.cpp without this file's device code.
-namespace {
-
-template <class F>
-int guarded(sg_ctx* ctx, F&& f) {
-  int code;
-  std::string msg;
-  try {
-    return f();
-  } catch (const sg::SgError& e) {
-    code = e.code;
-    msg = e.what();
-  } catch (const std::bad_alloc&) {
-    code = SG_E_NOMEM;
-    msg = "out of host memory";
-  } catch (const std::exception& e) {
-    code = SG_E_ARG;
-    msg = e.what();
-  }
-  if (ctx) ctx->err = msg;
-  return code;
-}
-
-}  // namespace
+using sg::guarded;
 
 extern "C" {
 
@@ -719,18 +648,14 @@ int sg_spectrogram(sg_ctx* ctx, const double* wave, int64_t len, const sg_spectr
     const sg::SpgSetup S = sg::spg_setup(*p);
     if (len < S.wl || len < 2)
       throw sg::SgError(SG_E_ARG, "sg_spectrogram: the sound is shorter than the window (R would index past its end)");
-    MELCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->device));
     const int64_t cells = (int64_t)sg::spg_frames(S, len) * S.bins;
-    sg::DevBuf db;
-    double* d = db.get<double>((size_t)len);
-    double* d_o = db.get<double>((size_t)cells);
-    MELCHK(hipMemcpyAsync(d, wave, (size_t)len * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    MELCHK(hipStreamSynchronize(ctx->stream));
-    const int64_t off = 0;
-    int32_t b = 0, f = 0;
-    sg::spectrogram_device<double>(S, d, &off, &len, 1, d_o, &off, &b, &f, ctx->stream,
-                                   ctx->profiling ? g_spg_ms : nullptr);
-    MELCHK(hipMemcpy(out, d_o, (size_t)cells * sizeof(double), hipMemcpyDeviceToHost));
+    sg::single_sound(ctx, wave, len, cells, out, [&](const double* d, double* d_o) {
+      const int64_t off = 0;
+      int32_t b = 0, f = 0;
+      sg::spectrogram_device<double>(S, d, &off, &len, 1, d_o, &off, &b, &f, ctx->stream,
+                                     ctx->profiling ? g_spg_ms : nullptr);
+    });
     return SG_OK;
   });
 }
@@ -744,7 +669,7 @@ int sg_spectrogram_batch(sg_ctx* ctx, const float* d_wave, const int64_t* offset
       throw sg::SgError(SG_E_ARG, "sg_spectrogram_batch: bad arguments");
     const sg::SpgSetup S = sg::spg_setup(*p);
     if (n_calls == 0) return SG_OK;
-    MELCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->device));
     sg::spectrogram_device<float>(S, d_wave, offsets, lengths, n_calls, d_out, out_off, bins_out, frames_out,
                                   ctx->stream, ctx->profiling ? g_spg_ms : nullptr);
     return SG_OK;

@@ -32,11 +32,11 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <memory>
 #include <string>
 #include <vector>
 
-#include "sg_ctx.h"
+#include "sg_dev64.h"
+#include "sg_launch.h"
 #include "sg_mel.h"
 #include "sg_mel_dev.h"
 #include "sg_rmath.h"
@@ -78,19 +78,6 @@ struct SsmRange {
   int32_t nan, pad;
 };
 
-__device__ __forceinline__ unsigned long long dkey(double v) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double dunkey(unsigned long long k) {
-  return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
-}
-
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 __device__ __forceinline__ double wmin(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o));
@@ -133,14 +120,8 @@ __global__ __launch_bounds__(256) void sg_ssm_stats(const T* __restrict__ x, con
     const double mean = stat[2 * J.snd];
     for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) acc = fmax(acc, fabs((double)xc[i] - mean));
   }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o)
-      red[threadIdx.x] = pass ? fmax(red[threadIdx.x], red[threadIdx.x + o]) : red[threadIdx.x] + red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) part[blockIdx.x] = red[0];
+  acc = block_reduce<256>(acc, pass ? 2 : 0, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = acc;
 }
 
 // one wavefront per sound: its chunks' partial sums into the mean (pass 0), their
@@ -499,22 +480,8 @@ void ssm_device(const SsmSetup& S, const T* d_x, const int64_t* offsets, const i
   const double* d_kc = upload(db, kc, s);
   std::vector<SsmRange> r0(n_calls, SsmRange{~0ull, 0ull, 0, 0});
   SsmRange* d_range = upload(db, r0, s);
-  // kernel_ms: device time of each stage between events on the stream (profiling only)
-  struct Stamps {
-    hipEvent_t e[kSsmStages + 1] = {};
-    ~Stamps() {
-      for (hipEvent_t v : e)
-        if (v) (void)hipEventDestroy(v);
-    }
-  } st;
-  int stage = 0;
-  auto stamp = [&]() {
-    if (!kernel_ms) return;
-    MELCHK(hipEventCreate(&st.e[stage]));
-    MELCHK(hipEventRecord(st.e[stage], s));
-    ++stage;
-  };
-  stamp();
+  StageClock clk(s, kernel_ms, kSsmStages);
+  clk.stamp();
   double* d_stat = nullptr;
   if (S.normalize) {
     d_stat = db.get<double>((size_t)2 * n_calls);
@@ -523,19 +490,19 @@ void ssm_device(const SsmSetup& S, const T* d_x, const int64_t* offsets, const i
     for (int pass = 0; pass < 2; ++pass) {
       hipLaunchKernelGGL(sg_ssm_stats<T>, dim3((unsigned)chunks.size()), dim3(256), 0, s, d_x, d_ch, d_snd, d_stat, pass,
                          d_part);
-      MELCHK(hipGetLastError());
+      HIPCHK(hipGetLastError());
       hipLaunchKernelGGL(sg_ssm_stats_fold, dim3((unsigned)n_calls), dim3(64), 0, s, d_part, d_snd, pass, d_stat);
-      MELCHK(hipGetLastError());
+      HIPCHK(hipGetLastError());
     }
   }
-  stamp();
+  clk.stamp();
   double* d_raw = db.get<double>((size_t)F * R);
   int logM = 0;
   while ((1 << logM) < M) ++logM;
   hipLaunchKernelGGL(sg_ssm_frames<T>, dim3((unsigned)F), dim3(256), (size_t)2 * M * sizeof(double2), s, d_x, d_fr,
                      d_stat, d_ham, d_tw, d_twN, S.input == 2 ? nullptr : d_bands, d_w, g.winpts, M, logM, g.nb, d_raw);
-  MELCHK(hipGetLastError());
-  stamp();
+  HIPCHK(hipGetLastError());
+  clk.stamp();
   double* d_feat = d_raw;  // audiogram / spectrum without norm: the rows as they are
   if (S.input == 0 || S.norm) {
     const double *d_dct = nullptr, *d_lift = nullptr;
@@ -548,45 +515,38 @@ void ssm_device(const SsmSetup& S, const T* d_x, const int64_t* offsets, const i
     d_feat = db.get<double>((size_t)F * D);
     hipLaunchKernelGGL(sg_ssm_feat, dim3((unsigned)F), dim3(256), (size_t)(R + D) * sizeof(double), s, d_raw, R, d_dct,
                        d_lift, D, S.norm, d_feat);
-    MELCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
   }
-  stamp();
+  clk.stamp();
   double* d_wmean = db.get<double>((size_t)W);
   double* d_wnn = db.get<double>((size_t)W);
   hipLaunchKernelGGL(sg_ssm_winstat, dim3((unsigned)W), dim3(64), 0, s, d_feat, d_ws, d_wsnd, d_snd, S.simil == 1,
                      d_wmean, d_wnn);
-  MELCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   double* d_ssm = db.get<double>((size_t)cells);
-  stamp();
+  clk.stamp();
   hipLaunchKernelGGL(sg_ssm_gram, dim3((unsigned)tiles.size()), dim3(64), 0, s, d_tiles, d_snd, d_feat, d_ws, d_wmean,
                      d_wnn, 0, d_ssm, d_range);
-  MELCHK(hipGetLastError());
+  HIPCHK(hipGetLastError());
   double* d_nov = db.get<double>((size_t)npts);
-  stamp();
+  clk.stamp();
   hipLaunchKernelGGL(sg_ssm_novelty, dim3((unsigned)npts), dim3(64), 0, s, d_pts, d_snd, d_ssm, d_range, d_kc, kss, S.K,
                      d_nov0, d_nov);
-  MELCHK(hipGetLastError());
-  stamp();
+  HIPCHK(hipGetLastError());
+  clk.stamp();
   std::vector<double> hn((size_t)npts), hs;
-  MELCHK(hipMemcpyAsync(hn.data(), d_nov, hn.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(hn.data(), d_nov, hn.size() * sizeof(double), hipMemcpyDeviceToHost, s));
   if (ssm_out) {
     const int64_t per = (int64_t)nmax * nmax;
     hipLaunchKernelGGL(sg_ssm_out, dim3((unsigned)n_calls, (unsigned)std::min<int64_t>((per + 255) / 256, 1024)),
                        dim3(256), 0, s, d_snd, d_range, d_ssm);
-    MELCHK(hipGetLastError());
-    stamp();
+    HIPCHK(hipGetLastError());
+    clk.stamp();
     hs.resize((size_t)cells);
-    MELCHK(hipMemcpyAsync(hs.data(), d_ssm, hs.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(hs.data(), d_ssm, hs.size() * sizeof(double), hipMemcpyDeviceToHost, s));
   }
-  MELCHK(hipStreamSynchronize(s));
-  if (kernel_ms) {
-    for (int k = 0; k < kSsmStages; ++k) kernel_ms[k] = 0;
-    for (int k = 0; k + 1 < stage; ++k) {
-      float ms = 0;
-      MELCHK(hipEventElapsedTime(&ms, st.e[k], st.e[k + 1]));
-      kernel_ms[k] = ms;
-    }
-  }
+  HIPCHK(hipStreamSynchronize(s));
+  clk.finish();
   for (int64_t c = 0; c < n_calls; ++c) {
     const int64_t n = snds[c].n;
     if (n == 0) continue;
@@ -618,38 +578,16 @@ void ssm_debug_gram(const double* feat, int L, int n, double* out, hipStream_t s
   double* d_ssm = db.get<double>((size_t)n * n);
   hipLaunchKernelGGL(sg_ssm_gram, dim3((unsigned)tiles.size()), dim3(64), 0, s, d_tiles, d_snd, d_feat, d_ws, d_zero,
                      d_zero, 1, d_ssm, d_range);
-  MELCHK(hipGetLastError());
-  MELCHK(hipMemcpyAsync(out, d_ssm, (size_t)n * n * sizeof(double), hipMemcpyDeviceToHost, s));
-  MELCHK(hipStreamSynchronize(s));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, d_ssm, (size_t)n * n * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
 }
 
 }  // namespace sg
 
 // The C entry points live here, not in sg_api.cpp: the host-only sanitizer build
 // links sg_api.cpp without this file's device code.
-namespace {
-
-template <class F>
-int guarded(sg_ctx* ctx, F&& f) {
-  int code;
-  std::string msg;
-  try {
-    return f();
-  } catch (const sg::SgError& e) {
-    code = e.code;
-    msg = e.what();
-  } catch (const std::bad_alloc&) {
-    code = SG_E_NOMEM;
-    msg = "out of host memory";
-  } catch (const std::exception& e) {
-    code = SG_E_ARG;
-    msg = e.what();
-  }
-  if (ctx) ctx->err = msg;
-  return code;
-}
-
-}  // namespace
+using sg::guarded;
 
 extern "C" {
 
@@ -658,13 +596,10 @@ int sg_ssm(sg_ctx* ctx, const double* wave, int64_t len, const sg_ssm_params* p,
   return guarded(ctx, [&]() {
     if (!ctx || !p || !wave || !novelty_out) throw sg::SgError(SG_E_ARG, "sg_ssm: bad arguments");
     if (len < 2) throw sg::SgError(SG_E_ARG, "sg_ssm: the sound must be longer than 1 sample");
-    MELCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->device));
     const sg::SsmSetup S = sg::ssm_setup(*p);
-    double* d = nullptr;
-    MELCHK(hipMalloc(&d, (size_t)len * sizeof(double)));
-    std::unique_ptr<double, void (*)(double*)> hold(d, [](double* q) { (void)hipFree(q); });
-    MELCHK(hipMemcpyAsync(d, wave, (size_t)len * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    MELCHK(hipStreamSynchronize(ctx->stream));
+    DevBuf db;
+    const double* d = sg::upload_sound(db, wave, len, ctx->stream);
     const int64_t off = 0;
     int32_t n = 0;
     sg::ssm_device<double>(S, d, &off, &len, 1, &n, novelty_out, &off, ssm_out, &off, ctx->stream,
@@ -681,7 +616,7 @@ int sg_ssm_batch(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, const
         (n_calls > 0 && (!d_wave || !offsets || !lengths || !n_out || !novelty_out || !novelty_off)) ||
         (ssm_out && !ssm_off))
       throw sg::SgError(SG_E_ARG, "sg_ssm_batch: bad arguments");
-    MELCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->device));
     const sg::SsmSetup S = sg::ssm_setup(*p);
     if (n_calls == 0) return SG_OK;
     sg::ssm_device<float>(S, d_wave, offsets, lengths, n_calls, n_out, novelty_out, novelty_off, ssm_out, ssm_off,
@@ -693,7 +628,7 @@ int sg_ssm_batch(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, const
 int sg_debug_ssm_gram(sg_ctx* ctx, const double* feat, int32_t L, int32_t n, double* out) {
   return guarded(ctx, [&]() {
     if (!ctx || !feat || !out || L < 1 || n < 1 || n > 4096) throw sg::SgError(SG_E_ARG, "sg_debug_ssm_gram: bad arguments");
-    MELCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipSetDevice(ctx->device));
     sg::ssm_debug_gram(feat, L, n, out, ctx->stream);
     return SG_OK;
   });

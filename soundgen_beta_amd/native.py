@@ -271,6 +271,34 @@ class Node:
             pass
 
 
+# ------------------------------------------------ marshalling of the *_batch entry points
+def batch_layout(offsets, lengths):
+    """The calls of a packed batch as the library reads them: (offs, lens, nc, p_offs,
+    p_lens), contiguous int64 arrays (keep them alive across the call) and their pointers."""
+    import numpy as np
+    i64p = C.POINTER(C.c_int64)
+    offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+    lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64))
+    return offs, lens, len(offs), offs.ctypes.data_as(i64p), lens.ctypes.data_as(i64p)
+
+
+def out_offsets(cells):
+    """Where each call's output starts in one packed buffer, from the cells of every
+    call: nc + 1 int64 (the last is the total), and the pointer."""
+    import numpy as np
+    ooff = np.concatenate([[0], np.cumsum(cells)]).astype(np.int64)
+    return ooff, ooff.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+def device_out(data, n):
+    """An fp64 tensor of n cells (at least 1) beside `data`, once the caller's work
+    on data's device is done: the library runs on its own stream."""
+    import torch
+    out = torch.empty(max(int(n), 1), dtype=torch.float64, device=data.device)
+    torch.cuda.synchronize(data.device)
+    return out
+
+
 _default_ctx = {}
 
 

@@ -391,32 +391,26 @@ def spectrogram_batch(data, offsets, lengths, samplingRate, windowLength=50, ste
     .view(frames, bins).T is bins x frames). to_host=True returns the list of
     bins x frames arrays instead. A call with lengths[i] <= 1 or shorter than the
     window has 0 frames."""
-    import torch
     kF, kT = _settings(wn, smoothFreq, smoothTime, method, output, False, False)
     L = native.lib()
     P = _params(samplingRate, windowLength, step, overlap, wn, zp, smoothFreq, smoothTime, qTime, percentNoise,
                 noiseReduction, contrast, brightness, method, output)
-    offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
-    lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64))
-    nc = len(offs)
+    offs, lens, nc, p_offs, p_lens = native.batch_layout(offsets, lengths)
     shapes = []
     for i in range(nc):
         _, _, bins, frames = _size(L, P, int(lens[i]))
         if frames and output == "processed":
             _check_extent(kF, kT, bins, frames, " of call %d" % i)
         shapes.append((bins, frames))
-    cells = np.array([b * f for b, f in shapes], dtype=np.int64)
-    ooff = np.concatenate([[0], np.cumsum(cells)]).astype(np.int64)
+    ooff, p_ooff = native.out_offsets([b * f for b, f in shapes])
     ctx = native.default_context(device)
-    out = torch.empty(max(int(ooff[-1]), 1), dtype=torch.float64, device=data.device)
     bo = np.zeros(max(nc, 1), dtype=np.int32)
     fo = np.zeros(max(nc, 1), dtype=np.int32)
-    i64p, i32p = C.POINTER(C.c_int64), C.POINTER(C.c_int32)
-    torch.cuda.synchronize(data.device)  # the library runs on its own stream
-    native.check(L.sg_spectrogram_batch(ctx.ptr, C.c_void_p(data.data_ptr()), offs.ctypes.data_as(i64p),
-                                        lens.ctypes.data_as(i64p), nc, C.byref(P), C.c_void_p(out.data_ptr()),
-                                        ooff.ctypes.data_as(i64p), bo.ctypes.data_as(i32p), fo.ctypes.data_as(i32p)),
-                 ctx.ptr)
+    i32p = C.POINTER(C.c_int32)
+    out = native.device_out(data, ooff[-1])
+    native.check(L.sg_spectrogram_batch(ctx.ptr, C.c_void_p(data.data_ptr()), p_offs, p_lens, nc, C.byref(P),
+                                        C.c_void_p(out.data_ptr()), p_ooff, bo.ctypes.data_as(i32p),
+                                        fo.ctypes.data_as(i32p)), ctx.ptr)
     if [(int(b), int(f)) for b, f in zip(bo[:nc], fo[:nc])] != shapes:
         raise native.SoundgenError(-1, "sg_spectrogram_batch: shapes disagree with sg_spectrogram_size")
     if not to_host:

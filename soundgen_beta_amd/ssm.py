@@ -383,25 +383,22 @@ def ssm_batch(data, offsets, lengths, samplingRate, windowLength=40, overlap=75,
     ctx = native.default_context(device)
     P = _params(samplingRate, windowLength, overlap, step, ssmWin, maxFreq, nBands, mf, input, norm, simil,
                 kernelLen, kernelSD, True)
-    offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
-    lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64))
-    nc = len(offs)
+    offs, lens, nc, p_offs, p_lens = native.batch_layout(offsets, lengths)
     ns = np.zeros(nc, dtype=np.int64)
     o = [C.c_int32() for _ in range(4)]
     for i in range(nc):
         native.check(L.sg_ssm_size(int(lens[i]), C.byref(P), *[C.byref(v) for v in o]), ctx.ptr)
         ns[i] = o[1].value
-    noff = np.concatenate([[0], np.cumsum(ns)]).astype(np.int64)
-    soff = np.concatenate([[0], np.cumsum(ns * ns)]).astype(np.int64)
+    noff, p_noff = native.out_offsets(ns)
+    soff, p_soff = native.out_offsets(ns * ns)
     nov = np.zeros(max(int(noff[-1]), 1))
     S = np.zeros(max(int(soff[-1]), 1)) if returnSSM else None
     n_out = np.zeros(max(nc, 1), dtype=np.int32)
-    dp, i64p = C.POINTER(C.c_double), C.POINTER(C.c_int64)
-    native.check(L.sg_ssm_batch(ctx.ptr, C.c_void_p(data.data_ptr()), offs.ctypes.data_as(i64p),
-                                lens.ctypes.data_as(i64p), nc, C.byref(P),
+    dp = C.POINTER(C.c_double)
+    native.check(L.sg_ssm_batch(ctx.ptr, C.c_void_p(data.data_ptr()), p_offs, p_lens, nc, C.byref(P),
                                 n_out.ctypes.data_as(C.POINTER(C.c_int32)), nov.ctypes.data_as(dp),
-                                noff.ctypes.data_as(i64p), S.ctypes.data_as(dp) if returnSSM else None,
-                                soff.ctypes.data_as(i64p) if returnSSM else None), ctx.ptr)
+                                p_noff, S.ctypes.data_as(dp) if returnSSM else None,
+                                p_soff if returnSSM else None), ctx.ptr)
     if not np.array_equal(n_out[:nc], ns):
         raise native.SoundgenError(-1, "sg_ssm_batch: n_out disagrees with sg_ssm_size")
     novs = [nov[noff[i]:noff[i + 1]].copy() for i in range(nc)]
