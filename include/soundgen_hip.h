@@ -585,6 +585,58 @@ int sg_pitch_candidates(sg_ctx* ctx, const double* wave, int64_t len, const sg_p
 int sg_pitch_candidates_batch(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, const int64_t* lengths,
                               int64_t n_calls, const sg_pitch_params* p, double* d_out, const int64_t* out_off,
                               int32_t* frames_out);
+/* analyze(): sg_pitch_candidates plus the tail behind the candidates (an additive
+ * extension of ABI 5; R/analyze.R:576-707, R/utilities_pitch_postprocessing.R): the
+ * prior, findVoicedSegments, pathfinder per voiced segment (interpolate, pathfinding
+ * 'none' / 'fast', snake), medianSmoother and the final columns. p: as for
+ * sg_pitch_candidates. priorMean / priorSD (semitones): the prior applies when both are
+ * numbers (NaN = not numeric: no prior; SG_E_ARG unless positive). minVoicedCands: NaN
+ * = 'autom' (also taken when < 1 or above the number of methods). shortestSyl,
+ * shortestPause in ms (shortestPause >= 0). interpolWin: a whole number of frames (<= 0:
+ * no interpolation). certWeight in [0, 1]. snakeStep <= 0 or NaN: no snake. smooth <= 0
+ * or NaN: no smoothing. pathfinding: 0 'none', 1 'fast', 2 'slow' (SG_E_UNSUPPORTED:
+ * simulated annealing on R's random stream is not built). smoothVars: bit 0 'pitch', bit
+ * 1 'dom'. SG_E_UNSUPPORTED also for interpolWin or half the smoothing window above 64
+ * frames and for 0 < snakeStep < 0.005. */
+typedef struct sg_analyze_params_full {
+  sg_pitch_params p;
+  double priorMean;
+  double priorSD;
+  double minVoicedCands;
+  double shortestSyl;
+  double shortestPause;
+  double interpolWin;
+  double interpolTol;
+  double interpolCert;
+  double certWeight;
+  double snakeStep;
+  double smooth;
+  int32_t pathfinding;
+  int32_t smoothVars;
+} sg_analyze_params_full;
+/* The integer decisions for a sound of len samples (host only, no device): the frame
+ * count, the columns of a row (15 + 6 nCands + 4: those of sg_pitch_candidates_size,
+ * then pitch, amplVoiced, voiced (0 / 1), harmonics) and, in extra (8 int32 or NULL):
+ * minVoicedCands resolved, noRequired = max(1, ceiling(shortestSyl / step)),
+ * nToleratedNA = floor(shortestPause / step), hw = floor(round(smooth * frames /
+ * duration / 10) / 2) (R's round: half to even), interpolWin, and zeros. The refusals of
+ * sg_pitch_candidates_size hold. Errors through sg_analyze_frames_size_error. */
+int sg_analyze_size(int64_t len, const sg_analyze_params_full* p, int32_t* frames, int32_t* cols, int32_t* extra);
+/* sg_pitch_candidates / sg_pitch_candidates_batch with rows of 15 + 6 nCands + 4 columns:
+ * the columns analyze() does not rewrite equal sg_pitch_candidates' bit for bit; HNR and
+ * harmonics are in dB, dom is smoothed (if asked for), the quartiles are NaN for unvoiced
+ * frames. A sound's table is the same bit for bit alone and in any batch. */
+int sg_analyze(sg_ctx* ctx, const double* wave, int64_t len, const sg_analyze_params_full* p, double* out);
+int sg_analyze_batch(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, const int64_t* lengths, int64_t n_calls,
+                     const sg_analyze_params_full* p, double* d_out, const int64_t* out_off, int32_t* frames_out);
+/* The tail alone, from a HOST table of `frames` rows of 15 + 6 nCands columns (a
+ * sg_pitch_candidates table, or the caller's own candidates) of a sound of len samples
+ * (len decides the smoothing window): out receives frames rows of 15 + 6 nCands + 4
+ * columns; harmonics, which needs the spectrum, is NaN. Of p->p only a.samplingRate,
+ * a.step, a.windowLength, a.overlap, a.nCands, a.pitchFloor, a.pitchCeiling and a.methods
+ * are read. */
+int sg_pitch_path(sg_ctx* ctx, const double* table, int32_t frames, int64_t len, const sg_analyze_params_full* p,
+                  double* out);
 /* Process-wide policy of the fp64 filter path for later sg_plan_batch calls:
  * mode 0 never, 1 when the conditioning estimate exceeds rho (default 100),
  * 2 every filtered bout. SG_E_ARG for an invalid mode or rho. */
@@ -726,6 +778,10 @@ int sg_debug_analyze_kernel_ms(double* out);
  * stages above, then the cepstrum and its peaks, then the spectral peaks and the
  * BaNa candidates (6 doubles; 0 for a stage that was not launched). */
 int sg_debug_pitch_kernel_ms(double* out);
+/* The same for the last sg_analyze / sg_analyze_batch / sg_pitch_path run: the 6 stages
+ * above, then the path stage (segments, pathfinder, smoother, final columns), then the
+ * harmonics (8 doubles; sg_pitch_path runs the seventh alone). */
+int sg_debug_track_kernel_ms(double* out);
 
 #ifdef __cplusplus
 }

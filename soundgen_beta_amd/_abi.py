@@ -70,6 +70,13 @@ class sg_pitch_params(C.Structure):
                                    "specHNRslope", "specSmooth", "specMerge")]
 
 
+class sg_analyze_params_full(C.Structure):
+    _fields_ = [("p", sg_pitch_params)] + \
+        [(f, C.c_double) for f in ("priorMean", "priorSD", "minVoicedCands", "shortestSyl", "shortestPause",
+                                   "interpolWin", "interpolTol", "interpolCert", "certWeight", "snakeStep", "smooth")] + \
+        [("pathfinding", C.c_int32), ("smoothVars", C.c_int32)]
+
+
 NORM_CB = C.CFUNCTYPE(C.c_double, C.c_void_p)
 UNIF_CB = C.CFUNCTYPE(C.c_double, C.c_void_p)
 GAMMA_CB = C.CFUNCTYPE(C.c_double, C.c_void_p, C.c_double, C.c_double)

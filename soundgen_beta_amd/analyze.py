@@ -28,12 +28,15 @@ What is returned is the stage's output BEFORE the pathfinder, so:
       the pathfinder).
 Differences from the reference's defaults: analyze_frames*' pitchMethods accepts a
 non-empty subset of ('autocor', 'dom'); the reference's default also has 'spec', and
-'cep' exists: both raise NotImplementedError there. pitch_candidates* (at the end of
-this module) run all four: getPitchCep (R/utilities_analyze.R:337-407) and getPitchSpec
-(:424-558) restated likewise and on the GPU (sg_anl_cep, sg_anl_bana), plus
-pitch_matrices (the pathfinder's inputs, R/analyze.R:578-591). The pathfinder is not built.
-Formants (phonTools is not in the reference tree), plots, summary and savePath are
-out of scope.
+'cep' exists: both raise NotImplementedError there. pitch_candidates* (further down) run
+all four: getPitchCep (R/utilities_analyze.R:337-407) and getPitchSpec (:424-558) restated
+likewise and on the GPU (sg_anl_cep, sg_anl_bana), plus pitch_matrices (the pathfinder's
+inputs, R/analyze.R:578-591). analyze* (at the end of this module) add what follows the
+candidates (R/analyze.R:576-707, R/utilities_pitch_postprocessing.R): the prior,
+findVoicedSegments, pathfinder, medianSmoother and the final columns, restated as
+analyze_numpy / pitch_path_numpy and on the GPU (sg_anl_path, sg_anl_harm; sg_path.h).
+Formants (phonTools is not in the reference tree), pathfinding = 'slow', the pitchAutocor /
+pitchCep / pitchSpec columns, plots, summary and savePath are out of scope.
 
 Quirks kept (what the statements do):
     * the frequency labels pass through R's character row names (spectrogram.R:176,
@@ -500,16 +503,18 @@ def _run(sound, sr, s, decisions, params, table, entry, device):
     return table(out.reshape(d["frames"], d["cols"]), s["nCands"], len(sound), sr, s["step"])
 
 
-def _run_batch(data, offsets, lengths, samplingRate, s, frames_of, params, table, cand_keys, entry, to_host, device):
+def _run_batch(data, offsets, lengths, samplingRate, s, frames_of, params, table, cand_keys, entry, to_host, device,
+               tail=()):
     """The *_batch forms likewise: frames_of(length, P) is the stage's frame count of a
-    sound, cand_keys name the nCands-wide column groups behind the fixed columns, and
-    the C entry points are entry + "_batch" and (in the text of the cross-check) entry + "_size"."""
+    sound, cand_keys name the nCands-wide column groups behind the fixed columns, `tail`
+    the single columns behind those, and the C entry points are entry + "_batch" and (in
+    the text of the cross-check) entry + "_size"."""
     L = native.lib()
     P = params(s)
     offs, lens, nc, p_offs, p_lens = native.batch_layout(offsets, lengths)
     nC = s["nCands"]
     frames = [frames_of(int(n), P) for n in lens]
-    cols = NFIXED + len(cand_keys) * nC
+    cols = NFIXED + len(cand_keys) * nC + len(tail)
     ooff, p_ooff = native.out_offsets([f * cols for f in frames])
     ctx = native.default_context(device)
     fo = np.zeros(max(nc, 1), dtype=np.int32)
@@ -521,7 +526,7 @@ def _run_batch(data, offsets, lengths, samplingRate, s, frames_of, params, table
         raise native.SoundgenError(-1, "%s_batch: frame counts disagree with %s_size" % (entry, entry))
     if not to_host:
         return dict(out=out, offsets=ooff[:-1].copy(), frames=frames, cols=cols,
-                    columns=COLUMNS + sum(((k,) * nC for k in cand_keys), ()))
+                    columns=COLUMNS + sum(((k,) * nC for k in cand_keys), ()) + tuple(tail))
     h = out.cpu().numpy()
     return [table(h[ooff[i]:ooff[i + 1]].reshape(frames[i], cols), nC, int(lens[i]), samplingRate, s["step"])
             for i in range(nc)]
@@ -805,10 +810,10 @@ def pitch_candidates_numpy(x, samplingRate=None, silence=0.04, windowLength=50, 
     _probe: receives analyze_frames_numpy()'s intermediates and, per tracked frame,
     the traces of get_pitch_cep / get_pitch_spec (`cep`, `spec`).
 
-    Not built (sequential host logic over these candidates): the prior
-    (R/analyze.R:593-612), findVoicedSegments and the pathfinder, and the pitchAutocor /
-    pitchCep / pitchSpec columns (:659-667), which hinge on what as.numeric does with
-    zero-length list elements and cannot be settled without R."""
+    What follows these candidates (the prior, R/analyze.R:593-612, findVoicedSegments, the
+    pathfinder, the smoothing) is analyze_numpy()'s. Not built: the pitchAutocor / pitchCep /
+    pitchSpec columns (:659-667), which hinge on what as.numeric does with zero-length list
+    elements and cannot be settled without R."""
     sound, sr = _input(x, samplingRate)
     s = repair_pitch(sr, len(sound) / sr, **_pitch_args(locals()))
     d = pitch_decisions(len(sound), s)
@@ -905,7 +910,7 @@ def pitch_candidates(x, samplingRate=None, silence=0.04, windowLength=50, step=N
     :424-558), frames x nCands, NaN for NA and for a method not asked for. pitchMethods:
     a non-empty subset of ('autocor', 'cep', 'spec', 'dom'); the default is analyze()'s.
     With pitchMethods within ('autocor', 'dom') the shared keys equal analyze_frames()'
-    bit for bit. Not built: see pitch_candidates_numpy()."""
+    bit for bit. analyze() goes on from these candidates to the pitch contour."""
     sound, sr = _input(x, samplingRate)
     s = repair_pitch(sr, len(sound) / sr, **_pitch_args(locals()))
     return _run(sound, sr, s, pitch_decisions_native, _pitch_params, _pitch_table, "sg_pitch_candidates", device)
@@ -939,7 +944,9 @@ def pitch_matrices(table):
     Known difference: the reference's 1:0 quirks (idx[1:0], pitchSpec_array[1:0, ]) can
     leave an extra all-NA row in a frame's pitch_array; such rows carry no candidate
     (:589-591 blank them) but can add an all-NA row to the matrices. They are not
-    reproduced. The prior (:593-612) and everything after it is not built."""
+    reproduced; they are immaterial to what follows (the pathfinder drops all-NA rows and
+    findVoicedSegments counts non-NA entries). The prior (:593-612) and everything after it:
+    analyze_numpy()."""
     frames = len(table["ampl"])
     per = []
     for f in range(frames):
@@ -955,3 +962,641 @@ def pitch_matrices(table):
         for i, (c, a, src) in enumerate(p):
             cands[i, f], cert[i, f], source[i, f] = c, a, src
     return cands, cert, source, PITCH_SOURCES
+
+
+# ------------------------------------------- analyze(): the tail behind the candidates
+SMOOTH_VARS = ("pitch", "dom")
+TRACK_COLUMNS = ("pitch", "amplVoiced", "voiced", "harmonics")  # the device table's last four
+PATHFINDING = ("none", "fast", "slow")
+PATH_MAX_WIN = 64  # interpolWin and floor(smoothing_ww / 2) on the GPU (kPathMaxWin)
+SNAKE_MIN_STEP = 0.005  # the smallest snakeStep the GPU takes (its iterations are capped by range / snakeStep * 2)
+_SLOW = "pathfinding = 'slow' is simulated annealing through optim() on R's random stream: not built"
+
+
+def to_dB(x):
+    """to_dB(), R/utilities_math.R:37-39; NaN for a ratio <= 0, as log10 gives."""
+    x = np.asarray(x, float)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return 10 * np.log10(x / (1 - x))
+
+
+def dgamma(x, shape, rate, lconst=None):
+    """stats::dgamma(x, shape, rate) restated as exp((shape - 1) ln x - rate x + shape
+    ln(rate) - lgamma(shape)); 0 for x < 0. lconst: the last two terms, if already known."""
+    if lconst is None:
+        lconst = shape * math.log(rate) - math.lgamma(shape)
+    if math.isnan(x):
+        return math.nan
+    if x < 0:
+        return 0.0
+    if x == 0:
+        return 0.0 if shape > 1 else (rate if shape == 1 else math.inf)
+    return math.exp((shape - 1) * math.log(x) - rate * x + lconst)
+
+
+def prior_setup(priorMean, priorSD, pitchFloor, pitchCeiling):
+    """R/analyze.R:599-605: (shape, rate, shape ln(rate) - lgamma(shape), prior_normalizer)."""
+    shape = priorMean ** 2 / priorSD ** 2
+    rate = priorMean / priorSD ** 2
+    lconst = shape * math.log(rate) - math.lgamma(shape)
+    grid = _r_seq_len(hz_to_semitones(pitchFloor), hz_to_semitones(pitchCeiling), 100)
+    return shape, rate, lconst, max(dgamma(v, shape, rate, lconst) for v in grid)
+
+
+def prior_multiplier(hz, prior):
+    """pitchCert_multiplier (:606-610) of one candidate (Hz); prior: prior_setup()'s tuple."""
+    shape, rate, lconst, norm = prior
+    return dgamma(hz_to_semitones(hz), shape, rate, lconst) / norm
+
+
+def find_voiced_segments(count, minVoicedCands, noRequired, nToleratedNA):
+    """findVoicedSegments(), R/utilities_pitch_postprocessing.R:622-669, with its loop
+    bounds as written: count[f] non-NA candidates in frame f -> [(start, end)], 1-based,
+    inclusive. The last noRequired - 1 frames (and the very last one) cannot start a
+    segment; the end is i - 1, or the last voiced frame of the sound."""
+    v = np.asarray(count) >= minVoicedCands                                   # :628-630
+    n = len(v)
+    segs = []
+    i = 1
+    while i < n - noRequired + 1:                                             # :642
+        found = False
+        while i < n - noRequired + 1:                                         # :644-650
+            if v[i - 1:i - 1 + noRequired].all():
+                found = True
+                break
+            i += 1
+        if found:                                                             # :652
+            start, end = i, None
+            while i < n - nToleratedNA + 1:                                   # :653-660
+                if not v[i - 1:i + nToleratedNA].any():
+                    end = i - 1
+                    i -= 1
+                    break
+                i += 1
+            if end is None:                                                   # :661-665
+                segs.append((start, int(np.nonzero(v)[0][-1]) + 1))
+                break
+            segs.append((start, end))
+        i += 1
+    return segs
+
+
+def _median(v):
+    s = sorted(v)
+    m = len(s)
+    return s[(m - 1) // 2] if m % 2 else (s[m // 2 - 1] + s[m // 2]) / 2
+
+
+def _mean(v):
+    acc = 0.0
+    for x in v:
+        acc += x
+    return acc / len(v) if len(v) else math.nan
+
+
+def cost_jumps(cand1, cand2):
+    """costJumps(), :283-285."""
+    return 1 / (1 + 10 * math.exp(3 - 7 * abs(cand1 - cand2)))
+
+
+def find_grad(path):
+    """findGrad(), :534-562; lm()'s slopes over 2 or 3 points in closed form."""
+    path = [float(v) for v in path]
+    n = len(path)
+    if n < 2:                                                                 # interpol == 1
+        sl = sr = 0.0
+    elif n == 2:
+        sl = sr = path[1] - path[0]
+    else:
+        sl, sr = (path[2] - path[0]) / 2, (path[-1] - path[-3]) / 2
+    ext = [path[0] - 2 * sl, path[0] - 1 * sl] + path + [path[-1] + 1 * sr, path[-1] + 2 * sr]
+    return [ext[i - 2] - 4 * ext[i - 1] + 6 * ext[i] - 4 * ext[i + 1] + ext[i + 2] for i in range(2, n + 2)]
+
+
+def force_per_path(pitch, cands, cert, certWeight, _pairs=None):
+    """forcePerPath(), :495-521. cands / cert: per frame, the packed log2 candidates."""
+    grad = find_grad(pitch)
+    out = []
+    for i, p in enumerate(pitch):
+        external = 0.0
+        for c, a in zip(cands[i], cert[i]):
+            f = a * (1 / math.exp((c - p) ** 2))
+            external += f if c > p else -f                                    # cands > pitch[i]: equal pushes with -cert
+            if _pairs is not None and c != p:  # bit-equal: the point is still a copy of this candidate
+                _pairs.append((c, p))
+        out.append(certWeight * external + (1 - certWeight) * (-grad[i]))
+    return out
+
+
+def _trace_pick(scores, values, k, largest, out):
+    """The chosen score against the best score of a different pitch value."""
+    other = [s for s, v in zip(scores, values) if v != values[k] and not math.isnan(s)]
+    if other:
+        out.append((scores[k], max(other) if largest else min(other)))
+
+
+def _which(scores, largest):
+    best = -1
+    for k, s in enumerate(scores):
+        if math.isnan(s):
+            continue
+        if best < 0 or (s > scores[best] if largest else s < scores[best]):
+            best = k
+    return best
+
+
+def _div(a, d):
+    return a / d if d else (math.inf if a > 0 else math.nan)
+
+
+def pathfinding_fast(C, A, cog, certWeight, tr):
+    """pathfinding_fast(), :203-267, on the packed, sorted log2 candidates. point_current
+    is never updated in either loop: every frame's choice depends on the start alone."""
+    n = len(C)
+
+    def run(order, p):
+        f0 = order[0]
+        start = math.nan
+        if not math.isnan(p) and C[f0]:
+            c = [_div(a, abs(v - p)) for v, a in zip(C[f0], A[f0])]           # :211, :241
+            k = _which(c, True)
+            if k >= 0:
+                start = C[f0][k]
+                _trace_pick(c, C[f0], k, True, tr["start"])
+        path, total = {f0: start}, 0.0
+        for f in order[1:]:
+            if not C[f]:                                                      # length(cands) == 0: the frame is skipped
+                path[f] = math.nan
+                continue
+            costs = [certWeight * abs(v - cog[f]) + (1 - certWeight) * (0.0 if math.isnan(start) else cost_jumps(start, v))
+                     for v in C[f]]                                           # :220-229
+            k = _which(costs, False)
+            _trace_pick(costs, C[f], k, False, tr["choice"])
+            path[f] = C[f][k]
+            total += costs[k]
+        return [path[f] for f in range(n)], total
+
+    head = [v for v in cog[:min(5, n)] if not math.isnan(v)]
+    pF = _median(head) if head else math.nan                                  # :209, na.rm = TRUE
+    tail = cog[::-1][:min(5, n)]
+    pB = math.nan if any(math.isnan(v) for v in tail) else _median(tail)      # :240, no na.rm
+    fwd, costF = run(list(range(n)), pF)
+    bwd, costB = run(list(range(n - 1, -1, -1)), pB)
+    same = all(a == b or (math.isnan(a) and math.isnan(b)) for a, b in zip(fwd, bwd))
+    if not same:
+        tr["fb"].append((costF, costB))
+    tr["direction"] = "forward" if costF < costB else "backward"
+    return fwd if costF < costB else bwd
+
+
+def pathfinder_numpy(pitchCands, pitchCert, certWeight=0.5, pathfinding="fast", interpolWin=3, interpolTol=0.05,
+                     interpolCert=0.3, snakeStep=0.05, _trace=None):
+    """pathfinder(), R/utilities_pitch_postprocessing.R:28-132, for one voiced segment.
+    pitchCands / pitchCert: per frame, the list of its non-NA candidates (Hz) and their
+    certainties in pitch_matrices' order (the reference's NA-padded matrix columns; order()
+    puts NA last and all-NA rows are dropped, so nrow is the largest count of a frame).
+    Returns the pitch (Hz) per frame. The stated difference (see analyze_numpy): a frame
+    that still has no candidate after interpolation keeps NaN, every other frame keeps its
+    aligned choice, and the snake is not run on that segment. _trace (a dict) receives the
+    sides (a, b) of the discrete comparisons."""
+    tr = _trace if _trace is not None else {}
+    for k in ("band", "start", "choice", "fb", "maxiter", "delta", "force"):
+        tr.setdefault(k, [])
+    tr.update(interpolated=0, direction=None, iterations=0, rows=0)
+    if pathfinding == "slow":
+        raise NotImplementedError(_SLOW)
+    n = len(pitchCands)
+    C = [[math.log2(v) for v in f] for f in pitchCands]                       # :39
+    A = [[float(a) for a in f] for f in pitchCert]
+    cog = [_mean(f) for f in C]                                               # :43-49: `weights` is ignored
+    if _num(interpolWin) and interpolWin > 0:                                 # interpolate(), :149-184
+        W = int(interpolWin)
+        for f in range(n):
+            win = [v for v in cog[max(0, f - W):min(n - 1, f + W) + 1] if not math.isnan(v)]
+            if not win:
+                continue
+            med = _median(win)
+            lo, hi = (1 - interpolTol) * med, (1 + interpolTol) * med
+            for c in C[f]:
+                tr["band"] += [(c, lo), (c, hi)]
+            if sum(1 for c in C[f] if c > lo and c < hi) == 0:
+                C[f].append(med)
+                A[f].append(float(interpolCert))
+                cog[f] = _mean(C[f])
+                tr["interpolated"] += 1
+    for f in range(n):                                                        # :69-79 order(): stable
+        o = sorted(range(len(C[f])), key=lambda k: C[f][k])
+        C[f], A[f] = [C[f][k] for k in o], [A[f][k] for k in o]
+    tr["rows"] = max(len(f) for f in C)
+    if tr["rows"] <= 1:                                                       # :87-89
+        return [2.0 ** f[0] if f else math.nan for f in C]
+    if n >= 2 and pathfinding == "fast":                                      # :93-100
+        path = pathfinding_fast(C, A, cog, certWeight, tr)
+    else:                                                                     # :110-113
+        path = []
+        for f in range(n):
+            if not C[f]:
+                path.append(math.nan)
+                continue
+            d = [abs(v - cog[f]) for v in C[f]]
+            k = _which(d, False)
+            _trace_pick(d, C[f], k, False, tr["choice"])
+            path.append(C[f][k])
+    if _num(snakeStep) and snakeStep > 0 and all(len(f) for f in C):          # snake(), :419-475
+        flat = [v for f in C for v in f]
+        q = (max(flat) - min(flat)) / snakeStep * 2                           # :426-427
+        tr["maxiter"].append((q, float(np.round(q))))
+        maxIter = math.floor(q)
+        i, force_old = 1, 1e10
+        while i < maxIter:
+            force = force_per_path(path, C, A, certWeight, tr["force"])
+            force_new = _mean([abs(v) for v in force])
+            force_delta = (force_old - force_new) / force_old if force_old else math.nan
+            force_old = force_new
+            if not math.isnan(force_delta):
+                tr["delta"].append((force_delta, snakeStep))
+            if math.isnan(force_delta) or force_delta < snakeStep:
+                break
+            path = [p + snakeStep * v for p, v in zip(path, force)]
+            i += 1
+            tr["iterations"] += 1
+    return [2.0 ** p for p in path]
+
+
+def median_smoother(x, smoothing_ww, smoothingThres, _pairs=None):
+    """medianSmoother(), :584-600, for one column: the medians read the unsmoothed copy
+    and the test is abs(deviance - 1)."""
+    x = np.array(x, float)
+    temp = x.copy()
+    hw = int(math.floor(smoothing_ww / 2))
+    n = len(x)
+    for i in range(n):
+        win = temp[max(i - hw, 0):min(i + hw, n - 1) + 1]
+        win = win[~np.isnan(win)]
+        if not len(win) or math.isnan(x[i]):
+            continue
+        med = _median([float(v) for v in win])
+        with np.errstate(invalid="ignore", divide="ignore"):
+            deviance = float(12 * np.log2(np.float64(x[i]) / np.float64(med)))
+        if math.isnan(deviance):
+            continue
+        if _pairs is not None:
+            _pairs.append((abs(deviance - 1), smoothingThres))
+        if abs(deviance - 1) > smoothingThres:
+            x[i] = med
+    return x
+
+
+def repair_track(s, priorMean="default", priorSD=6, priorPlot=False, minVoicedCands="autom", shortestSyl=20,
+                 shortestPause=60, interpolWin=3, interpolTol=0.3, interpolCert=0.3, pathfinding="fast", certWeight=.5,
+                 snakeStep=0.05, snakePlot=False, smooth=1, smoothVars=SMOOTH_VARS, plot=False):
+    """The settings of analyze()'s tail (R/analyze.R:593-681) added to repair_pitch()'s
+    dict s. What is out of scope raises here, before anything runs."""
+    if plot or priorPlot or snakePlot:
+        raise NotImplementedError("analyze(plot = TRUE / priorPlot = TRUE / snakePlot = TRUE): plotting is out of scope")
+    if priorMean == "default":
+        priorMean = hz_to_semitones(300)
+    if isinstance(smoothVars, str):
+        smoothVars = (smoothVars,)
+    smoothVars = tuple(smoothVars or ())
+    for v in smoothVars:
+        if v not in SMOOTH_VARS:
+            raise NotImplementedError("smoothVars = %r: only 'pitch' and 'dom' are smoothed" % (v,))
+    if pathfinding not in PATHFINDING:
+        raise ValueError("pathfinding must be one of %s" % (PATHFINDING,))
+    prior = _num(priorMean) and _num(priorSD)                                 # :598
+    if prior and not (priorMean > 0 and priorSD > 0):
+        raise ValueError("analyze: priorMean and priorSD must be positive (dgamma gives NaN in the reference)")
+    m = s["pitchMethods"]
+    if not _num(minVoicedCands) or minVoicedCands < 1 or minVoicedCands > len(m):  # :615-624
+        minVoicedCands = 2 if ("dom" in m and len(m) > 1) else 1
+    for k, v in (("shortestSyl", shortestSyl), ("shortestPause", shortestPause), ("interpolTol", interpolTol),
+                 ("interpolCert", interpolCert), ("certWeight", certWeight)):
+        if not _num(v) or math.isnan(v):
+            raise ValueError("analyze: %s must be a number" % k)
+    if shortestPause < 0:
+        raise ValueError("analyze: shortestPause must not be negative")
+    if not (0 <= certWeight <= 1):
+        raise ValueError("analyze: certWeight must lie in [0, 1]")
+    if not _num(interpolWin):
+        interpolWin = 0                                                       # !is.numeric(interpolWin): no interpolation
+    if interpolWin != math.floor(interpolWin):
+        raise ValueError("analyze: interpolWin must be a whole number (f - interpolWin indexes frames)")
+    interpolWin = max(int(interpolWin), 0)
+    if not _num(snakeStep) or math.isnan(snakeStep) or snakeStep <= 0:
+        snakeStep = 0.0
+    if not _num(smooth) or math.isnan(smooth) or smooth <= 0:
+        smooth = 0.0
+    s = dict(s)
+    s.update(priorMean=float(priorMean) if prior else None, priorSD=float(priorSD) if prior else None,
+             minVoicedCands=int(math.ceil(minVoicedCands)), shortestSyl=shortestSyl, shortestPause=shortestPause,
+             noRequired=int(min(max(1, math.ceil(shortestSyl / s["step"])), 2 ** 30)),  # :633
+             nToleratedNA=int(min(math.floor(shortestPause / s["step"]), 2 ** 30)),    # :636
+             interpolWin=interpolWin, interpolTol=float(interpolTol), interpolCert=float(interpolCert),
+             pathfinding=pathfinding, certWeight=float(certWeight), snakeStep=float(snakeStep), smooth=float(smooth),
+             smoothVars=smoothVars)
+    return s
+
+
+def smoothing_hw(smooth, frames, length, samplingRate):
+    """floor(smoothing_ww / 2) with smoothing_ww = round(smooth * nrow / duration / 10)
+    (R/analyze.R:671-673; R's round goes half to even); 0 without smoothing."""
+    if not smooth > 0 or frames <= 0:
+        return 0
+    duration = length / samplingRate
+    return int(math.floor(float(np.round(smooth * (frames / duration) / 10)) / 2))
+
+
+def track_decisions(length, s):
+    """pitch_decisions() plus the integers of the tail for repair_track()'s dict s: what
+    sg_analyze_size makes bit-equal."""
+    d = pitch_decisions(length, s)
+    d.update(cols=NFIXED + 6 * s["nCands"] + len(TRACK_COLUMNS), minVoicedCands=s["minVoicedCands"],
+             noRequired=s["noRequired"], nToleratedNA=s["nToleratedNA"], interpolWin=s["interpolWin"],
+             hw=smoothing_hw(s["smooth"], d["frames"], length, s["samplingRate"]))
+    if s["pathfinding"] == "slow":
+        raise native.SoundgenError(-4, "analyze: pathfinding = 'slow' (simulated annealing on R's random stream) is not built")
+    if s["interpolWin"] > PATH_MAX_WIN or d["hw"] > PATH_MAX_WIN:
+        raise native.SoundgenError(-4, "analyze: interpolWin and half the smoothing window may be at most %d frames"
+                                   % PATH_MAX_WIN)
+    if 0 < s["snakeStep"] < SNAKE_MIN_STEP:
+        raise native.SoundgenError(-4, "analyze: snakeStep below %g is not supported" % SNAKE_MIN_STEP)
+    return d
+
+
+def _track(t, s, length, S=None, lab=None, probe=None):
+    """R/analyze.R:576-703 on a pitch_candidates() table t (changed in place and returned)."""
+    probe = {} if probe is None else probe
+    probe.update(segments=[], smooth=[], harm=[])
+    frames = len(t["ampl"])
+    cands, cert, _, _ = pitch_matrices(t)                                     # :578-591
+    per = [[(cands[r, f], cert[r, f]) for r in range(cands.shape[0]) if not math.isnan(cands[r, f])]
+           for f in range(frames)]
+    if s["priorMean"] is not None:                                            # :598-612
+        prior = prior_setup(s["priorMean"], s["priorSD"], s["pitchFloor"], s["pitchCeiling"])
+        per = [[(c, a * prior_multiplier(c, prior)) for c, a in f] for f in per]
+    segs = find_voiced_segments([len(f) for f in per], s["minVoicedCands"], s["noRequired"], s["nToleratedNA"])  # :625-632
+    pitch = np.full(frames, math.nan)
+    for a, b in segs:                                                         # :635-654
+        tr = {}
+        pitch[a - 1:b] = pathfinder_numpy([[c for c, _ in f] for f in per[a - 1:b]], [[w for _, w in f] for f in per[a - 1:b]],
+                                          s["certWeight"], s["pathfinding"], s["interpolWin"], s["interpolTol"],
+                                          s["interpolCert"], s["snakeStep"], tr)
+        tr.update(start_frame=a, end_frame=b)
+        probe["segments"].append(tr)
+    t["pitch"] = pitch
+    if s["smooth"] > 0:                                                       # :670-681
+        duration = length / s["samplingRate"]
+        ww = float(np.round(s["smooth"] * (frames / duration) / 10))
+        for k in s["smoothVars"]:
+            t[k] = median_smoother(t[k], ww, 4 / s["smooth"], probe["smooth"])
+    voiced = ~np.isnan(t["pitch"])                                            # :685-691
+    t["amplVoiced"] = np.where(voiced, t["ampl"], math.nan)
+    for k in ("quartile25", "quartile50", "quartile75"):
+        t[k] = np.where(voiced, t[k], math.nan)
+    t["voiced"] = voiced
+    harm = np.full(frames, math.nan)
+    if S is not None:                                                         # :694-699
+        for f in np.nonzero(voiced)[0]:
+            threshold = 1.25 * t["pitch"][f] / 1000
+            probe["harm"] += [(float(v), threshold) for v in lab]
+            harm[f] = np.sum(S[lab > threshold, f]) / np.sum(S[:, f])
+    t["HNR"] = to_dB(t["HNR"])                                                # :702-703
+    t["harmonics"] = to_dB(harm)
+    return t
+
+
+def _track_args(a):
+    return {k: a[k] for k in ("priorMean", "priorSD", "priorPlot", "minVoicedCands", "shortestSyl", "shortestPause",
+                              "interpolWin", "interpolTol", "interpolCert", "pathfinding", "certWeight", "snakeStep",
+                              "snakePlot", "smooth", "smoothVars", "plot")}
+
+
+def analyze_numpy(x, samplingRate=None, silence=0.04, windowLength=50, step=None, overlap=50, wn="gaussian", zp=0,
+                  cutFreq=6000, pitchMethods=PITCH_DEFAULT_METHODS, entropyThres=0.6, pitchFloor=75, pitchCeiling=3500,
+                  priorMean="default", priorSD=6, priorPlot=False, nCands=1, minVoicedCands="autom", domThres=0.1,
+                  domSmooth=220, autocorThres=0.7, autocorSmooth=None, cepThres=0.3, cepSmooth=None, cepZp=0,
+                  specThres=0.3, specPeak=0.35, specSinglePeakCert=0.4, specHNRslope=0.8, specSmooth=150, specMerge=1,
+                  shortestSyl=20, shortestPause=60, interpolWin=3, interpolTol=0.3, interpolCert=0.3, pathfinding="fast",
+                  certWeight=.5, snakeStep=0.05, snakePlot=False, smooth=1, smoothVars=SMOOTH_VARS, plot=False,
+                  _probe=None):
+    """analyze() (R/analyze.R:153-707) restated on the host: pitch_candidates_numpy(), then
+    statement by statement pitch_matrices (:578-591), the prior (:598-612; priorMean
+    'default' is HzToSemitones(300), None skips it), minVoicedCands 'autom' (:615-624),
+    findVoicedSegments, pathfinder per segment, medianSmoother (:670-681) and the final
+    columns (:685-703). Returns pitch_candidates_numpy()'s dict with pitch, voiced,
+    amplVoiced and harmonics added, HNR and harmonics in dB, dom (and pitch) smoothed and
+    the quartiles blanked for unvoiced frames.
+
+    Quirks kept (what the statements do):
+        * mean(x, weights = ...) ignores `weights`: the centre of gravity is a plain mean;
+        * point_current is never updated in either loop of pathfinding_fast;
+        * the backward start's median has no na.rm, and its which.max indexes the
+          na.omit-ed vector;
+        * a candidate exactly equal to the snake's point pushes with -cert (cands >
+          pitch[i] is false);
+        * the smoother tests abs(deviance - 1), not abs(deviance);
+        * analyze() passes interpolTol = 0.3, not the pathfinder's 0.05, and the
+          tolerance multiplies a log2 value;
+        * force_old starts at 1e10;
+        * maxIter = floor(ran / snakeStep * 2), and the loop runs while i < maxIter.
+    The one stated difference: a frame of a voiced segment can have no candidate when
+    interpolate() is not run (interpolWin = 0 or not numeric; with interpolWin >= 1 every
+    gap is filled, because a filled frame enters the next frame's median). In the reference 'fast' then skips the frame and assigns a misaligned, recycled
+    path, and 'none' stops in apply(). Here the frame keeps NaN pitch and every other
+    frame keeps its aligned choice; everything before that is restated as written
+    (including the backward pass from a NaN median: no start, the last frame NaN,
+    cost_pitchJump 0), and the snake is not run on that segment (in the reference its
+    first force_new is NA and it breaks at once).
+    Out of scope: pathfinding = 'slow' (simulated annealing through optim() on R's random
+    stream) and smoothVars outside ('pitch', 'dom') raise NotImplementedError, as do the
+    plots; the columns pitchAutocor / pitchCep / pitchSpec (:659-667, as.numeric of
+    zero-length list elements, which cannot be settled without R), formants, summary
+    and savePath are not built.
+
+    _probe (a dict) receives pitch_candidates_numpy()'s intermediates and `segments`
+    (per voiced segment the sides (a, b) of every discrete comparison: `band` the
+    interpolation band test per candidate, `start` the start which.max, `choice` each
+    frame's which.min, best against the best of a different pitch value, `fb` forward
+    against backward cost, `maxiter` ran / snakeStep * 2 against the nearest integer,
+    `delta` each force_delta against snakeStep, `force` each cands > pitch[i]), `smooth`
+    (the smoother's threshold tests) and `harm` (each label against the threshold)."""
+    sound, sr = _input(x, samplingRate)
+    a = locals()
+    if pathfinding == "slow":
+        raise NotImplementedError(_SLOW)
+    s = repair_track(repair_pitch(sr, len(sound) / sr, **_pitch_args(a)), **_track_args(a))
+    probe = {} if _probe is None else _probe
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")  # repair_pitch() has warned already
+        t = pitch_candidates_numpy(sound, sr, _probe=probe, **_pitch_args(a))
+    d = probe["d"]
+    return _track(t, s, len(sound), probe["S"], freq_labels(sr, d["wl"], d["bins"]), probe)
+
+
+def pitch_path_numpy(table, step, samplingRate, pitchMethods=PITCH_DEFAULT_METHODS, pitchFloor=75, pitchCeiling=3500,
+                     priorMean="default", priorSD=6, minVoicedCands="autom", shortestSyl=20, shortestPause=60,
+                     interpolWin=3, interpolTol=0.3, interpolCert=0.3, pathfinding="fast", certWeight=.5, snakeStep=0.05,
+                     smooth=1, smoothVars=SMOOTH_VARS, _probe=None):
+    """analyze_numpy()'s tail from a caller-given table shaped as pitch_candidates()'
+    (ampl, HNR, dom, the quartiles, domCand / domCert, the *Cand / *Cert groups present,
+    and `duration` in s): a copy with pitch, voiced, amplVoiced added, HNR in dB, dom
+    smoothed, the quartiles blanked; harmonics is all NaN (it needs the spectrum).
+    step (ms) and pitchMethods decide the segment settings as in analyze()."""
+    if pathfinding == "slow":
+        raise NotImplementedError(_SLOW)
+    t = {k: np.array(v, float) for k, v in table.items()}
+    s = _path_settings(t, step, samplingRate, locals())
+    return _track(t, s, _path_length(t, samplingRate), probe=_probe)
+
+
+def _path_length(t, samplingRate):
+    return int(round(float(t["duration"][0]) * samplingRate)) if len(t["ampl"]) else 0
+
+
+def _path_settings(t, step, samplingRate, a):
+    nC = t["autocorCand"].shape[1] if "autocorCand" in t and np.ndim(t["autocorCand"]) == 2 else 1
+    m = a["pitchMethods"]
+    base = dict(samplingRate=samplingRate, step=float(step), pitchMethods=(m,) if isinstance(m, str) else tuple(m),
+                pitchFloor=a["pitchFloor"], pitchCeiling=a["pitchCeiling"], nCands=nC)
+    kw = {k: a[k] for k in ("priorMean", "priorSD", "minVoicedCands", "shortestSyl", "shortestPause", "interpolWin",
+                            "interpolTol", "interpolCert", "pathfinding", "certWeight", "snakeStep", "smooth", "smoothVars")}
+    return repair_track(base, **kw)
+
+
+# ------------------------------------------------- analyze() on the GPU (sg_anl_path, sg_anl_harm)
+TRACK_SIZE_KEYS = ("minVoicedCands", "noRequired", "nToleratedNA", "hw", "interpolWin")
+
+
+def _track_params(s, pitch=True):
+    """sg_analyze_params_full of repair_track()'s dict; pitch=False (pitch_path) fills
+    only what the tail reads."""
+    from . import _abi
+    P = _abi.sg_analyze_params_full()
+    if pitch:
+        P.p = _pitch_params(s)
+    else:
+        m = s["pitchMethods"]
+        P.p.a.samplingRate, P.p.a.step, P.p.a.nCands = float(s["samplingRate"]), float(s["step"]), float(s["nCands"])
+        P.p.a.pitchFloor, P.p.a.pitchCeiling = float(s["pitchFloor"]), float(s["pitchCeiling"])
+        P.p.a.methods = sum(b for k, b in (("autocor", 1), ("dom", 2), ("cep", 4), ("spec", 8)) if k in m)
+    P.priorMean = math.nan if s["priorMean"] is None else s["priorMean"]
+    P.priorSD = math.nan if s["priorSD"] is None else s["priorSD"]
+    P.minVoicedCands = float(s["minVoicedCands"])
+    P.shortestSyl, P.shortestPause = float(s["shortestSyl"]), float(s["shortestPause"])
+    P.interpolWin, P.interpolTol, P.interpolCert = float(s["interpolWin"]), s["interpolTol"], s["interpolCert"]
+    P.certWeight, P.snakeStep, P.smooth = s["certWeight"], s["snakeStep"], s["smooth"]
+    P.pathfinding = PATHFINDING.index(s["pathfinding"])
+    P.smoothVars = sum(b for k, b in (("pitch", 1), ("dom", 2)) if k in s["smoothVars"])
+    return P
+
+
+def track_decisions_native(length, s):
+    """sg_analyze_size (host only): the library's track_decisions()."""
+    L = native.lib()
+    P = _track_params(s)
+    frames, cols = C.c_int32(), C.c_int32()
+    extra = (C.c_int32 * 8)()
+    rc = L.sg_analyze_size(int(length), C.byref(P), C.byref(frames), C.byref(cols), extra)
+    if rc < 0:
+        _raise(rc, L.sg_analyze_frames_size_error().decode())
+    d = pitch_decisions_native(length, s)
+    d.update(zip(TRACK_SIZE_KEYS, extra))
+    d.update(frames=frames.value, cols=cols.value)
+    return d
+
+
+def _track_frames_native(length, P):
+    L = native.lib()
+    fr, cl = C.c_int32(), C.c_int32()
+    rc = L.sg_analyze_size(int(length), C.byref(P), C.byref(fr), C.byref(cl), None)
+    if rc < 0:
+        _raise(rc, L.sg_analyze_frames_size_error().decode())
+    return fr.value
+
+
+def _track_table(m, nC, length, sr, step):
+    """frames x (15 + 6 nCands + 4) device rows -> the dict analyze_numpy() returns."""
+    t = _pitch_table(m, nC, length, sr, step)
+    c0 = NFIXED + 6 * nC
+    for i, k in enumerate(TRACK_COLUMNS):
+        t[k] = m[:, c0 + i].copy()
+    t["voiced"] = t["voiced"] == 1
+    return t
+
+
+def analyze(x, samplingRate=None, silence=0.04, windowLength=50, step=None, overlap=50, wn="gaussian", zp=0,
+            cutFreq=6000, pitchMethods=PITCH_DEFAULT_METHODS, entropyThres=0.6, pitchFloor=75, pitchCeiling=3500,
+            priorMean="default", priorSD=6, priorPlot=False, nCands=1, minVoicedCands="autom", domThres=0.1,
+            domSmooth=220, autocorThres=0.7, autocorSmooth=None, cepThres=0.3, cepSmooth=None, cepZp=0, specThres=0.3,
+            specPeak=0.35, specSinglePeakCert=0.4, specHNRslope=0.8, specSmooth=150, specMerge=1, shortestSyl=20,
+            shortestPause=60, interpolWin=3, interpolTol=0.3, interpolCert=0.3, pathfinding="fast", certWeight=.5,
+            snakeStep=0.05, snakePlot=False, smooth=1, smoothVars=SMOOTH_VARS, plot=False, device=0):
+    """analyze() (R/analyze.R:153-707) on the GPU (sg_analyze, fp64): pitch_candidates()'
+    dict plus pitch (the pathfinder's contour through the voiced segments, smoothed),
+    voiced, amplVoiced and harmonics, with HNR and harmonics in dB, dom smoothed and the
+    quartiles blanked for unvoiced frames. The candidates are made and consumed in one
+    launch sequence (sg_anl_path: one 64-lane workgroup per sound; sg_anl_harm). The
+    quirks kept, the one stated difference from the reference and what is out of scope
+    (pathfinding = 'slow', pitchAutocor / pitchCep / pitchSpec, formants, summary,
+    plots, savePath) are listed at analyze_numpy(), which this is compared against.
+    plot defaults to False; True raises."""
+    sound, sr = _input(x, samplingRate)
+    a = locals()
+    s = repair_track(repair_pitch(sr, len(sound) / sr, **_pitch_args(a)), **_track_args(a))
+    return _run(sound, sr, s, track_decisions_native, _track_params, _track_table, "sg_analyze", device)
+
+
+def analyze_batch(data, offsets, lengths, samplingRate, silence=0.04, windowLength=50, step=None, overlap=50,
+                  wn="gaussian", zp=0, cutFreq=6000, pitchMethods=PITCH_DEFAULT_METHODS, entropyThres=0.6, pitchFloor=75,
+                  pitchCeiling=3500, priorMean="default", priorSD=6, priorPlot=False, nCands=1, minVoicedCands="autom",
+                  domThres=0.1, domSmooth=220, autocorThres=0.7, autocorSmooth=None, cepThres=0.3, cepSmooth=None, cepZp=0,
+                  specThres=0.3, specPeak=0.35, specSinglePeakCert=0.4, specHNRslope=0.8, specSmooth=150, specMerge=1,
+                  shortestSyl=20, shortestPause=60, interpolWin=3, interpolTol=0.3, interpolCert=0.3, pathfinding="fast",
+                  certWeight=.5, snakeStep=0.05, snakePlot=False, smooth=1, smoothVars=SMOOTH_VARS, plot=False,
+                  to_host=False, device=0):
+    """analyze(call i, samplingRate, ...) for a batch of sounds already in HBM, laid out
+    and returned as pitch_candidates_batch() does (sg_analyze_batch, one launch sequence,
+    tables left in HBM). A row has 15 + 6 nCands + 4 columns: `columns` names those of
+    pitch_candidates_batch(), then pitch, amplVoiced, voiced (0 / 1) and harmonics. A
+    call's table equals analyze()'s bit for bit. to_host=True returns the list of per-call
+    dicts analyze() returns."""
+    a = locals()
+    s = repair_track(repair_pitch(samplingRate, None, **_pitch_args(a)), **_track_args(a))
+    return _run_batch(data, offsets, lengths, samplingRate, s, _track_frames_native, _track_params, _track_table,
+                      ("autocorCand", "autocorCert") + PITCH_KEYS, "sg_analyze", to_host, device, TRACK_COLUMNS)
+
+
+def pitch_path(table, step, samplingRate, pitchMethods=PITCH_DEFAULT_METHODS, pitchFloor=75, pitchCeiling=3500,
+               priorMean="default", priorSD=6, minVoicedCands="autom", shortestSyl=20, shortestPause=60, interpolWin=3,
+               interpolTol=0.3, interpolCert=0.3, pathfinding="fast", certWeight=.5, snakeStep=0.05, smooth=1,
+               smoothVars=SMOOTH_VARS, device=0):
+    """pitch_path_numpy() on the GPU (sg_pitch_path: sg_anl_path alone): analyze()'s tail
+    from a caller-given pitch_candidates()-shaped table (a host dict; a *Cand / *Cert
+    group that is absent counts as all NaN). Returns a copy with pitch, voiced, amplVoiced
+    added, HNR in dB, dom smoothed, the quartiles blanked; harmonics is all NaN."""
+    t = {k: np.array(v, float) for k, v in table.items()}
+    s = _path_settings(t, step, samplingRate, locals())
+    frames, nC = len(t["ampl"]), s["nCands"]
+    length = _path_length(t, samplingRate)
+    m = np.full((frames, NFIXED + 6 * nC), math.nan)
+    for i, k in enumerate(COLUMNS):
+        if k in t:
+            m[:, i] = t[k]
+    for i, k in enumerate(("autocorCand", "autocorCert") + PITCH_KEYS):
+        if k in t:
+            m[:, NFIXED + i * nC:NFIXED + (i + 1) * nC] = np.reshape(t[k], (frames, nC))
+    P = _track_params(s, pitch=False)
+    out = np.zeros(max(frames, 1) * (m.shape[1] + len(TRACK_COLUMNS)))
+    ctx = native.default_context(device)
+    dp = C.POINTER(C.c_double)
+    m = np.ascontiguousarray(m)
+    _check(native.lib().sg_pitch_path(ctx.ptr, m.ctypes.data_as(dp), frames, int(length), C.byref(P), out.ctypes.data_as(dp)),
+           ctx.ptr)
+    o = out[:frames * (m.shape[1] + 4)].reshape(frames, m.shape[1] + 4)
+    for i, k in enumerate(COLUMNS):
+        t[k] = o[:, i].copy()
+    for i, k in enumerate(TRACK_COLUMNS):
+        t[k] = o[:, m.shape[1] + i].copy()
+    t["voiced"] = t["voiced"] == 1
+    return t

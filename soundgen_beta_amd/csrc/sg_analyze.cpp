@@ -8,6 +8,9 @@
 // pitch_setup adds the decisions of getPitchCep (utilities_analyze.R:346-367: the
 // padded length, the effective cepSmooth, the band and its labels) and getPitchSpec
 // (:438: the width) for sg_pitch_candidates_size, which needs no device either.
+// track_setup adds those of analyze()'s tail (R/analyze.R:593-681): the prior's shape, rate
+// and normaliser, minVoicedCands 'autom', noRequired and nToleratedNA of findVoicedSegments,
+// the smoother's half width per sound, and the refusals, for sg_analyze_size.
 // The numpy restatement (soundgen_beta_amd/analyze.py) makes the same decisions in
 // the same operation order, so no product and sum may fuse here.
 #pragma clang fp contract(off)
@@ -250,6 +253,90 @@ PitchSetup pitch_setup(const sg_pitch_params& p) {
   return S;
 }
 
+PathPars track_path_pars(const sg_analyze_params_full& p, double* smooth) {
+  PathPars P;
+  std::memset(&P, 0, sizeof P);
+  const sg_analyze_params& a = p.p.a;
+  if (!(a.nCands >= 1) || a.nCands != std::floor(a.nCands)) throw SgError(SG_E_ARG, "analyze: nCands must be a whole number >= 1");
+  if (a.nCands > kAnlMaxCands) throw SgError(SG_E_UNSUPPORTED, "analyze: at most " + std::to_string(kAnlMaxCands) + " candidates are kept");
+  if (a.methods < 1 || (a.methods & ~15)) throw SgError(SG_E_ARG, "analyze: pitchMethods must be a non-empty subset of 'autocor', 'dom', 'cep', 'spec'");
+  if (!(a.pitchFloor > 0) || !(a.pitchFloor <= a.pitchCeiling)) throw SgError(SG_E_ARG, "analyze: pitchFloor must be positive and at most pitchCeiling");
+  P.nCands = (int)a.nCands;
+  P.cols = kAnlFixed + 6 * P.nCands + kPathCols;
+  if (p.pathfinding == 2)
+    throw SgError(SG_E_UNSUPPORTED, "analyze: pathfinding = 'slow' (simulated annealing on R's random stream) is not built");
+  if (p.pathfinding < 0 || p.pathfinding > 2) throw SgError(SG_E_ARG, "analyze: pathfinding must be 0 'none', 1 'fast' or 2 'slow'");
+  P.pathfinding = p.pathfinding;
+  if (p.smoothVars & ~3) throw SgError(SG_E_ARG, "analyze: smoothVars must be a subset of 'pitch', 'dom'");
+  // :598-605 the prior, when priorMean and priorSD are both numbers
+  if (!std::isnan(p.priorMean) && !std::isnan(p.priorSD)) {
+    if (!(p.priorMean > 0) || !(p.priorSD > 0) || std::isinf(p.priorMean) || std::isinf(p.priorSD))
+      throw SgError(SG_E_ARG, "analyze: priorMean and priorSD must be positive (dgamma gives NaN in the reference)");
+    P.do_prior = 1;
+    P.shape = (p.priorMean * p.priorMean) / (p.priorSD * p.priorSD);
+    P.rate = p.priorMean / (p.priorSD * p.priorSD);
+    P.lconst = P.shape * std::log(P.rate) - std::lgamma(P.shape);
+    const double from = std::log2(a.pitchFloor / 16.3516) * 12, to = std::log2(a.pitchCeiling / 16.3516) * 12;
+    double mx = -INFINITY;
+    for (int i = 0; i < 100; ++i) mx = std::max(mx, path_dgamma(seq_len_at(from, to, 100, i), P.shape, P.rate, P.lconst));
+    if (!(mx > 0) || std::isinf(mx)) throw SgError(SG_E_ARG, "analyze: the prior vanishes over the whole pitch range");
+    P.prior_norm = mx;
+  }
+  // :615-624 minVoicedCands 'autom'
+  int nm = 0;
+  for (int b = 0; b < 4; ++b) nm += (a.methods >> b) & 1;
+  double mv = p.minVoicedCands;
+  if (std::isnan(mv) || mv < 1 || mv > nm) mv = ((a.methods & 2) && nm > 1) ? 2 : 1;
+  P.minVoiced = (int)std::ceil(mv);
+  // findVoicedSegments :633-636
+  const double step = std::isnan(a.step) ? a.windowLength * (1 - a.overlap / 100) : a.step;
+  if (!(step > 0)) throw SgError(SG_E_ARG, "analyze: step must be positive");
+  if (std::isnan(p.shortestSyl) || std::isnan(p.shortestPause) || p.shortestPause < 0)
+    throw SgError(SG_E_ARG, "analyze: shortestSyl and shortestPause must be numbers, shortestPause not negative");
+  P.noRequired = (int)std::min(std::max(1.0, std::ceil(p.shortestSyl / step)), 1073741824.0);
+  P.nTolerated = (int)std::min(std::floor(p.shortestPause / step), 1073741824.0);
+  if (std::isnan(p.interpolTol) || std::isnan(p.interpolCert)) throw SgError(SG_E_ARG, "analyze: interpolTol and interpolCert must be numbers");
+  if (std::isnan(p.interpolWin) || p.interpolWin != std::floor(p.interpolWin))
+    throw SgError(SG_E_ARG, "analyze: interpolWin must be a whole number (f - interpolWin indexes frames)");
+  if (p.interpolWin > kPathMaxWin)
+    throw SgError(SG_E_UNSUPPORTED, "analyze: interpolWin and half the smoothing window may be at most " + std::to_string(kPathMaxWin) + " frames");
+  P.interpolWin = p.interpolWin > 0 ? (int)p.interpolWin : 0;
+  P.interpolTol = p.interpolTol;
+  P.interpolCert = p.interpolCert;
+  if (!(p.certWeight >= 0 && p.certWeight <= 1)) throw SgError(SG_E_ARG, "analyze: certWeight must lie in [0, 1]");
+  P.certWeight = p.certWeight;
+  P.snakeStep = p.snakeStep > 0 ? p.snakeStep : 0.0;
+  if (P.snakeStep > 0 && P.snakeStep < 0.005) throw SgError(SG_E_UNSUPPORTED, "analyze: snakeStep below 0.005 is not supported");
+  *smooth = p.smooth > 0 ? p.smooth : 0.0;
+  if (std::isinf(*smooth)) throw SgError(SG_E_ARG, "analyze: smooth must be finite");
+  P.smooth_pitch = *smooth > 0 && (p.smoothVars & 1);
+  P.smooth_dom = *smooth > 0 && (p.smoothVars & 2);
+  P.smoothThres = *smooth > 0 ? 4 / *smooth : 0.0;
+  return P;
+}
+
+TrackSetup track_setup(const sg_analyze_params_full& p) {
+  TrackSetup S;
+  static_cast<PitchSetup&>(S) = pitch_setup(p.p);
+  S.path = track_path_pars(p, &S.smooth);
+  S.cols = S.path.cols;
+  const int bins = S.spg.bins;
+  const double sr = S.spg.sr, top = (sr / 2) - (sr / S.spg.wl);
+  S.lab.resize(bins);
+  for (int k = 0; k < bins; ++k) S.lab[k] = rt15(seq_len_at(0.0, top, bins, k) / 1000);  // as anl_setup labels the bins
+  return S;
+}
+
+int track_hw(double smooth, double samplingRate, int64_t len, int frames) {
+  if (!(smooth > 0) || frames <= 0 || len <= 0) return 0;
+  const double duration = (double)len / samplingRate;
+  const double ww = std::nearbyint(smooth * ((double)frames / duration) / 10);  // R's round(): half to even
+  const double hw = std::floor(ww / 2);
+  if (hw > kPathMaxWin)
+    throw SgError(SG_E_UNSUPPORTED, "analyze: interpolWin and half the smoothing window may be at most " + std::to_string(kPathMaxWin) + " frames");
+  return (int)hw;
+}
+
 int anl_frames(const AnlSetup& S, int64_t len) { return len <= S.spg.wl ? 0 : spg_frames(S.spg, len); }
 
 int64_t anl_ampl_start(const AnlSetup& S, int64_t len, int frames, int f) {
@@ -386,6 +473,39 @@ extern "C" int sg_pitch_candidates_cep_labels(const sg_pitch_params* p, double* 
     const sg::PitchSetup& S = cached_pitch_setup(*p);
     if (n > S.ncep) throw sg::SgError(SG_E_ARG, "sg_pitch_candidates_cep_labels: n exceeds the band");
     for (int i = 0; i < n; ++i) labels[i] = S.cepf[i];
+  });
+}
+
+namespace {
+thread_local sg_analyze_params_full g_last_tp;
+thread_local sg::TrackSetup g_last_TS;
+thread_local bool g_have_t = false;
+
+const sg::TrackSetup& cached_track_setup(const sg_analyze_params_full& p) {
+  if (!g_have_t || std::memcmp(&p, &g_last_tp, sizeof p) != 0) {
+    g_have_t = false;
+    g_last_TS = sg::track_setup(p);
+    g_last_tp = p;
+    g_have_t = true;
+  }
+  return g_last_TS;
+}
+}  // namespace
+
+extern "C" int sg_analyze_size(int64_t len, const sg_analyze_params_full* p, int32_t* frames, int32_t* cols, int32_t* extra) {
+  if (!p || !frames || !cols) {
+    g_anl_err = "sg_analyze_size: bad arguments";
+    return SG_E_ARG;
+  }
+  return size_guard([&]() {
+    const sg::TrackSetup& S = cached_track_setup(*p);
+    *frames = sg::anl_frames(S, len);
+    *cols = S.cols;
+    const int hw = sg::track_hw(S.smooth, S.spg.sr, len, *frames);
+    if (extra) {
+      const int32_t e[8] = {S.path.minVoiced, S.path.noRequired, S.path.nTolerated, hw, S.path.interpolWin};
+      std::memcpy(extra, e, sizeof e);
+    }
   });
 }
 

@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "sg_path.h"
 #include "sg_spectrogram.h"
 #include "soundgen_hip.h"
 
@@ -60,10 +61,29 @@ struct PitchSetup : AnlSetup {
 };
 PitchSetup pitch_setup(const sg_pitch_params& p);
 
-// pitch: nullptr for analyze_frames (S is then a plain AnlSetup), else S itself
+// analyze(): pitch_candidates plus the tail behind the candidates (R/analyze.R:576-707,
+// R/utilities_pitch_postprocessing.R; sg_path.h). A row then has kAnlFixed + 6 nCands +
+// kPathCols columns: the candidates', then pitch, amplVoiced, voiced, harmonics.
+constexpr int kTrackStages = 8;  // sg_debug_track_kernel_ms: the six of pitch_candidates, the path, the harmonics
+struct TrackSetup : PitchSetup {
+  PathPars path;            // the prior's shape, rate and normaliser, the resolved minVoicedCands, noRequired, ...
+  double smooth = 0;        // <= 0: no medianSmoother
+  std::vector<double> lab;  // the frequency label of every bin (kHz, after the round trip): `harmonics` reads it
+};
+// what the tail decides from p alone (of p.p only a.samplingRate, a.step, a.windowLength, a.overlap, a.nCands,
+// a.pitchFloor, a.pitchCeiling and a.methods are read), validated
+PathPars track_path_pars(const sg_analyze_params_full& p, double* smooth);
+TrackSetup track_setup(const sg_analyze_params_full& p);
+// floor(smoothing_ww / 2) for a sound of len samples and `frames` frames (:671-673); SG_E_UNSUPPORTED above kPathMaxWin
+int track_hw(double smooth, double samplingRate, int64_t len, int frames);
+
+// pitch: nullptr for analyze_frames (S is then a plain AnlSetup), else S itself; track:
+// nullptr for analyze_frames and pitch_candidates, else S itself (then pitch is S too)
 template <typename T>
 void analyze_device(const AnlSetup& S, const T* d_x, const int64_t* offsets, const int64_t* lengths, int64_t n_calls,
                     double* d_out, const int64_t* out_off, int32_t* frames_out, hipStream_t s, double* kernel_ms,
-                    const PitchSetup* pitch = nullptr);
+                    const PitchSetup* pitch = nullptr, const TrackSetup* track = nullptr);
+// the path stage alone on n rows of P.cols doubles already on the device (sg_pitch_path)
+void path_device(const PathPars& P, int frames, int hw, double* d_rows, hipStream_t s, double* kernel_ms);
 
 }  // namespace sg

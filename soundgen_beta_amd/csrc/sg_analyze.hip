@@ -23,6 +23,13 @@
 //                 a second transform through fft64, |C_k| / max, the peaks, the 1.8 rule
 //   sg_anl_bana   getPitchSpec (:424-558): the five lowest spectral peaks, then
 //                 sg::bana_candidates (sg_bana.h) in one thread
+// analyze (sg_analyze*) runs all of that on rows that end in pitch, amplVoiced, voiced and
+// harmonics, then the tail (R/analyze.R:576-707, R/utilities_pitch_postprocessing.R):
+//   sg_anl_path   one 64-lane workgroup per sound (sg::path_sound, sg_path.h): the prior,
+//                 findVoicedSegments, pathfinder per segment, medianSmoother, voiced /
+//                 amplVoiced, the blanked quartiles, HNR in dB
+//   sg_anl_harm   one workgroup per frame with a pitch: the share of |X| above 1.25 *
+//                 pitch, in dB
 // Cumulative sums run in index order: a thread sums a contiguous run, one thread
 // folds the 256 run sums in order, and the runs are rescanned from their offsets,
 // so a frame's result does not depend on the launch it is in.
@@ -38,6 +45,7 @@
 #include "sg_dev64.h"
 #include "sg_fft64_dev.h"
 #include "sg_launch.h"
+#include "sg_path.h"
 #include "sg_rmath.h"
 
 namespace {
@@ -65,6 +73,7 @@ struct AnlFrame {
 // the launch's constants
 struct AnlK {
   int wl, B, cols, nCands;
+  int fill;  // the columns sg_anl_spec blanks: cols, less the four that sg_anl_path writes for every frame
   int rowLow, rowHigh;  // 0-based, inclusive
   int cut0, ncut, pf_idx, domW, acW, lag0, nlag;
   int do_dom, do_autocor;
@@ -188,7 +197,7 @@ __global__ __launch_bounds__(kT) void sg_anl_spec(const AnlFrame* __restrict__ f
     row[sg::kCondSilence] = c_sil ? 1.0 : 0.0;
     row[sg::kCondEntropy] = c_ent ? 1.0 : 0.0;
     for (int c = sg::kHNR; c <= sg::kDomCert; ++c) row[c] = NAN;
-    for (int c = sg::kAnlFixed; c < K.cols; ++c) row[c] = NAN;
+    for (int c = sg::kAnlFixed; c < K.fill; ++c) row[c] = NAN;
   }
   if (!c_sil) return;  // workgroup-uniform
   // which.max(frame): the first maximum
@@ -560,8 +569,64 @@ __global__ __launch_bounds__(kT) void sg_anl_bana(const AnlFrame* __restrict__ f
   }
 }
 
+static_assert(sg::kPathAmpl == sg::kAmpl && sg::kPathHNR == sg::kHNR && sg::kPathDom == sg::kDom && sg::kPathQ25 == sg::kQ25 &&
+                  sg::kPathQ75 == sg::kQ75 && sg::kPathDomCand == sg::kDomCand && sg::kPathDomCert == sg::kDomCert &&
+                  sg::kPathFixed == sg::kAnlFixed,
+              "sg_path.h names the columns of sg::AnlCol");
+
+constexpr int kPathT = 64;  // one wave per sound
+
+struct PathSound {
+  int64_t row0;  // first double of its table in the output buffer
+  int64_t scr0;  // first double of its frames' scratch
+  int32_t nf, hw;
+};
+
+struct WgSync {
+  __device__ void operator()() const { __syncthreads(); }
+};
+
+// analyze()'s tail for one sound per workgroup (sg::path_sound, sg_path.h): lanes stride
+// over frames; one lane scans for voiced segments and interpolates; the per-frame sort,
+// the choices, the snake's iterations and the smoother are lane-parallel. The candidates
+// live in global scratch (a sound has no frame bound), sized by the launch's frame total.
+__global__ __launch_bounds__(kPathT) void sg_anl_path(const PathSound* __restrict__ snds, sg::PathPars P,
+                                                      double* __restrict__ out, double* __restrict__ scr) {
+  __shared__ double red[kPathT];
+  __shared__ int64_t sh[3];
+  const PathSound S = snds[blockIdx.x];
+  if (S.nf <= 0) return;  // workgroup-uniform
+  sg::path_sound(P, S.nf, S.hw, out + S.row0, scr + S.scr0, (int)threadIdx.x, kPathT, red, sh, WgSync());
+}
+
+// `harmonics` (R/analyze.R:694-703) for one frame per workgroup: the share of the frame's
+// |X| above 1.25 * pitch (labels in kHz, strictly above), in dB; sg_anl_path has left NaN
+// where pitch is NaN
+__global__ __launch_bounds__(kT) void sg_anl_harm(const AnlFrame* __restrict__ frames, const AnlSound* __restrict__ snds,
+                                                  const double* __restrict__ Z, const double* __restrict__ lab, int B,
+                                                  int cols, double* __restrict__ out) {
+  __shared__ double red[kT];
+  const AnlFrame F = frames[blockIdx.x];
+  const AnlSound S = snds[F.snd];
+  double* row = out + S.row0 + (int64_t)F.f * cols;
+  const double pitch = row[cols - sg::kPathCols + sg::kPathPitch];
+  if (pitch != pitch) return;  // workgroup-uniform
+  const double threshold = 1.25 * pitch / 1000;
+  const double* z = Z + S.z0 + (int64_t)F.f * B;
+  double above = 0, all = 0;
+  for (int b = threadIdx.x; b < B; b += kT) {
+    const double v = z[b];
+    all += v;
+    if (lab[b] > threshold) above += v;
+  }
+  above = block_reduce<kT>(above, 0, red);
+  all = block_reduce<kT>(all, 0, red);
+  if (threadIdx.x == 0) row[cols - sg::kPathCols + sg::kPathHarmonics] = sg::path_to_dB(above / all);
+}
+
 double g_anl_ms[sg::kAnlStages];  // of the last profiled launch sequence
 double g_pitch_ms[sg::kPitchStages];
+double g_track_ms[sg::kTrackStages];
 
 }  // namespace
 
@@ -570,12 +635,14 @@ namespace sg {
 template <typename T>
 void analyze_device(const AnlSetup& A, const T* d_x, const int64_t* offsets, const int64_t* lengths, int64_t n_calls,
                     double* d_out, const int64_t* out_off, int32_t* frames_out, hipStream_t s, double* kernel_ms,
-                    const PitchSetup* pitch) {
+                    const PitchSetup* pitch, const TrackSetup* track) {
   const SpgSetup& P = A.spg;
   const int B = P.bins, wl = P.wl;
   std::vector<AnlSound> snds(n_calls);
   std::vector<AnlFrame> fr;
   std::vector<int64_t> lens(n_calls), zoff(n_calls);
+  std::vector<PathSound> ps(track ? n_calls : 0);
+  const int pstride = track ? path_stride(track->path.nCands) : 0;
   int64_t cells = 0;
   for (int64_t c = 0; c < n_calls; ++c) {
     const int nf = anl_frames(A, lengths[c]);
@@ -583,6 +650,8 @@ void analyze_device(const AnlSetup& A, const T* d_x, const int64_t* offsets, con
     zoff[c] = cells;
     snds[c] = AnlSound{offsets[c], lens[c], cells, out_off[c], nf, 0};
     frames_out[c] = nf;
+    if (track)  // the smoothing window is refused before anything is launched
+      ps[c] = PathSound{out_off[c], (int64_t)fr.size() * pstride, nf, track_hw(track->smooth, P.sr, lengths[c], nf)};
     if ((int64_t)fr.size() + nf > 2147483647LL) throw SgError(SG_E_UNSUPPORTED, "analyze: the frames of one launch exceed 2^31");
     for (int f = 0; f < nf; ++f) {
       const int64_t o = spg_frame_start(P, lengths[c], f), a = anl_ampl_start(A, lengths[c], nf, f);
@@ -592,7 +661,7 @@ void analyze_device(const AnlSetup& A, const T* d_x, const int64_t* offsets, con
     }
     cells += (int64_t)nf * B;
   }
-  StageClock clk(s, kernel_ms, pitch ? kPitchStages : kAnlStages);
+  StageClock clk(s, kernel_ms, track ? kTrackStages : pitch ? kPitchStages : kAnlStages);
   clk.zero();
   const int64_t F = (int64_t)fr.size();
   if (F == 0) return;
@@ -624,6 +693,7 @@ void analyze_device(const AnlSetup& A, const T* d_x, const int64_t* offsets, con
   K.wl = wl;
   K.B = B;
   K.cols = A.cols;
+  K.fill = track ? A.cols - kPathCols : A.cols;
   K.nCands = A.nCands;
   K.rowLow = A.rowLow - 1;
   K.rowHigh = A.rowHigh - 1;
@@ -697,9 +767,41 @@ void analyze_device(const AnlSetup& A, const T* d_x, const int64_t* offsets, con
       HIPCHK(hipGetLastError());
     }
     clk.stamp();
+    if (track) {  // 6: voiced segments, pathfinder, smoother, final columns
+      if (track->path.cols != A.cols || A.cols != kAnlFixed + 6 * A.nCands + kPathCols || (int)track->lab.size() != B)
+        throw SgError(SG_E_DEVICE, "analyze: the tail's setup leaves the row");
+      const PathSound* d_ps = upload(db, ps, s);
+      double* d_scr = db.get<double>((size_t)F * pstride);
+      const double* d_lab = upload(db, track->lab, s);
+      hipLaunchKernelGGL(sg_anl_path, dim3((unsigned)n_calls), dim3(kPathT), 0, s, d_ps, track->path, d_out, d_scr);
+      HIPCHK(hipGetLastError());
+      clk.stamp();  // 7: harmonics
+      hipLaunchKernelGGL(sg_anl_harm, gF, bT, 0, s, d_fr, d_snd, d_Z, d_lab, B, A.cols, d_out);
+      HIPCHK(hipGetLastError());
+      clk.stamp();
+    }
   }
   HIPCHK(hipStreamSynchronize(s));
   clk.finish();
+}
+
+void path_device(const PathPars& P, int frames, int hw, double* d_rows, hipStream_t s, double* kernel_ms) {
+  double ms = 0;
+  StageClock clk(s, kernel_ms ? &ms : nullptr, 1);
+  for (int k = 0; kernel_ms && k < kTrackStages; ++k) kernel_ms[k] = 0;
+  if (frames <= 0) return;
+  if (P.cols != kAnlFixed + 6 * P.nCands + kPathCols || P.nCands < 1 || P.nCands > kAnlMaxCands || hw < 0)
+    throw SgError(SG_E_DEVICE, "analyze: the tail's setup leaves the row");
+  DevBuf db;
+  const PathSound* d_ps = upload(db, std::vector<PathSound>(1, PathSound{0, 0, frames, hw}), s);
+  double* d_scr = db.get<double>((size_t)frames * path_stride(P.nCands));
+  clk.stamp();
+  hipLaunchKernelGGL(sg_anl_path, dim3(1), dim3(kPathT), 0, s, d_ps, P, d_rows, d_scr);
+  HIPCHK(hipGetLastError());
+  clk.stamp();
+  HIPCHK(hipStreamSynchronize(s));
+  clk.finish();
+  if (kernel_ms) kernel_ms[kTrackStages - 2] = ms;
 }
 
 }  // namespace sg
@@ -712,24 +814,24 @@ using sg::guarded;
 // g_anl_ms) and of pitch_candidates (pitch == &S, ms = g_pitch_ms), behind their
 // argument checks
 int frames_single(sg_ctx* ctx, const sg::AnlSetup& S, const sg::PitchSetup* pitch, double* ms, const double* wave,
-                  int64_t len, double* out) {
+                  int64_t len, double* out, const sg::TrackSetup* track = nullptr) {
   HIPCHK(hipSetDevice(ctx->device));
   const int64_t cells = (int64_t)sg::anl_frames(S, len) * S.cols;
   sg::single_sound(ctx, wave, len, cells, out, [&](const double* d, double* d_o) {
     const int64_t off = 0;
     int32_t f = 0;
-    sg::analyze_device<double>(S, d, &off, &len, 1, d_o, &off, &f, ctx->stream, ctx->profiling ? ms : nullptr, pitch);
+    sg::analyze_device<double>(S, d, &off, &len, 1, d_o, &off, &f, ctx->stream, ctx->profiling ? ms : nullptr, pitch, track);
   });
   return SG_OK;
 }
 
 int frames_batch(sg_ctx* ctx, const sg::AnlSetup& S, const sg::PitchSetup* pitch, double* ms, const float* d_wave,
                  const int64_t* offsets, const int64_t* lengths, int64_t n_calls, double* d_out, const int64_t* out_off,
-                 int32_t* frames_out) {
+                 int32_t* frames_out, const sg::TrackSetup* track = nullptr) {
   if (n_calls == 0) return SG_OK;
   HIPCHK(hipSetDevice(ctx->device));
   sg::analyze_device<float>(S, d_wave, offsets, lengths, n_calls, d_out, out_off, frames_out, ctx->stream,
-                            ctx->profiling ? ms : nullptr, pitch);
+                            ctx->profiling ? ms : nullptr, pitch, track);
   return SG_OK;
 }
 
@@ -781,6 +883,58 @@ int sg_pitch_candidates_batch(sg_ctx* ctx, const float* d_wave, const int64_t* o
     const sg::PitchSetup S = sg::pitch_setup(*p);
     return frames_batch(ctx, S, &S, g_pitch_ms, d_wave, offsets, lengths, n_calls, d_out, out_off, frames_out);
   });
+}
+
+int sg_analyze(sg_ctx* ctx, const double* wave, int64_t len, const sg_analyze_params_full* p, double* out) {
+  return guarded(ctx, [&]() {
+    if (!ctx || !p || !wave || !out) throw sg::SgError(SG_E_ARG, "sg_analyze: bad arguments");
+    const sg::TrackSetup S = sg::track_setup(*p);
+    if (len <= S.spg.wl)
+      throw sg::SgError(SG_E_ARG, "sg_analyze: the sound is not longer than the window (the reference's amplitude window "
+                                  "sound[a:(a + wl)] leaves it)");
+    return frames_single(ctx, S, &S, g_track_ms, wave, len, out, &S);
+  });
+}
+
+int sg_analyze_batch(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, const int64_t* lengths, int64_t n_calls,
+                     const sg_analyze_params_full* p, double* d_out, const int64_t* out_off, int32_t* frames_out) {
+  return guarded(ctx, [&]() {
+    if (!ctx || !p || n_calls < 0 || n_calls > 2147483647LL ||
+        (n_calls > 0 && (!d_wave || !offsets || !lengths || !d_out || !out_off || !frames_out)))
+      throw sg::SgError(SG_E_ARG, "sg_analyze_batch: bad arguments");
+    const sg::TrackSetup S = sg::track_setup(*p);
+    return frames_batch(ctx, S, &S, g_track_ms, d_wave, offsets, lengths, n_calls, d_out, out_off, frames_out, &S);
+  });
+}
+
+int sg_pitch_path(sg_ctx* ctx, const double* table, int32_t frames, int64_t len, const sg_analyze_params_full* p,
+                  double* out) {
+  return guarded(ctx, [&]() {
+    if (!ctx || !p || frames < 0 || len < 0 || (frames > 0 && (!table || !out)))
+      throw sg::SgError(SG_E_ARG, "sg_pitch_path: bad arguments");
+    double smooth = 0;
+    const sg::PathPars P = sg::track_path_pars(*p, &smooth);
+    const int hw = sg::track_hw(smooth, p->p.a.samplingRate, len, frames);
+    if (frames == 0) return (int)SG_OK;
+    if (!(p->p.a.samplingRate > 0)) throw sg::SgError(SG_E_ARG, "sg_pitch_path: samplingRate must be positive");
+    HIPCHK(hipSetDevice(ctx->device));
+    const int in_cols = P.cols - sg::kPathCols;
+    for (int32_t f = 0; f < frames; ++f) {  // the caller's rows, widened, staged in `out`
+      for (int c = 0; c < in_cols; ++c) out[(int64_t)f * P.cols + c] = table[(int64_t)f * in_cols + c];
+      for (int c = in_cols; c < P.cols; ++c) out[(int64_t)f * P.cols + c] = NAN;
+    }
+    sg::DevBuf db;
+    double* d_rows = sg::upload_sound(db, out, (int64_t)frames * P.cols, ctx->stream);
+    sg::path_device(P, frames, hw, d_rows, ctx->stream, ctx->profiling ? g_track_ms : nullptr);
+    HIPCHK(hipMemcpy(out, d_rows, (size_t)frames * P.cols * sizeof(double), hipMemcpyDeviceToHost));
+    return (int)SG_OK;
+  });
+}
+
+int sg_debug_track_kernel_ms(double* out) {
+  if (!out) return SG_E_ARG;
+  for (int k = 0; k < sg::kTrackStages; ++k) out[k] = g_track_ms[k];
+  return SG_OK;
 }
 
 int sg_debug_pitch_kernel_ms(double* out) {

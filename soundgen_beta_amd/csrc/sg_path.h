@@ -1,0 +1,446 @@
+// sg_path.h — analyze()'s tail once every frame has its pitch candidates
+// (R/analyze.R:576-707, R/utilities_pitch_postprocessing.R): the prior, findVoicedSegments,
+// pathfinder (interpolate, pathfinding 'none' / 'fast', costJumps, snake, forcePerPath,
+// findGrad), medianSmoother and the final columns. The scalar routines are plain
+// functions; path_sound() drives them for one sound with `nl` cooperating lanes: the 64
+// lanes of sg_anl_path's workgroup on the device, one lane (and a sync that does nothing)
+// on the host (tests/cpp/path_pins.cpp). No HIP header is needed on the host side, no
+// dynamic memory anywhere.
+//
+// A frame's candidates live in global scratch, path_stride() doubles per frame: W = 2 +
+// 3 nCands log2 pitches (dom, autocor[.], cep[.], spec[.] as pitch_matrices packs them,
+// then room for the one interpolate() adds), W certainties, and kPathSlots per-frame
+// values. What R keeps as matrices with NA-padded columns is here a packed list per
+// frame: order() puts NA last and the all-NA rows are dropped (:67-83), so nrow is the
+// largest count of a frame and which.min / which.max index the packed values.
+//
+// Sums over frames (the two path costs, mean(|force|)) are made by a scheme that depends
+// on nl alone: lane l adds its frames l, l + nl, ... in order, then every lane folds the
+// nl partial sums in lane order. A sound's result therefore does not depend on the launch.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define SG_PATH_HD __host__ __device__
+#else
+#define SG_PATH_HD
+#endif
+
+namespace sg {
+
+// columns of a frame's row read or rewritten here (sg::AnlCol; sg_analyze.hip asserts they agree)
+constexpr int kPathAmpl = 0, kPathHNR = 2, kPathDom = 3, kPathQ25 = 7, kPathQ75 = 9, kPathDomCand = 11, kPathDomCert = 12,
+              kPathFixed = 15;
+// the four columns behind the candidates
+constexpr int kPathPitch = 0, kPathAmplVoiced = 1, kPathVoiced = 2, kPathHarmonics = 3, kPathCols = 4;
+// per-frame scratch slots behind the 2 W candidate cells
+constexpr int kSlotCog = 0,     // pitchCenterGravity
+              kSlotPath = 1,    // the path (log2), forward while both are alive
+              kSlotAux = 2,     // the backward path, then the snake's force
+              kSlotCnt = 3,     // candidates in the frame
+              kSlotHz = 4,      // pitchFinal (Hz) before the smoother
+              kSlotDom = 5,     // dom before the smoother
+              kSlotVoiced = 6,  // putativelyVoiced
+              kPathSlots = 7;
+// interpolWin and the smoother's half width: a median costs its width squared, and interpolate()'s run in one lane
+constexpr int kPathMaxWin = 64;
+
+struct PathPars {
+  int nCands;       // per method
+  int cols;         // doubles of a row: kPathFixed + 6 nCands + kPathCols
+  int minVoiced;    // minVoicedCands, resolved
+  int noRequired;   // max(1, ceiling(shortestSyl / step))
+  int nTolerated;   // floor(shortestPause / step)
+  int interpolWin;  // 0: interpolate() is not called
+  int pathfinding;  // 0 'none', 1 'fast'
+  int do_prior, smooth_pitch, smooth_dom;
+  double shape, rate, lconst, prior_norm;  // lconst = shape log(rate) - lgamma(shape); prior_norm = max(dgamma(seq))
+  double interpolTol, interpolCert, certWeight;
+  double snakeStep;    // <= 0: no snake
+  double smoothThres;  // 4 / smooth
+};
+
+SG_PATH_HD inline int path_width(int nCands) { return 2 + 3 * nCands; }
+SG_PATH_HD inline int path_stride(int nCands) { return 2 * path_width(nCands) + kPathSlots; }
+
+// to_dB(), R/utilities_math.R:37-39; a ratio <= 0 gives NaN as log10 does
+SG_PATH_HD inline double path_to_dB(double x) { return 10 * log10(x / (1 - x)); }
+
+// dgamma(x, shape, rate) = exp((shape - 1) ln x - rate x + shape ln(rate) - lgamma(shape)); 0 for x < 0
+SG_PATH_HD inline double path_dgamma(double x, double shape, double rate, double lconst) {
+  if (x < 0) return 0.0;
+  if (x == 0) return shape > 1 ? 0.0 : (shape == 1 ? rate : INFINITY);
+  return exp((shape - 1) * log(x) - rate * x + lconst);
+}
+
+// pitchCert_multiplier (R/analyze.R:606-610) of a candidate in Hz
+SG_PATH_HD inline double path_prior(double hz, const PathPars& P) {
+  const double semitones = log2(hz / 16.3516) * 12;  // HzToSemitones
+  return path_dgamma(semitones, P.shape, P.rate, P.lconst) / P.prior_norm;
+}
+
+// findVoicedSegments (:622-669), resumable: v[(k - 1) * stride] != 0 says frame k (1-based)
+// is putatively voiced; *ip is the loop's i (1 before the first call). Returns 1 with the
+// next segment [*s, *e] (1-based, inclusive), 0 when the outer loop has ended.
+SG_PATH_HD inline int path_next_segment(const double* v, int stride, int64_t n, int64_t noRequired, int64_t nTolerated,
+                                        int64_t* ip, int64_t* s, int64_t* e) {
+  int64_t i = *ip;
+  while (i < n - noRequired + 1) {
+    bool found = false;
+    while (i < n - noRequired + 1) {  // find beginning
+      bool all = true;
+      for (int64_t k = i; k <= i + noRequired - 1 && all; ++k) all = v[(k - 1) * stride] != 0;
+      if (all) {
+        found = true;
+        break;
+      }
+      ++i;
+    }
+    if (found) {
+      *s = i;
+      while (i < n - nTolerated + 1) {  // find end
+        bool any = false;
+        for (int64_t k = i; k <= i + nTolerated && !any; ++k) any = v[(k - 1) * stride] != 0;
+        if (!any) {
+          *e = i - 1;
+          *ip = i;  // i = i - 1, then i = i + 1
+          return 1;
+        }
+        ++i;
+      }
+      int64_t last = *s;  // the end is not found: the last non-NA value, and the outer loop breaks
+      for (int64_t k = n; k > *s; --k)
+        if (v[(k - 1) * stride] != 0) {
+          last = k;
+          break;
+        }
+      *e = last;
+      *ip = n + 1;
+      return 1;
+    }
+    ++i;
+  }
+  *ip = i;
+  return 0;
+}
+
+// median(x, na.rm = TRUE) of the n values p[j * stride], by ranks (no storage); NaN if none
+SG_PATH_HD inline double path_median(const double* p, int stride, int n) {
+  int m = 0;
+  for (int j = 0; j < n; ++j) m += p[(int64_t)j * stride] == p[(int64_t)j * stride];
+  if (!m) return NAN;
+  const int k1 = (m - 1) / 2, k2 = m / 2;
+  double a = NAN, b = NAN;
+  for (int j = 0; j < n; ++j) {
+    const double v = p[(int64_t)j * stride];
+    if (v != v) continue;
+    int lt = 0, le = 0;
+    for (int i = 0; i < n; ++i) {
+      const double w = p[(int64_t)i * stride];
+      lt += w < v;
+      le += w <= v;
+    }
+    if (lt <= k1 && k1 < le) a = v;
+    if (lt <= k2 && k2 < le) b = v;
+  }
+  return k1 == k2 ? a : (a + b) / 2;
+}
+
+// mean(x): the weights argument of the reference's mean(x, weights = ...) is ignored
+SG_PATH_HD inline double path_mean(const double* c, int cnt) {
+  if (cnt <= 0) return NAN;
+  double s = 0;
+  for (int k = 0; k < cnt; ++k) s += c[k];
+  return s / cnt;
+}
+
+// interpolate() (:149-184) at frame f of the n frames of a segment whose scratch starts
+// at seg: 1 if a candidate was added. Sequential in f: the updated centre of gravity
+// enters the medians of the next interpolWin frames.
+SG_PATH_HD inline int path_interpolate_frame(double* seg, int S, int W, int n, int f, const PathPars& P) {
+  const int left = f - P.interpolWin < 0 ? 0 : f - P.interpolWin;
+  const int right = f + P.interpolWin > n - 1 ? n - 1 : f + P.interpolWin;
+  const double med = path_median(seg + (int64_t)left * S + 2 * W + kSlotCog, S, right - left + 1);
+  if (med != med) return 0;
+  double* c = seg + (int64_t)f * S;
+  const int cnt = (int)c[2 * W + kSlotCnt];
+  const double lo = (1 - P.interpolTol) * med, hi = (1 + P.interpolTol) * med;
+  for (int k = 0; k < cnt; ++k)
+    if (c[k] > lo && c[k] < hi) return 0;
+  if (cnt >= W) return 0;  // cannot happen: W has room for one more than a row holds
+  c[cnt] = med;
+  c[W + cnt] = P.interpolCert;
+  c[2 * W + kSlotCnt] = cnt + 1;
+  c[2 * W + kSlotCog] = path_mean(c, cnt + 1);
+  return 1;
+}
+
+// order(pitchCands[, x]) (:69-79): ascending, stable, the certainties carried along
+SG_PATH_HD inline void path_sort_frame(double* c, double* a, int cnt) {
+  for (int i = 1; i < cnt; ++i) {
+    const double v = c[i], w = a[i];
+    int k = i;
+    for (; k > 0 && c[k - 1] > v; --k) {
+      c[k] = c[k - 1];
+      a[k] = a[k - 1];
+    }
+    c[k] = v;
+    a[k] = w;
+  }
+}
+
+// costJumps() (:283-285)
+SG_PATH_HD inline double path_cost_jump(double a, double b) { return 1 / (1 + 10 * exp(3 - 7 * fabs(a - b))); }
+
+// The start of pathfinding_fast (:209-213, :240-243): which.max(cert / |cand - p|), NA
+// skipped. p NaN (the backward median has no na.rm) leaves no start: NaN.
+SG_PATH_HD inline double path_start(const double* c, const double* a, int cnt, double p) {
+  if (p != p) return NAN;
+  int best = -1;
+  double bv = 0;
+  for (int k = 0; k < cnt; ++k) {
+    const double v = a[k] / fabs(c[k] - p);
+    if (v != v) continue;
+    if (best < 0 || v > bv) {
+      best = k;
+      bv = v;
+    }
+  }
+  return best < 0 ? NAN : c[best];
+}
+
+// which.min(costs) over a frame's candidates and min(costs). fast == 0 ('none', :110-113):
+// |cand - cog|. fast == 1 (:220-231): certWeight |cand - cog| + (1 - certWeight)
+// costJumps(start, cand); start is the segment's start point for every frame
+// (point_current is never updated) and the jump cost is 0 where there is no start.
+SG_PATH_HD inline int path_choose(const double* c, int cnt, double cog, double start, int fast, double certWeight,
+                                  double* cost) {
+  int best = -1;
+  double bv = 0;
+  for (int k = 0; k < cnt; ++k) {
+    double v = fabs(c[k] - cog);
+    if (fast) v = certWeight * v + (1 - certWeight) * (start == start ? path_cost_jump(start, c[k]) : 0.0);
+    if (v != v) continue;
+    if (best < 0 || v < bv) {
+      best = k;
+      bv = v;
+    }
+  }
+  *cost = best < 0 ? 0.0 : bv;
+  return best;
+}
+
+// findGrad() (:534-562): the slopes lm() fits to the first and the last min(3, n) points
+// (closed forms), the two extrapolated points at either end, the fourth difference
+SG_PATH_HD inline void path_end_slopes(const double* p, int S, int n, double* sl, double* sr) {
+  if (n < 2) {
+    *sl = *sr = 0;  // interpol == 1: the end values are repeated
+  } else if (n == 2) {
+    *sl = *sr = p[S] - p[0];
+  } else {
+    *sl = (p[2 * (int64_t)S] - p[0]) / 2;
+    *sr = (p[(int64_t)(n - 1) * S] - p[(int64_t)(n - 3) * S]) / 2;
+  }
+}
+SG_PATH_HD inline double path_ext(const double* p, int S, int n, int j, double sl, double sr) {
+  if (j < 0) return p[0] - (double)(-j) * sl;
+  if (j >= n) return p[(int64_t)(n - 1) * S] + (double)(j - n + 1) * sr;
+  return p[(int64_t)j * S];
+}
+SG_PATH_HD inline double path_grad(const double* p, int S, int n, int f, double sl, double sr) {
+  return path_ext(p, S, n, f - 2, sl, sr) - 4 * path_ext(p, S, n, f - 1, sl, sr) + 6 * path_ext(p, S, n, f, sl, sr) -
+         4 * path_ext(p, S, n, f + 1, sl, sr) + path_ext(p, S, n, f + 2, sl, sr);
+}
+
+// forcePerPath() (:495-521) at one frame: a candidate pulls with cert / exp((cand - pitch)^2),
+// towards itself only where cand > pitch (one equal to pitch pushes with -cert)
+SG_PATH_HD inline double path_force(const double* c, const double* a, int cnt, double pitch, double grad, double certWeight) {
+  double external = 0;
+  for (int k = 0; k < cnt; ++k) {
+    const double d = c[k] - pitch;
+    const double f = a[k] * (1 / exp(d * d));
+    external += c[k] > pitch ? f : -f;
+  }
+  return certWeight * external + (1 - certWeight) * (-grad);
+}
+
+// medianSmoother()'s decision (:595-597): abs(deviance - 1), not abs(deviance); NA keeps v
+SG_PATH_HD inline double path_smooth(double v, double med, double thres) {
+  const double deviance = 12 * log2(v / med);
+  return fabs(deviance - 1) > thres ? med : v;
+}
+
+// op 0 sum, 1 min, 2 max of v over the lanes, folded in lane order; every lane gets it
+template <class Sync>
+SG_PATH_HD inline double path_reduce(double v, int op, int lane, int nl, double* red, Sync& sync) {
+  sync();
+  red[lane] = v;
+  sync();
+  double r = red[0];
+  for (int t = 1; t < nl; ++t) r = op == 0 ? r + red[t] : (op == 1 ? fmin(r, red[t]) : fmax(r, red[t]));
+  return r;
+}
+
+// One sound: nf rows of P.cols doubles (the candidates as pitch_candidates leaves them)
+// -> pitch, amplVoiced, voiced (harmonics NaN: sg_anl_harm fills it), the smoothed dom,
+// the blanked quartiles, HNR in dB. scr: nf * path_stride() doubles; red: nl doubles and
+// sh: 3 int64 shared by the lanes; hw: floor(smoothing_ww / 2). Every lane must call it.
+template <class Sync>
+SG_PATH_HD inline void path_sound(const PathPars& P, int nf, int hw, double* rows, double* scr, int lane, int nl,
+                                  double* red, int64_t* sh, Sync sync) {
+  const int W = path_width(P.nCands), S = path_stride(P.nCands), X = 2 * W;
+  const int c0 = P.cols - kPathCols;
+  // pitch_matrices (:578-591), log2 (pathfinder :39), the prior (:598-612), the centre of gravity (:43-49)
+  for (int f = lane; f < nf; f += nl) {
+    const double* row = rows + (int64_t)f * P.cols;
+    double* c = scr + (int64_t)f * S;
+    int cnt = 0;
+    for (int j = 0; j < 1 + 3 * P.nCands; ++j) {
+      const int m = (j - 1) / P.nCands, k = (j - 1) % P.nCands;
+      const double cand = j == 0 ? row[kPathDomCand] : row[kPathFixed + 2 * m * P.nCands + k];
+      const double cert = j == 0 ? row[kPathDomCert] : row[kPathFixed + (2 * m + 1) * P.nCands + k];
+      if (cand != cand) continue;
+      c[cnt] = log2(cand);
+      c[W + cnt] = P.do_prior ? cert * path_prior(cand, P) : cert;
+      ++cnt;
+    }
+    for (int k = cnt; k < W; ++k) c[k] = c[W + k] = NAN;
+    c[X + kSlotCog] = path_mean(c, cnt);
+    c[X + kSlotPath] = c[X + kSlotAux] = c[X + kSlotHz] = NAN;
+    c[X + kSlotCnt] = cnt;
+    c[X + kSlotDom] = row[kPathDom];
+    c[X + kSlotVoiced] = cnt >= P.minVoiced ? 1.0 : 0.0;
+  }
+  if (lane == 0) sh[0] = 1;
+  for (;;) {
+    sync();
+    if (lane == 0) {
+      int64_t i = sh[0], s = 0, e = 0;
+      if (!path_next_segment(scr + X + kSlotVoiced, S, nf, P.noRequired, P.nTolerated, &i, &s, &e)) s = 0;
+      sh[0] = i;
+      sh[1] = s;
+      sh[2] = e;
+    }
+    sync();
+    if (sh[1] == 0) break;
+    double* seg = scr + (sh[1] - 1) * S;
+    const int n = (int)(sh[2] - sh[1] + 1);
+    if (P.interpolWin > 0) {
+      if (lane == 0)
+        for (int f = 0; f < n; ++f) path_interpolate_frame(seg, S, W, n, f, P);
+      sync();
+    }
+    double lo = INFINITY, hi = -INFINITY, most = 0, least = INFINITY;
+    for (int f = lane; f < n; f += nl) {
+      double* c = seg + (int64_t)f * S;
+      const int cnt = (int)c[X + kSlotCnt];
+      path_sort_frame(c, c + W, cnt);
+      if (cnt) {
+        lo = fmin(lo, c[0]);
+        hi = fmax(hi, c[cnt - 1]);
+      }
+      most = fmax(most, (double)cnt);
+      least = fmin(least, (double)cnt);
+    }
+    most = path_reduce(most, 2, lane, nl, red, sync);
+    least = path_reduce(least, 1, lane, nl, red, sync);
+    if (most <= 1) {  // a single row: no paths to choose among (:87-89)
+      for (int f = lane; f < n; f += nl) {
+        double* c = seg + (int64_t)f * S;
+        c[X + kSlotHz] = c[X + kSlotCnt] > 0 ? exp2(c[0]) : NAN;
+      }
+      continue;
+    }
+    if (n >= 2 && P.pathfinding == 1) {  // pathfinding_fast (:203-267)
+      const int nh = n < 5 ? n : 5;
+      const double pF = path_median(seg + X + kSlotCog, S, nh);
+      bool na = false;  // the backward median has no na.rm
+      for (int f = n - nh; f < n; ++f) na = na || seg[(int64_t)f * S + X + kSlotCog] != seg[(int64_t)f * S + X + kSlotCog];
+      const double pB = na ? NAN : path_median(seg + (int64_t)(n - nh) * S + X + kSlotCog, S, nh);
+      const double* c1 = seg + (int64_t)(n - 1) * S;
+      const double startF = path_start(seg, seg + W, (int)seg[X + kSlotCnt], pF);
+      const double startB = path_start(c1, c1 + W, (int)c1[X + kSlotCnt], pB);
+      double costF = 0, costB = 0;
+      for (int f = lane; f < n; f += nl) {
+        double* c = seg + (int64_t)f * S;
+        const int cnt = (int)c[X + kSlotCnt];
+        double cost = 0;
+        int k = f == 0 ? -1 : path_choose(c, cnt, c[X + kSlotCog], startF, 1, P.certWeight, &cost);
+        c[X + kSlotPath] = f == 0 ? startF : (k < 0 ? NAN : c[k]);
+        if (f != 0) costF += cost;
+        k = f == n - 1 ? -1 : path_choose(c, cnt, c[X + kSlotCog], startB, 1, P.certWeight, &cost);
+        c[X + kSlotAux] = f == n - 1 ? startB : (k < 0 ? NAN : c[k]);
+        if (f != n - 1) costB += cost;
+      }
+      costF = path_reduce(costF, 0, lane, nl, red, sync);
+      costB = path_reduce(costB, 0, lane, nl, red, sync);
+      if (!(costF < costB))
+        for (int f = lane; f < n; f += nl) seg[(int64_t)f * S + X + kSlotPath] = seg[(int64_t)f * S + X + kSlotAux];
+    } else {  // 'none' (:110-113)
+      for (int f = lane; f < n; f += nl) {
+        double* c = seg + (int64_t)f * S;
+        double cost;
+        const int k = path_choose(c, (int)c[X + kSlotCnt], c[X + kSlotCog], NAN, 0, P.certWeight, &cost);
+        c[X + kSlotPath] = k < 0 ? NAN : c[k];
+      }
+    }
+    sync();
+    // snake() (:419-475); not run on a segment with a frame that has no candidate (in the
+    // reference its first force_new is NA and it breaks at once)
+    if (P.snakeStep > 0 && least > 0) {
+      lo = path_reduce(lo, 1, lane, nl, red, sync);
+      hi = path_reduce(hi, 2, lane, nl, red, sync);
+      const double maxIter = floor((hi - lo) / P.snakeStep * 2);
+      const double* p = seg + X + kSlotPath;
+      double force_old = 1e10;
+      for (double it = 1; it < maxIter; it += 1) {
+        double sl, sr, part = 0;
+        path_end_slopes(p, S, n, &sl, &sr);
+        for (int f = lane; f < n; f += nl) {
+          double* c = seg + (int64_t)f * S;
+          const double force = path_force(c, c + W, (int)c[X + kSlotCnt], c[X + kSlotPath], path_grad(p, S, n, f, sl, sr),
+                                          P.certWeight);
+          c[X + kSlotAux] = force;
+          part += fabs(force);
+        }
+        const double force_new = path_reduce(part, 0, lane, nl, red, sync) / n;
+        const double force_delta = (force_old - force_new) / force_old;
+        force_old = force_new;
+        if (force_delta != force_delta || force_delta < P.snakeStep) break;
+        for (int f = lane; f < n; f += nl) {
+          double* c = seg + (int64_t)f * S;
+          c[X + kSlotPath] = c[X + kSlotPath] + P.snakeStep * c[X + kSlotAux];
+        }
+        sync();
+      }
+    }
+    for (int f = lane; f < n; f += nl) {
+      double* c = seg + (int64_t)f * S;
+      c[X + kSlotHz] = exp2(c[X + kSlotPath]);  // 2 ^ bestPath; NaN where the frame had no candidate
+    }
+  }
+  sync();
+  // medianSmoother (:670-681, reading the unsmoothed copies) and the final columns (:685-703)
+  for (int f = lane; f < nf; f += nl) {
+    double* row = rows + (int64_t)f * P.cols;
+    const double* c = scr + (int64_t)f * S;
+    const int a = f - hw < 0 ? 0 : f - hw, b = f + hw > nf - 1 ? nf - 1 : f + hw;
+    double pitch = c[X + kSlotHz], dom = c[X + kSlotDom];
+    if (P.smooth_pitch && pitch == pitch)
+      pitch = path_smooth(pitch, path_median(scr + (int64_t)a * S + X + kSlotHz, S, b - a + 1), P.smoothThres);
+    if (P.smooth_dom && dom == dom)
+      dom = path_smooth(dom, path_median(scr + (int64_t)a * S + X + kSlotDom, S, b - a + 1), P.smoothThres);
+    const bool voiced = pitch == pitch;
+    row[kPathDom] = dom;
+    row[c0 + kPathPitch] = pitch;
+    row[c0 + kPathAmplVoiced] = voiced ? row[kPathAmpl] : NAN;
+    row[c0 + kPathVoiced] = voiced ? 1.0 : 0.0;
+    row[c0 + kPathHarmonics] = NAN;
+    if (!voiced)
+      for (int q = kPathQ25; q <= kPathQ75; ++q) row[q] = NAN;
+    row[kPathHNR] = path_to_dB(row[kPathHNR]);
+  }
+}
+
+}  // namespace sg

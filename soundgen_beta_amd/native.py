@@ -134,6 +134,14 @@ def lib():
         L.sg_pitch_candidates.argtypes = [vp, dp, i64, ppp, dp]
         L.sg_pitch_candidates_batch.argtypes = [vp, vp, i64p, i64p, i64, ppp, vp, i64p, i32p]
         L.sg_debug_pitch_kernel_ms.argtypes = [dp]
+    if hasattr(L, "sg_analyze_size"):  # analyze()'s tail behind the candidates: likewise additive
+        i32p = C.POINTER(C.c_int32)
+        fpp = C.POINTER(_abi.sg_analyze_params_full)
+        L.sg_analyze_size.argtypes = [i64, fpp, i32p, i32p, i32p]
+        L.sg_analyze.argtypes = [vp, dp, i64, fpp, dp]
+        L.sg_analyze_batch.argtypes = [vp, vp, i64p, i64p, i64, fpp, vp, i64p, i32p]
+        L.sg_pitch_path.argtypes = [vp, dp, C.c_int32, i64, fpp, dp]
+        L.sg_debug_track_kernel_ms.argtypes = [dp]
     L.sg_rrng_create.argtypes = [C.c_int32, C.POINTER(vp)]
     L.sg_rrng_destroy.argtypes = [vp]
     L.sg_rrng_set_seed.argtypes = [vp, C.c_int32]
