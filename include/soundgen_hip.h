@@ -637,6 +637,69 @@ int sg_analyze_batch(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, c
  * are read. */
 int sg_pitch_path(sg_ctx* ctx, const double* table, int32_t frames, int64_t len, const sg_analyze_params_full* p,
                   double* out);
+/* segment() (an additive extension of ABI 5; R/segment.R:79-219, R/utilities_segment.R):
+ * the smoothed Hilbert envelope of the whole sound (seewave::env(envt = "hil", msmooth =
+ * c(windowLength_points, overlap)): a transform of 2^ceiling(log2(len)) points), the
+ * syllables, the bursts and the summary row, fp64. shortestPause NaN = NULL / NA (no
+ * merging); interburst NaN = NULL (median(sylLen) * interburstMult, or shortestSyl without
+ * a syllable), otherwise >= 0 (SG_E_ARG). overlap is clamped to 0..99 as the reference
+ * does. mode 0: segment(); mode 1: Mod(seewave::hilbert(wave)) alone, un-padded by the
+ * reference's rule and not normalized (only len is read of the other fields' effects).
+ * workspace_cap: bytes of transform workspace one chunk of a batch may take (0: the
+ * default, sg_segment.h; a larger sound runs alone); results do not depend on it.
+ * SG_E_ARG where the reference stops (len < 2, a smoothing window of 0 or 1 points: len
+ * == 2 among them); SG_E_UNSUPPORTED for more than 2^22 transform points. */
+typedef struct sg_segment_params {
+  double samplingRate;
+  double windowLength;
+  double overlap;
+  double shortestSyl;
+  double shortestPause;
+  double sylThres;
+  double interburst;
+  double interburstMult;
+  double burstThres;
+  double peakToTrough;
+  int32_t troughLeft;
+  int32_t troughRight;
+  int32_t mode;
+  int32_t reserved;
+  int64_t workspace_cap;
+} sg_segment_params;
+/* The integer decisions for a sound of len samples (host only, no device): log2 of the
+ * transform length, the envelope's values (mode 0: the smoothed envelope's, mode 1: the
+ * un-padded transform's: len, or len - 1 for len = 2^p - 1), the points of a smoothing
+ * window (mode 0) and the doubles of the sound's output. Mode 0's cells (m = *n_env):
+ * [0] m [1] rows of the syllable table [2] 1 if a syllable was found (0: one row,
+ * syllable = 0, NaN elsewhere) [3] bursts [4] timestep, ms [5] threshold [6] interburst,
+ * ms [7] floor(interburst / timestep); [8 .. 18] nSyl, sylLen_mean, sylLen_median,
+ * sylLen_sd, pauseLen_mean, pauseLen_median, pauseLen_sd, nBursts, interburst_mean,
+ * interburst_median, interburst_sd (NaN for NA); from 19 the envelope (m); from 19 + m the
+ * syllable table, rows x (syllable, start, end, sylLen, pauseLen), room for (m + 1) / 2
+ * rows; behind it the burst table, bursts x (time, ampl, interburstInt), room for m rows;
+ * then m cells of scratch. Mode 1's cells: the envelope. Errors through
+ * sg_segment_size_error. */
+int sg_segment_size(int64_t len, const sg_segment_params* p, int32_t* log2n, int32_t* n_env, int32_t* points,
+                    int64_t* cells);
+const char* sg_segment_size_error(void);
+/* Host only, mode 0: the n = *n_env smoothing windows of the sound and the envelope's time
+ * step in ms. Point j of a window is the envelope's value first + j (0-based), and first +
+ * j + 1 from j = jump on: R's from:to adds in fp64 from a fractional from, and a from a
+ * rounding error below a whole number makes the truncated indices skip one value where
+ * the sum rounds up (jump = points: nothing skipped). */
+int sg_segment_windows(int64_t len, const sg_segment_params* p, int64_t* first, int64_t* points, int64_t* jump,
+                       int32_t n, double* timestep);
+/* One sound from host memory; out: *cells doubles of host memory. */
+int sg_segment(sg_ctx* ctx, const double* wave, int64_t len, const sg_segment_params* p, double* out);
+/* n_calls sounds already in device memory (d_wave + offsets[c], lengths[c] samples) into
+ * d_out + out_off[c] (device memory; out_off has n_calls + 1 entries, and out_off[c + 1] -
+ * out_off[c] must hold the sound's cells: SG_E_CAPACITY). Mode 0 only. A sound of fewer
+ * than three samples (the reference stops) takes 19 cells: zeros, and a NaN summary with
+ * nSyl = nBursts = 0. A sound's cells are the same bit for bit alone (from the same fp32
+ * samples), in any batch and under any workspace_cap. Nothing is launched when a sound is
+ * refused. */
+int sg_segment_batch(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, const int64_t* lengths, int64_t n_calls,
+                     const sg_segment_params* p, double* d_out, const int64_t* out_off);
 /* Process-wide policy of the fp64 filter path for later sg_plan_batch calls:
  * mode 0 never, 1 when the conditioning estimate exceeds rho (default 100),
  * 2 every filtered bout. SG_E_ARG for an invalid mode or rho. */
@@ -782,6 +845,12 @@ int sg_debug_pitch_kernel_ms(double* out);
  * above, then the path stage (segments, pathfinder, smoother, final columns), then the
  * harmonics (8 doubles; sg_pitch_path runs the seventh alone). */
 int sg_debug_track_kernel_ms(double* out);
+/* The same for the last sg_segment / sg_segment_batch run, summed over the chunks of a
+ * batch: the normalization statistics, the forward columns with their twiddle (or the
+ * whole transform of a sound of at most 2048 points), the rows (forward, the Hilbert
+ * multiplier, inverse, twiddle), the inverse columns with Mod and the un-padding, the
+ * smoothing, and the tail (syllables, bursts, summary) (6 doubles). */
+int sg_debug_segment_kernel_ms(double* out);
 
 #ifdef __cplusplus
 }

@@ -77,6 +77,13 @@ class sg_analyze_params_full(C.Structure):
         [("pathfinding", C.c_int32), ("smoothVars", C.c_int32)]
 
 
+class sg_segment_params(C.Structure):
+    _fields_ = [(f, C.c_double) for f in ("samplingRate", "windowLength", "overlap", "shortestSyl", "shortestPause",
+                                          "sylThres", "interburst", "interburstMult", "burstThres", "peakToTrough")] + \
+        [("troughLeft", C.c_int32), ("troughRight", C.c_int32), ("mode", C.c_int32), ("reserved", C.c_int32),
+         ("workspace_cap", C.c_int64)]
+
+
 NORM_CB = C.CFUNCTYPE(C.c_double, C.c_void_p)
 UNIF_CB = C.CFUNCTYPE(C.c_double, C.c_void_p)
 GAMMA_CB = C.CFUNCTYPE(C.c_double, C.c_void_p, C.c_double, C.c_double)

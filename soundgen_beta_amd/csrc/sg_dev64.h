@@ -1,5 +1,5 @@
 // sg_dev64.h — the fp64 device helpers that more than one of sg_mel.hip,
-// sg_ssm.hip, sg_spectrogram.hip and sg_analyze.hip use: the order-preserving
+// sg_ssm.hip, sg_spectrogram.hip, sg_analyze.hip and sg_segment.hip use: the order-preserving
 // keys behind their atomic minima and maxima, and the reductions whose order is
 // part of the results. Included by .hip files only.
 #pragma once

@@ -1,5 +1,6 @@
 // sg_fft64_dev.h — the fp64 complex transform that sg_fft.hip (the fp64 formant
-// filter frames, sg_fft_frames64) and sg_spectrogram.hip (spectrogram()'s frames)
+// filter frames, sg_fft_frames64), sg_spectrogram.hip (spectrogram()'s frames) and
+// sg_segment.hip (the rows and columns of segment()'s whole-sound transform)
 // share on the device: an M-point mixed-radix Stockham FFT (radices 2, 4 and the
 // odd primes <= 31, M <= 2048) of one frame per SG_F64_THREADS-thread workgroup,
 // and the contract of its table of roots. Included by .hip files only.

@@ -1,5 +1,5 @@
 // sg_launch.h — what every host-side launch sequence of the analysis features
-// (sg_mel.hip, sg_ssm.hip, sg_spectrogram.hip, sg_analyze.hip) and the C entry
+// (sg_mel.hip, sg_ssm.hip, sg_spectrogram.hip, sg_analyze.hip, sg_segment.hip) and the C entry
 // points (theirs and sg_api.cpp's) share: the HIP error check, the buffers of a
 // launch sequence, the exception-to-code mapping of an entry point, the per-stage
 // device clock and the single-sound round trip. Host code that needs the HIP runtime.

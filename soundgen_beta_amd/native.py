@@ -142,6 +142,16 @@ def lib():
         L.sg_analyze_batch.argtypes = [vp, vp, i64p, i64p, i64, fpp, vp, i64p, i32p]
         L.sg_pitch_path.argtypes = [vp, dp, C.c_int32, i64, fpp, dp]
         L.sg_debug_track_kernel_ms.argtypes = [dp]
+    if hasattr(L, "sg_segment_size"):  # segment(): likewise additive
+        i32p = C.POINTER(C.c_int32)
+        gpp = C.POINTER(_abi.sg_segment_params)
+        L.sg_segment_size.argtypes = [i64, gpp, i32p, i32p, i32p, i64p]
+        L.sg_segment_size_error.argtypes = []
+        L.sg_segment_size_error.restype = C.c_char_p
+        L.sg_segment_windows.argtypes = [i64, gpp, i64p, i64p, i64p, C.c_int32, dp]
+        L.sg_segment.argtypes = [vp, dp, i64, gpp, dp]
+        L.sg_segment_batch.argtypes = [vp, vp, i64p, i64p, i64, gpp, vp, i64p]
+        L.sg_debug_segment_kernel_ms.argtypes = [dp]
     L.sg_rrng_create.argtypes = [C.c_int32, C.POINTER(vp)]
     L.sg_rrng_destroy.argtypes = [vp]
     L.sg_rrng_set_seed.argtypes = [vp, C.c_int32]
