@@ -637,6 +637,40 @@ int sg_analyze_batch(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, c
  * are read. */
 int sg_pitch_path(sg_ctx* ctx, const double* table, int32_t frames, int64_t len, const sg_analyze_params_full* p,
                   double* out);
+/* analyze(summary = TRUE) (an additive extension of ABI 5; R/analyze.R:770-796): one row
+ * of SG_ANALYZE_SUMMARY_COLS doubles per sound from its finished table: duration (s: the
+ * sound's len / samplingRate), voiced (the proportion of voiced frames), then <var>_mean,
+ * <var>_median, <var>_sd over the frames where the variable is not NaN, for ampl,
+ * amplVoiced, dom, entropy, harmonics, HNR, meanFreq, peakFreq, peakFreqCut, pitch,
+ * quartile25, quartile50, quartile75, specSlope (the reference's sort() of the column
+ * names under a case-insensitive collation; the C locale would put HNR first: the names
+ * identify the cells). R's arithmetic in fp64: the mean is sum / n refined once by the
+ * mean of the residuals, the sd is the two-pass variance about the refined mean over n -
+ * 1 (NaN for n < 2), the median is exact (a zero comes out as +0.0); NaN for no value;
+ * +-Inf are ordinary values. A sound without frames (not longer than the window, or len <
+ * 0) gets SG_ANALYZE_SUMMARY_COLS NaN. A sound's row is the same bit for bit alone, in any
+ * batch and at any position of it. */
+#define SG_ANALYZE_SUMMARY_COLS 44
+/* Host only: the name of cell i of a row ("duration", "voiced", "ampl_mean", ...); NULL
+ * outside 0 .. SG_ANALYZE_SUMMARY_COLS - 1. Valid until the thread's next call. */
+const char* sg_analyze_summary_name(int32_t i);
+/* The summary stage alone, from a HOST table of `frames` rows of cols = 15 + 6 nCands + 4
+ * doubles (an sg_analyze table, or the caller's own) of a sound of len samples; out
+ * receives SG_ANALYZE_SUMMARY_COLS doubles of host memory. */
+int sg_analyze_summary(sg_ctx* ctx, const double* table, int32_t frames, int32_t cols, int32_t nCands, int64_t len,
+                       double samplingRate, double* out);
+/* sg_analyze_batch followed by the summary kernel in the same launch sequence: d_tables,
+ * out_off and frames_out exactly as sg_analyze_batch's d_out, out_off and frames_out (the
+ * tables are the same bit for bit and stay valid); d_summary (device memory) receives
+ * n_calls x SG_ANALYZE_SUMMARY_COLS doubles, row c for call c. */
+int sg_analyze_summary_batch(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, const int64_t* lengths,
+                             int64_t n_calls, const sg_analyze_params_full* p, double* d_tables, const int64_t* out_off,
+                             int32_t* frames_out, double* d_summary);
+/* sg_analyze for one sound from host memory with its summary row: out (host, the table of
+ * sg_analyze, or NULL when only the row is wanted) and summary (host,
+ * SG_ANALYZE_SUMMARY_COLS doubles). Refuses what sg_analyze refuses. */
+int sg_analyze_summary_sound(sg_ctx* ctx, const double* wave, int64_t len, const sg_analyze_params_full* p, double* out,
+                             double* summary);
 /* segment() (an additive extension of ABI 5; R/segment.R:79-219, R/utilities_segment.R):
  * the smoothed Hilbert envelope of the whole sound (seewave::env(envt = "hil", msmooth =
  * c(windowLength_points, overlap)): a transform of 2^ceiling(log2(len)) points), the
@@ -845,6 +879,10 @@ int sg_debug_pitch_kernel_ms(double* out);
  * above, then the path stage (segments, pathfinder, smoother, final columns), then the
  * harmonics (8 doubles; sg_pitch_path runs the seventh alone). */
 int sg_debug_track_kernel_ms(double* out);
+/* The device milliseconds of the summary kernel of the last sg_analyze_summary /
+ * sg_analyze_summary_batch / sg_analyze_summary_sound run (1 double); the stages before it
+ * are sg_debug_track_kernel_ms's, unchanged. */
+int sg_debug_summary_kernel_ms(double* out);
 /* The same for the last sg_segment / sg_segment_batch run, summed over the chunks of a
  * batch: the normalization statistics, the forward columns with their twiddle (or the
  * whole transform of a sound of at most 2048 points), the rows (forward, the Hilbert

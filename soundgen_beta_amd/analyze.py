@@ -35,8 +35,13 @@ inputs, R/analyze.R:578-591). analyze* (at the end of this module) add what foll
 candidates (R/analyze.R:576-707, R/utilities_pitch_postprocessing.R): the prior,
 findVoicedSegments, pathfinder, medianSmoother and the final columns, restated as
 analyze_numpy / pitch_path_numpy and on the GPU (sg_anl_path, sg_anl_harm; sg_path.h).
+summary = TRUE (R/analyze.R:770-796: one row per sound, the mean, median and sd of every
+acoustic variable) is summarize_table_numpy and, on the GPU, sg_anl_summary (sg_summary.h):
+analyze(summary=True), analyze_batch(summary=True), summarize_table; analyze_folder is
+analyzeFolder() (:831-930) on top of analyze_batch.
 Formants (phonTools is not in the reference tree), pathfinding = 'slow', the pitchAutocor /
-pitchCep / pitchSpec columns, plots, summary and savePath are out of scope.
+pitchCep / pitchSpec columns (so also their summary cells and the formants'), plots and
+savePath are out of scope.
 
 Quirks kept (what the statements do):
     * the frequency labels pass through R's character row names (spectrogram.R:176,
@@ -504,11 +509,12 @@ def _run(sound, sr, s, decisions, params, table, entry, device):
 
 
 def _run_batch(data, offsets, lengths, samplingRate, s, frames_of, params, table, cand_keys, entry, to_host, device,
-               tail=()):
+               tail=(), summary=False):
     """The *_batch forms likewise: frames_of(length, P) is the stage's frame count of a
     sound, cand_keys name the nCands-wide column groups behind the fixed columns, `tail`
     the single columns behind those, and the C entry points are entry + "_batch" and (in
-    the text of the cross-check) entry + "_size"."""
+    the text of the cross-check) entry + "_size". summary (analyze_batch only): the entry
+    point is sg_analyze_summary_batch, which also fills one row of 44 cells per call."""
     L = native.lib()
     P = params(s)
     offs, lens, nc, p_offs, p_lens = native.batch_layout(offsets, lengths)
@@ -519,11 +525,22 @@ def _run_batch(data, offsets, lengths, samplingRate, s, frames_of, params, table
     ctx = native.default_context(device)
     fo = np.zeros(max(nc, 1), dtype=np.int32)
     out = native.device_out(data, ooff[-1])
-    _check(getattr(L, entry + "_batch")(ctx.ptr, C.c_void_p(data.data_ptr()), p_offs, p_lens, nc, C.byref(P),
-                                        C.c_void_p(out.data_ptr()), p_ooff,
-                                        fo.ctypes.data_as(C.POINTER(C.c_int32))), ctx.ptr)
+    if summary:
+        rows = native.device_out(data, max(nc, 1) * len(SUMMARY_COLUMNS))
+        _check(L.sg_analyze_summary_batch(ctx.ptr, C.c_void_p(data.data_ptr()), p_offs, p_lens, nc, C.byref(P),
+                                          C.c_void_p(out.data_ptr()), p_ooff, fo.ctypes.data_as(C.POINTER(C.c_int32)),
+                                          C.c_void_p(rows.data_ptr())), ctx.ptr)
+    else:
+        _check(getattr(L, entry + "_batch")(ctx.ptr, C.c_void_p(data.data_ptr()), p_offs, p_lens, nc, C.byref(P),
+                                            C.c_void_p(out.data_ptr()), p_ooff,
+                                            fo.ctypes.data_as(C.POINTER(C.c_int32))), ctx.ptr)
     if [int(f) for f in fo[:nc]] != frames:
         raise native.SoundgenError(-1, "%s_batch: frame counts disagree with %s_size" % (entry, entry))
+    if summary:
+        rows = rows[:nc * len(SUMMARY_COLUMNS)].view(nc, len(SUMMARY_COLUMNS))
+        if not to_host:
+            return dict(out=rows, columns=SUMMARY_COLUMNS, frames=frames, tables=out, offsets=ooff[:-1].copy(), cols=cols)
+        return [dict(zip(SUMMARY_COLUMNS, (float(v) for v in r))) for r in rows.cpu().numpy()]
     if not to_host:
         return dict(out=out, offsets=ooff[:-1].copy(), frames=frames, cols=cols,
                     columns=COLUMNS + sum(((k,) * nC for k in cand_keys), ()) + tuple(tail))
@@ -1379,14 +1396,15 @@ def analyze_numpy(x, samplingRate=None, silence=0.04, windowLength=50, step=None
                   specThres=0.3, specPeak=0.35, specSinglePeakCert=0.4, specHNRslope=0.8, specSmooth=150, specMerge=1,
                   shortestSyl=20, shortestPause=60, interpolWin=3, interpolTol=0.3, interpolCert=0.3, pathfinding="fast",
                   certWeight=.5, snakeStep=0.05, snakePlot=False, smooth=1, smoothVars=SMOOTH_VARS, plot=False,
-                  _probe=None):
+                  summary=False, _probe=None):
     """analyze() (R/analyze.R:153-707) restated on the host: pitch_candidates_numpy(), then
     statement by statement pitch_matrices (:578-591), the prior (:598-612; priorMean
     'default' is HzToSemitones(300), None skips it), minVoicedCands 'autom' (:615-624),
     findVoicedSegments, pathfinder per segment, medianSmoother (:670-681) and the final
     columns (:685-703). Returns pitch_candidates_numpy()'s dict with pitch, voiced,
     amplVoiced and harmonics added, HNR and harmonics in dB, dom (and pitch) smoothed and
-    the quartiles blanked for unvoiced frames.
+    the quartiles blanked for unvoiced frames. summary=True (:770-796) returns
+    summarize_table_numpy() of that table instead.
 
     Quirks kept (what the statements do):
         * mean(x, weights = ...) ignores `weights`: the centre of gravity is a plain mean;
@@ -1411,8 +1429,8 @@ def analyze_numpy(x, samplingRate=None, silence=0.04, windowLength=50, step=None
     Out of scope: pathfinding = 'slow' (simulated annealing through optim() on R's random
     stream) and smoothVars outside ('pitch', 'dom') raise NotImplementedError, as do the
     plots; the columns pitchAutocor / pitchCep / pitchSpec (:659-667, as.numeric of
-    zero-length list elements, which cannot be settled without R), formants, summary
-    and savePath are not built.
+    zero-length list elements, which cannot be settled without R), formants and savePath
+    are not built.
 
     _probe (a dict) receives pitch_candidates_numpy()'s intermediates and `segments`
     (per voiced segment the sides (a, b) of every discrete comparison: `band` the
@@ -1431,7 +1449,8 @@ def analyze_numpy(x, samplingRate=None, silence=0.04, windowLength=50, step=None
         warnings.simplefilter("ignore")  # repair_pitch() has warned already
         t = pitch_candidates_numpy(sound, sr, _probe=probe, **_pitch_args(a))
     d = probe["d"]
-    return _track(t, s, len(sound), probe["S"], freq_labels(sr, d["wl"], d["bins"]), probe)
+    t = _track(t, s, len(sound), probe["S"], freq_labels(sr, d["wl"], d["bins"]), probe)
+    return summarize_table_numpy(t) if summary else t
 
 
 def pitch_path_numpy(table, step, samplingRate, pitchMethods=PITCH_DEFAULT_METHODS, pitchFloor=75, pitchCeiling=3500,
@@ -1531,19 +1550,35 @@ def analyze(x, samplingRate=None, silence=0.04, windowLength=50, step=None, over
             domSmooth=220, autocorThres=0.7, autocorSmooth=None, cepThres=0.3, cepSmooth=None, cepZp=0, specThres=0.3,
             specPeak=0.35, specSinglePeakCert=0.4, specHNRslope=0.8, specSmooth=150, specMerge=1, shortestSyl=20,
             shortestPause=60, interpolWin=3, interpolTol=0.3, interpolCert=0.3, pathfinding="fast", certWeight=.5,
-            snakeStep=0.05, snakePlot=False, smooth=1, smoothVars=SMOOTH_VARS, plot=False, device=0):
+            snakeStep=0.05, snakePlot=False, smooth=1, smoothVars=SMOOTH_VARS, plot=False, device=0,
+            summary=False):
     """analyze() (R/analyze.R:153-707) on the GPU (sg_analyze, fp64): pitch_candidates()'
     dict plus pitch (the pathfinder's contour through the voiced segments, smoothed),
     voiced, amplVoiced and harmonics, with HNR and harmonics in dB, dom smoothed and the
     quartiles blanked for unvoiced frames. The candidates are made and consumed in one
     launch sequence (sg_anl_path: one 64-lane workgroup per sound; sg_anl_harm). The
     quirks kept, the one stated difference from the reference and what is out of scope
-    (pathfinding = 'slow', pitchAutocor / pitchCep / pitchSpec, formants, summary,
-    plots, savePath) are listed at analyze_numpy(), which this is compared against.
-    plot defaults to False; True raises."""
+    (pathfinding = 'slow', pitchAutocor / pitchCep / pitchSpec, formants, plots, savePath)
+    are listed at analyze_numpy(), which this is compared against. plot defaults to False;
+    True raises (with summary=True too, before anything runs). summary=True (R/analyze.R:
+    770-796) returns the sound's summary row instead, a dict of the 44 floats named by
+    SUMMARY_COLUMNS (see summarize_table_numpy): sg_anl_summary makes it from the table in
+    the same launch sequence (sg_analyze_summary_sound) and only the row leaves the device."""
     sound, sr = _input(x, samplingRate)
     a = locals()
     s = repair_track(repair_pitch(sr, len(sound) / sr, **_pitch_args(a)), **_track_args(a))
+    if summary:
+        d = track_decisions_native(len(sound), s)
+        if len(sound) <= d["wl"]:
+            raise _too_short(len(sound), d["wl"])
+        ctx = native.default_context(device)
+        sound = np.ascontiguousarray(sound)
+        row = np.zeros(len(SUMMARY_COLUMNS))
+        dp = C.POINTER(C.c_double)
+        P = _track_params(s)
+        _check(native.lib().sg_analyze_summary_sound(ctx.ptr, sound.ctypes.data_as(dp), len(sound), C.byref(P), None,
+                                                     row.ctypes.data_as(dp)), ctx.ptr)
+        return dict(zip(SUMMARY_COLUMNS, (float(v) for v in row)))
     return _run(sound, sr, s, track_decisions_native, _track_params, _track_table, "sg_analyze", device)
 
 
@@ -1554,17 +1589,26 @@ def analyze_batch(data, offsets, lengths, samplingRate, silence=0.04, windowLeng
                   specThres=0.3, specPeak=0.35, specSinglePeakCert=0.4, specHNRslope=0.8, specSmooth=150, specMerge=1,
                   shortestSyl=20, shortestPause=60, interpolWin=3, interpolTol=0.3, interpolCert=0.3, pathfinding="fast",
                   certWeight=.5, snakeStep=0.05, snakePlot=False, smooth=1, smoothVars=SMOOTH_VARS, plot=False,
-                  to_host=False, device=0):
+                  to_host=False, device=0, summary=False):
     """analyze(call i, samplingRate, ...) for a batch of sounds already in HBM, laid out
     and returned as pitch_candidates_batch() does (sg_analyze_batch, one launch sequence,
     tables left in HBM). A row has 15 + 6 nCands + 4 columns: `columns` names those of
     pitch_candidates_batch(), then pitch, amplVoiced, voiced (0 / 1) and harmonics. A
     call's table equals analyze()'s bit for bit. to_host=True returns the list of per-call
-    dicts analyze() returns."""
+    dicts analyze() returns.
+
+    summary=True (R/analyze.R:770-796, sg_analyze_summary_batch): sg_anl_summary follows in
+    the same launch sequence and the tables never leave HBM. Returns a dict with `out` (an
+    fp64 CUDA tensor of shape (n_calls, 44): row i is analyze(call i, summary=True) bit for
+    bit, whatever the batch and the call's place in it), `columns` (SUMMARY_COLUMNS) and
+    `frames`, and also the tables as above under `tables`, `offsets` and `cols`. A call
+    with no frames (not longer than the window, or a failed call of length < 0) has a row
+    of NaN. to_host=True then returns the list of per-call dicts of 44 named floats."""
     a = locals()
     s = repair_track(repair_pitch(samplingRate, None, **_pitch_args(a)), **_track_args(a))
     return _run_batch(data, offsets, lengths, samplingRate, s, _track_frames_native, _track_params, _track_table,
-                      ("autocorCand", "autocorCert") + PITCH_KEYS, "sg_analyze", to_host, device, TRACK_COLUMNS)
+                      ("autocorCand", "autocorCert") + PITCH_KEYS, "sg_analyze", to_host, device, TRACK_COLUMNS,
+                      summary=bool(summary))
 
 
 def pitch_path(table, step, samplingRate, pitchMethods=PITCH_DEFAULT_METHODS, pitchFloor=75, pitchCeiling=3500,
@@ -1600,3 +1644,159 @@ def pitch_path(table, step, samplingRate, pitchMethods=PITCH_DEFAULT_METHODS, pi
         t[k] = o[:, m.shape[1] + i].copy()
     t["voiced"] = t["voiced"] == 1
     return t
+
+
+# ------------------------------------------------- analyze(summary = TRUE), analyzeFolder()
+# vars (R/analyze.R:771-772) for the columns this table has: sort() of the column names (:706-707) under a
+# case-insensitive collation such as en_US, less `voiced`
+SUMMARY_VARS = ("ampl", "amplVoiced", "dom", "entropy", "harmonics", "HNR", "meanFreq", "peakFreq", "peakFreqCut", "pitch",
+                "quartile25", "quartile50", "quartile75", "specSlope")
+SUMMARY_COLUMNS = ("duration", "voiced") + tuple(v + "_" + k for v in SUMMARY_VARS for k in ("mean", "median", "sd"))
+
+
+def summarize_table_numpy(table):
+    """analyze()'s summary row (R/analyze.R:770-796) of an analyze()-shaped dict, restated
+    on the host: a dict of the 44 floats named by SUMMARY_COLUMNS. duration is
+    result$duration[1], in s (the reference's comment says ms; the value is not); voiced is
+    mean(result$voiced); then <var>_mean, <var>_median, <var>_sd over the frames where the
+    variable is not NA, in R's arithmetic (segment.py's r_mean, r_median, r_sd: NaN for no
+    value, sd NaN for fewer than two; +-Inf, which HNR and harmonics can hold, are ordinary
+    values: mean(c(Inf, 1)) is Inf, its sd NaN, its median finite).
+
+    The variables are those of `result` that this table has, in the order sort() gives their
+    names (:706-707) under a case-insensitive collation such as en_US; that order leaves
+    `voiced` last, so myseq (:787) is aligned with vars (:771-772). Under the C locale HNR
+    would come first: the names identify the cells, not the positions. The values are the
+    final table's (HNR and harmonics in dB, dom and pitch smoothed, the quartiles blanked
+    for unvoiced frames). Absent, with their columns: the pitchAutocor / pitchCep / pitchSpec
+    and the formant groups. domCand, domCert, the *Cand / *Cert groups and cond_* are not
+    columns of the reference's result and are not summarised. A table without frames (the
+    reference stops before it has one) gives 44 NaN."""
+    from .segment import r_mean, r_median, r_sd
+    out = dict.fromkeys(SUMMARY_COLUMNS, math.nan)                            # :773-785
+    frames = len(table["ampl"])
+    if frames == 0:
+        return out
+    out["duration"] = float(np.asarray(table["duration"], float)[0])          # :788
+    out["voiced"] = float(np.sum(np.asarray(table["voiced"]) != 0) / frames)  # :789
+    with np.errstate(invalid="ignore", over="ignore"):
+        for v in SUMMARY_VARS:                                                # :791-796
+            x = np.asarray(table[v], float)
+            x = x[~np.isnan(x)]                                               # na.rm = TRUE
+            out[v + "_mean"], out[v + "_median"], out[v + "_sd"] = r_mean(x), r_median(x), r_sd(x)
+    return out
+
+
+def _whole_ratio(duration):
+    """(len, samplingRate) as whole numbers with len / samplingRate == duration bit for bit:
+    what summarize_table() hands the kernel, which divides them, when it is not told the
+    rate. Exact for a duration that is a sample count over a whole rate up to 1e6 Hz."""
+    from fractions import Fraction
+    r = Fraction(float(duration)).limit_denominator(1000000)
+    if r.numerator / r.denominator != float(duration):
+        raise ValueError("summarize_table: the table's duration is not a sample count over a whole sampling rate; "
+                         "pass samplingRate")
+    return r.numerator, float(r.denominator)
+
+
+def summarize_table(table, device=0, samplingRate=None):
+    """summarize_table_numpy() on the GPU (sg_analyze_summary: sg_anl_summary alone, the
+    counterpart of pitch_path()): the summary row of an analyze()-shaped host dict (a
+    *Cand / *Cert group that is absent counts as all NaN; they are not summarised). The
+    kernel writes duration as length / samplingRate: with samplingRate the length is
+    round(duration * samplingRate); without it the two are the whole-number ratio that
+    gives table['duration'][0] back bit for bit."""
+    frames = len(table["ampl"])
+    ac = np.asarray(table["autocorCand"], float) if "autocorCand" in table else None
+    nC = ac.shape[1] if ac is not None and ac.ndim == 2 else 1
+    cols = NFIXED + 6 * nC + len(TRACK_COLUMNS)
+    m = np.full((frames, cols), math.nan)
+    for i, k in enumerate(COLUMNS):
+        if k in table:
+            m[:, i] = table[k]
+    for i, k in enumerate(("autocorCand", "autocorCert") + PITCH_KEYS):
+        if k in table:
+            m[:, NFIXED + i * nC:NFIXED + (i + 1) * nC] = np.reshape(table[k], (frames, nC))
+    for i, k in enumerate(TRACK_COLUMNS):
+        if k in table:
+            m[:, NFIXED + 6 * nC + i] = table[k]
+    if frames == 0:
+        length, sr = 0, 1.0 if samplingRate is None else float(samplingRate)
+    elif samplingRate is None:
+        length, sr = _whole_ratio(np.asarray(table["duration"], float)[0])
+    else:
+        length, sr = _path_length(table, samplingRate), float(samplingRate)
+    m = np.ascontiguousarray(m)
+    row = np.zeros(len(SUMMARY_COLUMNS))
+    ctx = native.default_context(device)
+    dp = C.POINTER(C.c_double)
+    _check(native.lib().sg_analyze_summary(ctx.ptr, m.ctypes.data_as(dp), frames, cols, nC, int(length), sr,
+                                           row.ctypes.data_as(dp)), ctx.ptr)
+    return dict(zip(SUMMARY_COLUMNS, (float(v) for v in row)))
+
+
+def summary_columns_native():
+    """The library's names of a summary row's cells (sg_analyze_summary_name; host only)."""
+    L = native.lib()
+    out = []
+    while True:
+        name = L.sg_analyze_summary_name(len(out))
+        if name is None:
+            return tuple(out)
+        out.append(name.decode())
+
+
+def analyze_folder(myfolder, verbose=True, samplingRate=None, silence=0.04, windowLength=50, step=None, overlap=50,
+                   wn="gaussian", zp=0, cutFreq=6000, nFormants=3, pitchMethods=PITCH_DEFAULT_METHODS, entropyThres=0.6,
+                   pitchFloor=75, pitchCeiling=3500, priorMean="default", priorSD=6, priorPlot=False, nCands=1,
+                   minVoicedCands="autom", domThres=0.1, domSmooth=220, autocorThres=0.7, autocorSmooth=None, cepThres=0.3,
+                   cepSmooth=None, cepZp=0, specThres=0.3, specPeak=0.35, specSinglePeakCert=0.4, specHNRslope=0.8,
+                   specSmooth=150, specMerge=1, shortestSyl=20, shortestPause=60, interpolWin=3, interpolTol=0.3,
+                   interpolCert=0.3, pathfinding="fast", annealPars=None, certWeight=.5, snakeStep=0.05, snakePlot=False,
+                   smooth=1, smoothVars=SMOOTH_VARS, summary=True, plot=False, savePath=None, specPlot=None, pitchPlot=None,
+                   candPlot=None, device=0):
+    """analyzeFolder() (R/analyze.R:831-930) on the GPU: analyze() for every .wav file of
+    myfolder, by default (summary=True) one summary row per sound.
+
+    The reference lists the folder with list.files(pattern = "*.wav"), a regular expression
+    and not a glob; what a leading * means there is the regex library's choice. Stated
+    difference: here the files are those whose names end in '.wav', in sorted() order of the
+    names (list.files sorts them by the locale's collation). Each file is read with the
+    module's WAV input (mono 16-bit PCM), the files are grouped by sampling rate (a batch
+    has one rate), each group is uploaded packed as float32 (exact for 16-bit PCM) and runs
+    through analyze_batch(), so the tables stay in HBM when only the rows are wanted.
+    samplingRate is not read for files, as in the reference.
+
+    summary=True: a list of dicts in file order, `sound` (the base name, :920-923) first,
+    then the 44 cells of SUMMARY_COLUMNS; a row equals analyze(path, summary=True) bit for
+    bit. summary=False: a dict from the file's full path (:926) to its analyze() table. As in
+    analyze_batch(), the two repairs that need a sound's duration are not made, and a file not
+    longer than the window gives a row of NaN (an empty table) where analyze() stops. verbose is
+    accepted and prints nothing; nFormants (formants are not built) and annealPars
+    (pathfinding = 'slow' raises) and the plot settings are accepted and not read; plot=True
+    and a savePath raise before any file is read."""
+    import os
+
+    import torch
+    a = locals()
+    if plot or priorPlot or snakePlot or savePath is not None:
+        raise NotImplementedError("analyze_folder(plot = TRUE / savePath): plotting is out of scope")
+    if pathfinding == "slow":
+        raise NotImplementedError(_SLOW)
+    kw = dict(_pitch_args(a), **_track_args(a))
+    names = sorted(n for n in os.listdir(myfolder) if n.endswith(".wav"))     # :895
+    paths = [os.path.join(myfolder, n) for n in names]
+    sounds = [_input(p, None) for p in paths]
+    results = [None] * len(paths)
+    for sr in sorted(set(r for _, r in sounds)):                              # :909-911, a group per rate
+        idx = [i for i, (_, r) in enumerate(sounds) if r == sr]
+        lens = np.array([len(sounds[i][0]) for i in idx], dtype=np.int64)
+        offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+        host = np.concatenate([sounds[i][0] for i in idx]).astype(np.float32)
+        data = torch.from_numpy(host).to("cuda:%d" % device)
+        got = analyze_batch(data, offs, lens, sr, to_host=True, device=device, summary=bool(summary), **kw)
+        for i, r in zip(idx, got):
+            results[i] = r
+    if summary:                                                               # :918-923
+        return [dict([("sound", n)] + list(r.items())) for n, r in zip(names, results)]
+    return dict(zip(paths, results))                                          # :925-926

@@ -510,3 +510,16 @@ extern "C" int sg_analyze_size(int64_t len, const sg_analyze_params_full* p, int
 }
 
 extern "C" const char* sg_analyze_frames_size_error(void) { return g_anl_err.c_str(); }
+
+// analyze(summary = TRUE): the cells of a row (R/analyze.R:777-784), the variables in sg::sum_column's order
+extern "C" const char* sg_analyze_summary_name(int32_t i) {
+  static const char* const vars[sg::kSumVars] = {"ampl",     "amplVoiced",  "dom",   "entropy",    "harmonics",  "HNR",        "meanFreq",
+                                                 "peakFreq", "peakFreqCut", "pitch", "quartile25", "quartile50", "quartile75", "specSlope"};
+  static const char* const stats[3] = {"_mean", "_median", "_sd"};
+  static_assert(SG_ANALYZE_SUMMARY_COLS == sg::kSumCols, "the header's row is sg_summary.h's");
+  thread_local std::string name;
+  if (i < 0 || i >= sg::kSumCols) return nullptr;
+  if (i < 2) return i ? "voiced" : "duration";
+  name = std::string(vars[(i - 2) / 3]) + stats[(i - 2) % 3];
+  return name.c_str();
+}

@@ -7,6 +7,7 @@
 
 #include "sg_path.h"
 #include "sg_spectrogram.h"
+#include "sg_summary.h"
 #include "soundgen_hip.h"
 
 namespace sg {
@@ -77,12 +78,26 @@ TrackSetup track_setup(const sg_analyze_params_full& p);
 // floor(smoothing_ww / 2) for a sound of len samples and `frames` frames (:671-673); SG_E_UNSUPPORTED above kPathMaxWin
 int track_hw(double smooth, double samplingRate, int64_t len, int frames);
 
+// analyze(summary = TRUE): a sound's table in the buffer sg_anl_summary reads (sg_summary.h)
+struct SumSound {
+  int64_t row0;  // first double of its table
+  int64_t len;   // samples (duration = len / samplingRate)
+  int32_t nf, pad;
+};
+// one row of kSumCols doubles per sound into d_summary (device), from finished tables of `cols` columns on the device;
+// kernel_ms (or nullptr): the device time of the kernel. Synchronises the stream.
+void summary_device(const std::vector<SumSound>& snds, int cols, double samplingRate, const double* d_tables,
+                    double* d_summary, hipStream_t s, double* kernel_ms);
+
 // pitch: nullptr for analyze_frames (S is then a plain AnlSetup), else S itself; track:
-// nullptr for analyze_frames and pitch_candidates, else S itself (then pitch is S too)
+// nullptr for analyze_frames and pitch_candidates, else S itself (then pitch is S too);
+// d_summary: nullptr, or (with track) n_calls x kSumCols doubles of device memory that sg_anl_summary fills in the
+// same launch sequence, its device time going to summary_ms
 template <typename T>
 void analyze_device(const AnlSetup& S, const T* d_x, const int64_t* offsets, const int64_t* lengths, int64_t n_calls,
                     double* d_out, const int64_t* out_off, int32_t* frames_out, hipStream_t s, double* kernel_ms,
-                    const PitchSetup* pitch = nullptr, const TrackSetup* track = nullptr);
+                    const PitchSetup* pitch = nullptr, const TrackSetup* track = nullptr, double* d_summary = nullptr,
+                    double* summary_ms = nullptr);
 // the path stage alone on n rows of P.cols doubles already on the device (sg_pitch_path)
 void path_device(const PathPars& P, int frames, int hw, double* d_rows, hipStream_t s, double* kernel_ms);
 

@@ -30,6 +30,10 @@
 //                 amplVoiced, the blanked quartiles, HNR in dB
 //   sg_anl_harm   one workgroup per frame with a pitch: the share of |X| above 1.25 *
 //                 pitch, in dB
+// and, where the caller asks for analyze(summary = TRUE) (R/analyze.R:770-796), behind them
+//   sg_anl_summary one 256-lane workgroup per sound (sg::sum_sound, sg_summary.h): duration,
+//                 the proportion of voiced frames, and the mean, median and sd of the 14
+//                 acoustic variables over their non-NA frames, from the finished table
 // Cumulative sums run in index order: a thread sums a contiguous run, one thread
 // folds the 256 run sums in order, and the runs are rescanned from their offsets,
 // so a frame's result does not depend on the launch it is in.
@@ -47,6 +51,7 @@
 #include "sg_launch.h"
 #include "sg_path.h"
 #include "sg_rmath.h"
+#include "sg_summary.h"
 
 namespace {
 
@@ -624,7 +629,21 @@ __global__ __launch_bounds__(kT) void sg_anl_harm(const AnlFrame* __restrict__ f
   if (threadIdx.x == 0) row[cols - sg::kPathCols + sg::kPathHarmonics] = sg::path_to_dB(above / all);
 }
 
+constexpr int kSumT = 256;
+static_assert(kSumT == sg::kSumSlots * sg::kSumMaxGroups, "sg::SumShared holds one cell per lane");
+
+// analyze(summary = TRUE) for one sound per workgroup (sg::sum_sound, sg_summary.h). A sound
+// without frames (not longer than the window, or a failed call) gets NaN.
+__global__ __launch_bounds__(kSumT) void sg_anl_summary(const sg::SumSound* __restrict__ snds, int cols, double samplingRate,
+                                                        const double* __restrict__ tables, double* __restrict__ out) {
+  __shared__ sg::SumShared sh;
+  const sg::SumSound S = snds[blockIdx.x];
+  sg::sum_sound(tables + S.row0, S.nf, cols, S.len, samplingRate, out + (int64_t)blockIdx.x * sg::kSumCols, (int)threadIdx.x,
+                kSumT, sh, WgSync());
+}
+
 double g_anl_ms[sg::kAnlStages];  // of the last profiled launch sequence
+double g_summary_ms[1];
 double g_pitch_ms[sg::kPitchStages];
 double g_track_ms[sg::kTrackStages];
 
@@ -632,16 +651,35 @@ double g_track_ms[sg::kTrackStages];
 
 namespace sg {
 
+void summary_device(const std::vector<SumSound>& snds, int cols, double samplingRate, const double* d_tables,
+                    double* d_summary, hipStream_t s, double* kernel_ms) {
+  StageClock clk(s, kernel_ms, 1);
+  clk.zero();
+  if (snds.empty()) return;
+  if (cols < kAnlFixed + 6 + kPathCols || (cols - kAnlFixed - kPathCols) % 6)
+    throw SgError(SG_E_DEVICE, "analyze: the summary's setup leaves the row");
+  DevBuf db;
+  const SumSound* d_ss = upload(db, snds, s);
+  clk.stamp();
+  hipLaunchKernelGGL(sg_anl_summary, dim3((unsigned)snds.size()), dim3(kSumT), 0, s, d_ss, cols, samplingRate, d_tables,
+                     d_summary);
+  HIPCHK(hipGetLastError());
+  clk.stamp();
+  HIPCHK(hipStreamSynchronize(s));
+  clk.finish();
+}
+
 template <typename T>
 void analyze_device(const AnlSetup& A, const T* d_x, const int64_t* offsets, const int64_t* lengths, int64_t n_calls,
                     double* d_out, const int64_t* out_off, int32_t* frames_out, hipStream_t s, double* kernel_ms,
-                    const PitchSetup* pitch, const TrackSetup* track) {
+                    const PitchSetup* pitch, const TrackSetup* track, double* d_summary, double* summary_ms) {
   const SpgSetup& P = A.spg;
   const int B = P.bins, wl = P.wl;
   std::vector<AnlSound> snds(n_calls);
   std::vector<AnlFrame> fr;
   std::vector<int64_t> lens(n_calls), zoff(n_calls);
   std::vector<PathSound> ps(track ? n_calls : 0);
+  std::vector<SumSound> ss(d_summary ? n_calls : 0);
   const int pstride = track ? path_stride(track->path.nCands) : 0;
   int64_t cells = 0;
   for (int64_t c = 0; c < n_calls; ++c) {
@@ -652,6 +690,7 @@ void analyze_device(const AnlSetup& A, const T* d_x, const int64_t* offsets, con
     frames_out[c] = nf;
     if (track)  // the smoothing window is refused before anything is launched
       ps[c] = PathSound{out_off[c], (int64_t)fr.size() * pstride, nf, track_hw(track->smooth, P.sr, lengths[c], nf)};
+    if (d_summary) ss[c] = SumSound{out_off[c], lengths[c], nf, 0};
     if ((int64_t)fr.size() + nf > 2147483647LL) throw SgError(SG_E_UNSUPPORTED, "analyze: the frames of one launch exceed 2^31");
     for (int f = 0; f < nf; ++f) {
       const int64_t o = spg_frame_start(P, lengths[c], f), a = anl_ampl_start(A, lengths[c], nf, f);
@@ -664,7 +703,11 @@ void analyze_device(const AnlSetup& A, const T* d_x, const int64_t* offsets, con
   StageClock clk(s, kernel_ms, track ? kTrackStages : pitch ? kPitchStages : kAnlStages);
   clk.zero();
   const int64_t F = (int64_t)fr.size();
-  if (F == 0) return;
+  if (d_summary && !track) throw SgError(SG_E_DEVICE, "analyze: the summary needs the tail's columns");
+  if (F == 0) {  // nothing to analyse; the summary rows are still written (NaN)
+    if (d_summary) summary_device(ss, A.cols, P.sr, d_out, d_summary, s, summary_ms);
+    return;
+  }
   if (A.rowLow < 1 || A.rowHigh > B || A.rowLow > A.rowHigh || A.cut0 < 0 || A.cut0 + A.ncut > B || A.lag0 < 0 ||
       A.lag0 + A.nlag > wl || B > kSpgMaxBins || A.nCands > kAnlMaxCands)
     throw SgError(SG_E_DEVICE, "analyze: the setup leaves the frame");
@@ -780,6 +823,11 @@ void analyze_device(const AnlSetup& A, const T* d_x, const int64_t* offsets, con
       HIPCHK(hipGetLastError());
       clk.stamp();
     }
+  }
+  if (d_summary) {  // on the same stream behind sg_anl_harm; it synchronises
+    summary_device(ss, A.cols, P.sr, d_out, d_summary, s, summary_ms);
+    clk.finish();
+    return;
   }
   HIPCHK(hipStreamSynchronize(s));
   clk.finish();
@@ -929,6 +977,71 @@ int sg_pitch_path(sg_ctx* ctx, const double* table, int32_t frames, int64_t len,
     HIPCHK(hipMemcpy(out, d_rows, (size_t)frames * P.cols * sizeof(double), hipMemcpyDeviceToHost));
     return (int)SG_OK;
   });
+}
+
+int sg_analyze_summary(sg_ctx* ctx, const double* table, int32_t frames, int32_t cols, int32_t nCands, int64_t len,
+                       double samplingRate, double* out) {
+  return guarded(ctx, [&]() {
+    if (!ctx || !out || frames < 0 || (frames > 0 && !table)) throw sg::SgError(SG_E_ARG, "sg_analyze_summary: bad arguments");
+    if (nCands < 1 || nCands > sg::kAnlMaxCands || cols != sg::kAnlFixed + 6 * nCands + sg::kPathCols)
+      throw sg::SgError(SG_E_ARG, "sg_analyze_summary: a row has 15 + 6 nCands + 4 columns, nCands in 1..8");
+    if (!(samplingRate > 0)) throw sg::SgError(SG_E_ARG, "sg_analyze_summary: samplingRate must be positive");
+    HIPCHK(hipSetDevice(ctx->device));
+    sg::DevBuf db;
+    const double* d_rows = frames > 0 ? sg::upload_sound(db, table, (int64_t)frames * cols, ctx->stream) : db.get<double>(1);
+    double* d_sum = db.get<double>(sg::kSumCols);
+    // a failed call (len < 0) has no table: NaN, as in a batch
+    const std::vector<sg::SumSound> one(1, sg::SumSound{0, len, len < 0 ? 0 : frames, 0});
+    sg::summary_device(one, cols, samplingRate, d_rows, d_sum, ctx->stream, ctx->profiling ? g_summary_ms : nullptr);
+    HIPCHK(hipMemcpy(out, d_sum, sg::kSumCols * sizeof(double), hipMemcpyDeviceToHost));
+    return (int)SG_OK;
+  });
+}
+
+int sg_analyze_summary_batch(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, const int64_t* lengths,
+                             int64_t n_calls, const sg_analyze_params_full* p, double* d_tables, const int64_t* out_off,
+                             int32_t* frames_out, double* d_summary) {
+  return guarded(ctx, [&]() {
+    if (!ctx || !p || n_calls < 0 || n_calls > 2147483647LL ||
+        (n_calls > 0 && (!d_wave || !offsets || !lengths || !d_tables || !out_off || !frames_out || !d_summary)))
+      throw sg::SgError(SG_E_ARG, "sg_analyze_summary_batch: bad arguments");
+    const sg::TrackSetup S = sg::track_setup(*p);
+    if (n_calls == 0) return (int)SG_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    sg::analyze_device<float>(S, d_wave, offsets, lengths, n_calls, d_tables, out_off, frames_out, ctx->stream,
+                              ctx->profiling ? g_track_ms : nullptr, &S, &S, d_summary,
+                              ctx->profiling ? g_summary_ms : nullptr);
+    return (int)SG_OK;
+  });
+}
+
+int sg_analyze_summary_sound(sg_ctx* ctx, const double* wave, int64_t len, const sg_analyze_params_full* p, double* out,
+                             double* summary) {
+  return guarded(ctx, [&]() {
+    if (!ctx || !p || !wave || !summary) throw sg::SgError(SG_E_ARG, "sg_analyze_summary_sound: bad arguments");
+    const sg::TrackSetup S = sg::track_setup(*p);
+    if (len <= S.spg.wl)
+      throw sg::SgError(SG_E_ARG, "sg_analyze_summary_sound: the sound is not longer than the window (the reference's "
+                                  "amplitude window sound[a:(a + wl)] leaves it)");
+    HIPCHK(hipSetDevice(ctx->device));
+    const int64_t cells = (int64_t)sg::anl_frames(S, len) * S.cols, off = 0;
+    sg::DevBuf db;
+    const double* d = sg::upload_sound(db, wave, len, ctx->stream);
+    double* d_o = db.get<double>((size_t)cells);
+    double* d_sum = db.get<double>(sg::kSumCols);
+    int32_t f = 0;
+    sg::analyze_device<double>(S, d, &off, &len, 1, d_o, &off, &f, ctx->stream, ctx->profiling ? g_track_ms : nullptr, &S, &S,
+                               d_sum, ctx->profiling ? g_summary_ms : nullptr);
+    if (out) HIPCHK(hipMemcpy(out, d_o, (size_t)cells * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(summary, d_sum, sg::kSumCols * sizeof(double), hipMemcpyDeviceToHost));
+    return (int)SG_OK;
+  });
+}
+
+int sg_debug_summary_kernel_ms(double* out) {
+  if (!out) return SG_E_ARG;
+  out[0] = g_summary_ms[0];
+  return SG_OK;
 }
 
 int sg_debug_track_kernel_ms(double* out) {

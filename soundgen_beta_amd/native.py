@@ -142,6 +142,15 @@ def lib():
         L.sg_analyze_batch.argtypes = [vp, vp, i64p, i64p, i64, fpp, vp, i64p, i32p]
         L.sg_pitch_path.argtypes = [vp, dp, C.c_int32, i64, fpp, dp]
         L.sg_debug_track_kernel_ms.argtypes = [dp]
+    if hasattr(L, "sg_analyze_summary"):  # analyze(summary = TRUE): likewise additive
+        i32p = C.POINTER(C.c_int32)
+        fpp = C.POINTER(_abi.sg_analyze_params_full)
+        L.sg_analyze_summary_name.argtypes = [C.c_int32]
+        L.sg_analyze_summary_name.restype = C.c_char_p
+        L.sg_analyze_summary.argtypes = [vp, dp, C.c_int32, C.c_int32, C.c_int32, i64, C.c_double, dp]
+        L.sg_analyze_summary_batch.argtypes = [vp, vp, i64p, i64p, i64, fpp, vp, i64p, i32p, vp]
+        L.sg_analyze_summary_sound.argtypes = [vp, dp, i64, fpp, dp, dp]
+        L.sg_debug_summary_kernel_ms.argtypes = [dp]
     if hasattr(L, "sg_segment_size"):  # segment(): likewise additive
         i32p = C.POINTER(C.c_int32)
         gpp = C.POINTER(_abi.sg_segment_params)
