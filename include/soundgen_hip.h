@@ -848,6 +848,14 @@ double sg_noise_threshold(int32_t which, double nonlinBalance);
  * SG_E_UNSUPPORTED if wl is not on that path. */
 int sg_debug_wave_fft(sg_ctx* ctx, int32_t wl, int32_t inverse, int32_t nframes,
                       const float* in, float* out);
+/* Test hook, no reference counterpart: the fp64 transform under spectrogram(),
+ * analyze()'s frames and cepstrum, segment() and the fp64 formant-filter frames
+ * (fft64, sg_fft64_dev.h), alone: out = DFT(in) of nframes frames of M complex
+ * points (host, interleaved re, im), unscaled; inverse != 0 uses
+ * exp(+2 pi i nk / M). SG_E_UNSUPPORTED, checked before anything else (ctx may be
+ * NULL then, out is left alone), for M < 1, M > 2048 or M not 31-smooth. */
+int sg_debug_fft64(sg_ctx* ctx, int32_t M, int32_t inverse, int32_t nframes,
+                   const double* in, double* out);
 /* Test hook, no reference counterpart: the tile map of ssm()'s Gram kernel
  * (sg_ssm_gram, one wavefront per 16 x 16 tile on the fp64 matrix pipe). feat
  * holds n vectors of L doubles one after another (host); out (host, n * n

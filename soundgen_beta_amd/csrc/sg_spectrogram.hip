@@ -165,6 +165,22 @@ __global__ __launch_bounds__(kT) void sg_spg_roots(double2* __restrict__ TN, int
   if (t < N) TN[t] = root64(t, N);
 }
 
+// Test hook (sg_debug_fft64): fft64 alone, one workgroup per frame of M complex
+// points, unscaled. LDS as sg_spg_frames: two M-point buffers and the 32 radix roots.
+__global__ __launch_bounds__(kT) void sg_fft64_probe(const double2* __restrict__ in, const double2* __restrict__ TN,
+                                                     int M, int inv, double2* __restrict__ out) {
+  extern __shared__ double2 lds64[];
+  double2* a = lds64;
+  double2* b = a + M;
+  double2* rt = b + M;
+  const double2* x = in + (int64_t)blockIdx.x * M;
+  for (int n = threadIdx.x; n < M; n += kT) a[n] = x[n];
+  __syncthreads();
+  fft64(a, b, M, TN, rt, inv != 0);
+  double2* y = out + (int64_t)blockIdx.x * M;
+  for (int k = threadIdx.x; k < M; k += kT) y[k] = a[k];
+}
+
 // |X_k|, k < M = N / 2, of every frame: N = wl + 2 pad points, the wl windowed
 // samples in the middle. LDS: two M-point buffers and fft64's 32 radix roots.
 template <typename T>
@@ -672,6 +688,40 @@ int sg_spectrogram_batch(sg_ctx* ctx, const float* d_wave, const int64_t* offset
     HIPCHK(hipSetDevice(ctx->device));
     sg::spectrogram_device<float>(S, d_wave, offsets, lengths, n_calls, d_out, out_off, bins_out, frames_out,
                                   ctx->stream, ctx->profiling ? g_spg_ms : nullptr);
+    return SG_OK;
+  });
+}
+
+// Test hook (not part of the reference surface): fft64 on nframes frames of M complex
+// points from host memory. The refusals come first and need no context.
+int sg_debug_fft64(sg_ctx* ctx, int32_t M, int32_t inverse, int32_t nframes, const double* in, double* out) {
+  return guarded(ctx, [&]() {
+    int rest = M < 1 || M > sg::kSpgMaxBins ? 0 : M;
+    for (int p : {2, 3, 5, 7, 11, 13, 17, 19, 23, 29, 31})
+      while (rest > 1 && rest % p == 0) rest /= p;
+    if (rest != 1)
+      throw sg::SgError(SG_E_UNSUPPORTED, "sg_debug_fft64: M must be 31-smooth and in 1.." +
+                                              std::to_string(sg::kSpgMaxBins));
+    if (!ctx || !in || !out || nframes < 0) throw sg::SgError(SG_E_ARG, "sg_debug_fft64: bad arguments");
+    if (nframes == 0) return SG_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const size_t n = (size_t)nframes * M;
+    DevBuf db;
+    double2* d_in = db.get<double2>(n);
+    double2* d_out = db.get<double2>(n);
+    double2* d_TN = db.get<double2>((size_t)2 * M);
+    HIPCHK(hipMemcpyAsync(d_in, in, n * sizeof(double2), hipMemcpyHostToDevice, s));
+    sg::fill_roots64(d_TN, 2 * M, s);
+    const int lds = (2 * M + 32) * (int)sizeof(double2);
+    if (lds > 48 * 1024)
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&sg_fft64_probe),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    hipLaunchKernelGGL(sg_fft64_probe, dim3((unsigned)nframes), dim3(kT), (size_t)lds, s, d_in, d_TN, (int)M,
+                       (int)inverse, d_out);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipMemcpy(out, d_out, n * sizeof(double2), hipMemcpyDeviceToHost));
     return SG_OK;
   });
 }

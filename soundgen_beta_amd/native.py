@@ -116,6 +116,8 @@ def lib():
         L.sg_spectrogram.argtypes = [vp, dp, i64, spp, dp]
         L.sg_spectrogram_batch.argtypes = [vp, vp, i64p, i64p, i64, spp, vp, i64p, i32p, i32p]
         L.sg_debug_spectrogram_kernel_ms.argtypes = [dp]
+    if hasattr(L, "sg_debug_fft64"):  # the fp64 transform alone (tests/test_fft64.py): likewise additive
+        L.sg_debug_fft64.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, dp, dp]
     if hasattr(L, "sg_analyze_frames_size"):  # analyze()'s per-frame stage: likewise additive
         i32p = C.POINTER(C.c_int32)
         app = C.POINTER(_abi.sg_analyze_params)

@@ -222,6 +222,50 @@ def test_c5_every_preset_vs_oracle(oracle, policy):
     print(sorted(worst.items(), key=lambda kv: -kv[1])[:6])
 
 
+# (samplingRate, windowLength in ms, M): windowLength_points = 2 floor(windowLength / 1000 * sr / 2)
+# (R/soundgen.R:317) = 2 M with M = 7 x 11 x 13, 23 x 31 and 2 x 3 x 11 x 31 (above the default LDS)
+FP64_WINDOWS = [(16000, 125.2, 1001), (16000, 89.2, 713), (44100, 92.8, 2046)]
+
+
+@pytest.mark.parametrize("sr,wlen,M", FP64_WINDOWS, ids=["M%d" % c[2] for c in FP64_WINDOWS])
+def test_fp64_frames_at_odd_radix_windows(oracle, sr, wlen, M):
+    """One-bout calls on the fp64 filter path (policy 2) whose window's half holds the radices
+    7, 11, 13, 23, 31: sg_fft_frames64's packing, forward and inverse transform at these sizes,
+    with the noise filtered with the voiced part and on its own (formantsNoise). The arithmetic
+    itself is held to fp64 round-off by tests/test_fft64.py; here the project's waveform bar."""
+    import math
+    from soundgen_beta_amd import batch, native
+    assert int(math.floor(wlen / 1000 * sr / 2)) == M and 2 * M != 2204
+    base = dict(sylLen=300, samplingRate=sr, windowLength=wlen, temperature=0, addSilence=0, pitchAnchors=[300, 350],
+                formants="a", noiseAnchors={"time": [0, 300], "value": [-20, -20]})
+    # formantsNoise = "i": the noise is filtered on its own and stays fp32, so only the filter's
+    # frames (forward and inverse) are fp64; without it the noise frames (inverse only) are too
+    cases = [base, dict(base, formantsNoise="i")]
+    calls = [{"kind": "soundgen", "args": a, "normals": N, "uniforms": U} for a in cases]
+    L = native.lib()
+    assert L.sg_set_fp64_policy(2, native.HP_RHO_DEFAULT) == 0
+    try:
+        nfr = []
+        for c in calls:
+            plan = batch.Plan([c], None)
+            assert plan.status[0] == 0, plan.message(0)
+            hp, frames64, _ = plan.precision()
+            assert hp[0] > 0
+            nfr.append(frames64)
+        outs = batch.synthesize(calls)
+    finally:
+        L.sg_set_fp64_policy(1, native.HP_RHO_DEFAULT)
+    assert nfr[0] > nfr[1] > 0, nfr  # filter and noise frames; filter frames alone
+    for a, y, nf in zip(cases, outs, nfr):
+        assert not isinstance(y, Exception), y
+        ref = oracle.soundgen(normals=N, uniforms=U, **a)
+        assert len(ref) >= 4 * M  # the window is not shrunk to floor(L / 2) (R/soundgen.R:743)
+        assert len(y) == len(ref), (M, "formantsNoise" in a)
+        r = _rms(y, ref)
+        print("fp64 frames M %d formantsNoise %s: rms %.3g, %d fp64 frames" % (M, "formantsNoise" in a, r, nf))
+        assert r <= TOL, (M, "formantsNoise" in a, r)
+
+
 def test_c3_all_vowels_vs_oracle(oracle):
     """C3: 36 calls of bench.c3_calls(1024) covering all six vowels
     a/o/i/e/u/0 (R/presets.R:176-212), 2 s at 44.1 kHz with breathing noise,

@@ -416,6 +416,15 @@ CASES = [
     (16000, "cep", dict(pitchMethods=("cep",))),
     (16000, "spec", dict(pitchMethods=("spec",))),
     (16000, "reference-default", dict()),  # analyze()'s own default: autocor, spec, dom
+    # cepstrum lengths the planner accepts whose radices (7, 11, 13, 17) and LDS sizes no case above launches
+    (22050, "cepZp609", dict(pitchMethods=("cep",), cepZp=609)),  # L = 609, odd: complex 3 x 7 x 29
+    (22050, "cepZp551", dict(pitchMethods=("cep",), cepZp=551)),  # cepZp = B: the padded branch with no zeros, L = 551
+    (16000, "cepZp551", dict(pitchMethods=("cep",), cepZp=551)),  # L = 550: packed, M = 275 = 5 x 5 x 11
+    (16000, "cepZp1225", dict(pitchMethods=("cep",), cepZp=1225, cepSmooth=1)),  # L = 1224, M = 612 = 4 x 3 x 3 x 17
+    (16000, "wl38.5", dict(pitchMethods=("cep",), windowLength=38.5)),  # B = 308 = 4 x 7 x 11 in the frames, cepstrum M = 154
+    (16000, "wl35.75", dict(pitchMethods=("cep",), windowLength=35.75)),  # B = 286, cepstrum M = 143 = 11 x 13
+    (32000, "cepZp4096", dict(pitchMethods=("cep",), cepZp=4096)),  # L = 4096, M = 2048: 82 KB of LDS
+    (22050, "cepZp1875", dict(pitchMethods=("cep",), cepZp=1875)),  # L = 1875, odd: complex 3 x 5^4, 68 KB
 ]
 SEEDS = {(44100, "defaults"): 2}  # seed 1 leaves a margin of 4.5e-7 there
 IDS = ["%d-%s" % (c[0], c[1]) for c in CASES]
@@ -510,6 +519,22 @@ def test_pitch_inputs_have_frames_of_every_class():
     assert np.all(np.isnan(ref["specCand"])) and np.all(np.isnan(ref["HNR"])) and np.all(np.isnan(ref["dom"]))
     ref, _ = by["16000-reference-default"]
     assert np.all(np.isnan(ref["cepCand"])) and (~np.isnan(ref["specCand"])).any() and (~np.isnan(ref["HNR"])).any()
+
+
+CEP_LENGTHS = {"22050-cepZp609": 609, "22050-cepZp551": 551, "16000-cepZp551": 550, "16000-cepZp1225": 1224,
+               "16000-wl38.5": 308, "16000-wl35.75": 286, "32000-cepZp4096": 4096, "22050-cepZp1875": 1875}
+
+
+def test_cep_cases_reach_their_transforms():
+    """The cases added for the cepstrum's transform make the library decide the length their
+    comments name, and have frames to compare: >= 12 tracked, >= 10 with a cepstral candidate."""
+    for i, (sr, name, kw) in enumerate(CASES):
+        if IDS[i] not in CEP_LENGTHS:
+            continue
+        d = AN.pitch_decisions_native(int(0.6 * sr), AN.repair_pitch(sr, **kw))
+        assert d["cepL"] == CEP_LENGTHS[IDS[i]], IDS[i]
+        ref, p = _reference(i)
+        assert len(p["cep"]) >= 12 and (~np.isnan(ref["cepCand"][:, 0])).sum() >= 10, IDS[i]
 
 
 def test_pitch_candidates_numpy_equals_analyze_frames_numpy_on_shared_keys():

@@ -411,6 +411,44 @@ def test_spectrogram_scale_branch_gpu():
         assert e <= TOL_PLAIN
 
 
+# Frames whose half holds the radices no case above runs (7, 11, 13, 17, 23, 31), at the
+# transform's own accuracy: tests/test_fft64.py derives TOL64; the frame kernel adds the
+# untangling of the packed real transform (one more radix-2 stage in the sum) and the
+# fp64 reference (numpy's FFT of the N-point frame) its own 2 * 2^-52.
+FFT64_CASES = [("zp2002", dict(zp=2002), 1001), ("zp1426", dict(zp=1426), 713), ("zp3844", dict(zp=3844), 1922),
+               ("zp4046", dict(zp=4046), 2023), ("zp4092", dict(zp=4092), 2046),
+               ("wl9.625", dict(windowLength=9.625), 77)]
+
+
+@lru_cache(maxsize=None)
+def _short_signal():
+    x = _signal(16000, dur=0.15)
+    x.setflags(write=False)
+    return x
+
+
+@pytest.mark.parametrize("name,kw,M", FFT64_CASES, ids=[c[0] for c in FFT64_CASES])
+def test_fft64_cases_reach_their_sizes(name, kw, M):
+    from test_fft64 import stages
+    wl, N, bins, frames = SP.spectrogram_size(len(_short_signal()), 16000, **kw)
+    assert (N, bins) == (2 * M, M) and 4 <= frames <= 64
+    assert set(stages(M)) & {7, 11, 13, 17, 23, 31}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,kw,M", FFT64_CASES, ids=[c[0] for c in FFT64_CASES])
+def test_spectrogram_original_at_fft64_accuracy(name, kw, M):
+    from test_fft64 import tol64
+    x = _short_signal()
+    want = SP.spectrogram_numpy(x, 16000, output="original", **kw)
+    got = SP.spectrogram(x, 16000, output="original", **kw)
+    assert got.shape == want.shape == (M, want.shape[1]) and not np.isnan(got).any()
+    e = np.linalg.norm(got - want, axis=0) / np.linalg.norm(want, axis=0)
+    tol = tol64(M, extra=(2,)) + 2 * 2.0 ** -52
+    print("spectrogram original %s: M %d, %d frames, worst frame %.3g, bound %.3g" % (name, M, len(e), e.max(), tol))
+    assert (e <= tol).all(), (name, float(e.max()), tol)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("kw", [dict(smoothFreq=3), dict(smoothFreq=7), dict(smoothTime=3), dict(smoothTime=399)],
                          ids=["freq3", "freq7", "time3", "time399"])
