@@ -734,6 +734,32 @@ int sg_segment(sg_ctx* ctx, const double* wave, int64_t len, const sg_segment_pa
  * refused. */
 int sg_segment_batch(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, const int64_t* lengths, int64_t n_calls,
                      const sg_segment_params* p, double* d_out, const int64_t* out_off);
+/* A parameter sweep of segment(summary = TRUE) (an additive extension of ABI 5; what
+ * optimizePars() evaluates, R/optimize.R:206-234): n_rows parameter rows over n_calls sounds
+ * laid out as for sg_segment_batch. d_out (device memory): n_rows x n_calls x 11 doubles, the
+ * summary row (cells 8 .. 18 of sg_segment_size's layout, NaN for NA) of sound c under
+ * rows[r] at (r * n_calls + c) * 11; a sound of fewer than three samples has nSyl = nBursts
+ * = 0 and NaN elsewhere. samplingRate, mode (0) and workspace_cap are those of rows[0]; a
+ * row that differs in one of them is SG_E_ARG. The raw envelope is computed once per sound,
+ * the smoothed one once per sound and (windowLength, clamped overlap), and all pairs of a
+ * chunk of rows run in one launch; workspace_cap also bounds the bytes of the tables one such
+ * chunk keeps (at least one row runs). A pair's eleven cells are sg_segment_batch's bit for
+ * bit, whatever rows and sounds share the sweep and whatever the cap. A row refused for any
+ * sound refuses the sweep before anything is launched; the text names the row and the sound. */
+int sg_segment_sweep(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, const int64_t* lengths, int64_t n_calls,
+                     const sg_segment_params* rows, int64_t n_rows, double* d_out);
+/* 1 - cor(x, key, use = 'pairwise.complete.obs') per row of a device matrix of n_rows x
+ * n_calls x width doubles (width 11: sg_segment_sweep's; 44: sg_analyze_summary_batch's, one
+ * row), x = column `column` of the row's n_calls sounds; key: n_calls doubles of host
+ * memory; NaN = NA on either side (the pair is dropped). fit: n_rows doubles of host memory;
+ * NaN for fewer than two complete pairs or a side whose values are all equal (R: NA). A
+ * row's value does not depend on the other rows. */
+int sg_sweep_fitness(sg_ctx* ctx, const double* d_matrix, int64_t n_rows, int64_t n_calls, int32_t width, int32_t column,
+                     const double* key, double* fit);
+/* Process-wide: whether sg_segment_sweep's tail copies a pair's envelope to LDS first (1,
+ * the default; an envelope of more than 8192 values is read in place either way) or reads
+ * it in place (0). The results are the same bit for bit; for measurements. */
+int sg_set_sweep_staging(int32_t mode);
 /* Process-wide policy of the fp64 filter path for later sg_plan_batch calls:
  * mode 0 never, 1 when the conditioning estimate exceeds rho (default 100),
  * 2 every filtered bout. SG_E_ARG for an invalid mode or rho. */
@@ -897,6 +923,9 @@ int sg_debug_summary_kernel_ms(double* out);
  * multiplier, inverse, twiddle), the inverse columns with Mod and the un-padding, the
  * smoothing, and the tail (syllables, bursts, summary) (6 doubles). */
 int sg_debug_segment_kernel_ms(double* out);
+/* The same six stages for the last sg_segment_sweep: the first four once per sound, the
+ * smoothing summed over the envelope groups, the tail summed over the chunks of rows. */
+int sg_debug_sweep_kernel_ms(double* out);
 
 #ifdef __cplusplus
 }

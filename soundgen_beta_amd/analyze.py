@@ -1746,6 +1746,28 @@ def summary_columns_native():
         out.append(name.decode())
 
 
+def folder_groups(myfolder, device=0):
+    """The sounds of a folder on the device, as analyze_folder() documents it: (names, paths,
+    groups). names: the files that end in '.wav', sorted; groups: one dict per sampling rate,
+    in ascending order of the rates, with `samplingRate`, `files` (indices into names),
+    `offsets`, `lengths` and `data` (the group's samples packed as a float32 CUDA tensor)."""
+    import os
+
+    import torch
+    names = sorted(n for n in os.listdir(myfolder) if n.endswith(".wav"))     # :895
+    paths = [os.path.join(myfolder, n) for n in names]
+    sounds = [_input(p, None) for p in paths]
+    groups = []
+    for sr in sorted(set(r for _, r in sounds)):                              # :909-911, a group per rate
+        idx = [i for i, (_, r) in enumerate(sounds) if r == sr]
+        lens = np.array([len(sounds[i][0]) for i in idx], dtype=np.int64)
+        offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+        host = np.concatenate([sounds[i][0] for i in idx]).astype(np.float32)
+        data = torch.from_numpy(host).to("cuda:%d" % device)
+        groups.append(dict(samplingRate=sr, files=idx, offsets=offs, lengths=lens, data=data))
+    return names, paths, groups
+
+
 def analyze_folder(myfolder, verbose=True, samplingRate=None, silence=0.04, windowLength=50, step=None, overlap=50,
                    wn="gaussian", zp=0, cutFreq=6000, nFormants=3, pitchMethods=PITCH_DEFAULT_METHODS, entropyThres=0.6,
                    pitchFloor=75, pitchCeiling=3500, priorMean="default", priorSD=6, priorPlot=False, nCands=1,
@@ -1775,27 +1797,18 @@ def analyze_folder(myfolder, verbose=True, samplingRate=None, silence=0.04, wind
     accepted and prints nothing; nFormants (formants are not built) and annealPars
     (pathfinding = 'slow' raises) and the plot settings are accepted and not read; plot=True
     and a savePath raise before any file is read."""
-    import os
-
-    import torch
     a = locals()
     if plot or priorPlot or snakePlot or savePath is not None:
         raise NotImplementedError("analyze_folder(plot = TRUE / savePath): plotting is out of scope")
     if pathfinding == "slow":
         raise NotImplementedError(_SLOW)
     kw = dict(_pitch_args(a), **_track_args(a))
-    names = sorted(n for n in os.listdir(myfolder) if n.endswith(".wav"))     # :895
-    paths = [os.path.join(myfolder, n) for n in names]
-    sounds = [_input(p, None) for p in paths]
+    names, paths, groups = folder_groups(myfolder, device)
     results = [None] * len(paths)
-    for sr in sorted(set(r for _, r in sounds)):                              # :909-911, a group per rate
-        idx = [i for i, (_, r) in enumerate(sounds) if r == sr]
-        lens = np.array([len(sounds[i][0]) for i in idx], dtype=np.int64)
-        offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
-        host = np.concatenate([sounds[i][0] for i in idx]).astype(np.float32)
-        data = torch.from_numpy(host).to("cuda:%d" % device)
-        got = analyze_batch(data, offs, lens, sr, to_host=True, device=device, summary=bool(summary), **kw)
-        for i, r in zip(idx, got):
+    for g in groups:
+        got = analyze_batch(g["data"], g["offsets"], g["lengths"], g["samplingRate"], to_host=True, device=device,
+                            summary=bool(summary), **kw)
+        for i, r in zip(g["files"], got):
             results[i] = r
     if summary:                                                               # :918-923
         return [dict([("sound", n)] + list(r.items())) for n, r in zip(names, results)]

@@ -65,7 +65,7 @@ SegPlan seg_plan(const sg_segment_params& p, int64_t len, bool windows) {
   S.m = (int64_t)step.size();
   if (S.m < 1 || S.m > 2147483647LL) throw SgError(SG_E_ARG, "segment: no smoothing window");
   S.timestep = 1000 / p.samplingRate * ((double)len / (double)S.m);
-  S.minCount = (int64_t)std::fmin(std::ceil(p.shortestSyl / S.timestep), 4e18);
+  S.minCount = seg_min_count(p.shortestSyl, S.timestep);
   for (int64_t i = 0; i < S.m; ++i) {
     const double x = step[i], to = x + wl;
     const int64_t cnt = (int64_t)(std::fabs(to - x) + 1 + (double)FLT_EPSILON);  // length of from:to (seq_colon)

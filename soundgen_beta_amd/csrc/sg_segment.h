@@ -53,6 +53,19 @@ SG_SEG_HD inline int64_t seg_bur0(int64_t m) { return seg_syl0(m) + 5 * seg_max_
 SG_SEG_HD inline int64_t seg_scr0(int64_t m) { return seg_bur0(m) + 3 * m; }
 SG_SEG_HD inline int64_t seg_cells(int64_t m) { return seg_scr0(m) + m; }
 
+// A (sound, parameter row) pair of a sweep keeps the head, the two tables and the scratch,
+// not the envelope and not the summary row (that one goes to the sweep's output)
+SG_SEG_HD inline int64_t seg_pair_syl0() { return kSegHead; }
+SG_SEG_HD inline int64_t seg_pair_bur0(int64_t m) { return seg_pair_syl0() + 5 * seg_max_syl(m); }
+SG_SEG_HD inline int64_t seg_pair_scr0(int64_t m) { return seg_pair_bur0(m) + 3 * m; }
+SG_SEG_HD inline int64_t seg_pair_cells(int64_t m) { return seg_pair_scr0(m) + m; }
+
+// findSyllables' shortest run, ceiling(shortestSyl / timestep): the planner's statement and
+// the sweep's, which makes it per pair on the device
+SG_SEG_HD inline int64_t seg_min_count(double shortestSyl, double timestep) {
+  return (int64_t)fmin(ceil(shortestSyl / timestep), 4e18);
+}
+
 // What every sound of a launch shares; timestep and the shortest run come per sound
 struct SegPars {
   double sylThres, shortestSyl;
@@ -63,6 +76,16 @@ struct SegPars {
 };
 
 SG_SEG_HD inline bool seg_isnan(double v) { return v != v; }
+
+// v as it is rounded, for a product that must not fuse with the sum behind it: the library is
+// built with -ffp-contract=fast, under which the device compiler fuses across the contract(off)
+// pragmas below. The empty statement holds no instruction; the compiler cannot see through it.
+SG_SEG_HD inline double seg_rounded(double v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "+v"(v));
+#endif
+  return v;
+}
 
 // v[0 .. n) ascending (heapsort: no recursion, no memory)
 SG_SEG_HD inline void seg_sort(double* v, int64_t n) {
@@ -142,7 +165,7 @@ SG_SEG_HD inline int64_t seg_syllables(const double* env, int64_t m, double thr,
       double start = (double)(i == 0 ? count : i) * timestep;
       if (rows == 0 && begins_above) start = 0;  // syllables$start[1] = 0: the first KEPT one
       syl[5 * rows + 1] = start;
-      syl[5 * rows + 2] = start + (double)count * timestep;
+      syl[5 * rows + 2] = start + seg_rounded((double)count * timestep);
       ++rows;
     }
     i = j;
@@ -203,14 +226,17 @@ SG_SEG_HD inline bool seg_is_burst(const double* env, int64_t m, int64_t n, int6
   return true;
 }
 
-// One sound: o = its cells with the envelope in place. red: nl doubles shared by the lanes.
+// One sound whose envelope (m values at env) lies apart from what is written: o = the
+// kSegHead head cells, sum = the summary row, syl / bur / scr = the tables and the scratch
+// with the room the layout above gives them. red: nl doubles shared by the lanes. A parameter
+// sweep (sg_seg_sweep_tail) reads one envelope for many parameter rows this way.
 template <class Sync>
-SG_SEG_HD inline void seg_sound(const SegPars& P, double timestep, int64_t minCount, int64_t m, double* o, int lane,
-                                int nl, double* red, Sync sync) {
+SG_SEG_HD inline void seg_sound_at(const SegPars& P, double timestep, int64_t minCount, int64_t m, const double* env,
+                                   double* o, double* sum, double* syl, double* bur, double* scr, int lane, int nl,
+                                   double* red, Sync sync) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
-  double* sum = o + kSegHead;
   if (m <= 0) {  // a sound the reference stops on: nothing but the counts
     if (lane == 0) {
       for (int k = 0; k < kSegHead; ++k) o[k] = 0;
@@ -219,10 +245,6 @@ SG_SEG_HD inline void seg_sound(const SegPars& P, double timestep, int64_t minCo
     }
     return;
   }
-  const double* env = o + seg_env0();
-  double* syl = o + seg_syl0(m);
-  double* bur = o + seg_bur0(m);
-  double* scr = o + seg_scr0(m);
   double s = 0, mx = -INFINITY;
   for (int64_t i = lane; i < m; i += nl) {
     s += env[i];
@@ -281,6 +303,15 @@ SG_SEG_HD inline void seg_sound(const SegPars& P, double timestep, int64_t minCo
   sum[8] = seg_mean(bur, 3, 2, nb - 1);
   sum[9] = seg_median(bur, 3, 2, nb - 1, scr);
   sum[10] = seg_sd(bur, 3, 2, nb - 1);
+}
+
+// One sound: o = its cells with the envelope in place
+template <class Sync>
+SG_SEG_HD inline void seg_sound(const SegPars& P, double timestep, int64_t minCount, int64_t m, double* o, int lane,
+                                int nl, double* red, Sync sync) {
+  const int64_t mm = m > 0 ? m : 0;
+  seg_sound_at(P, timestep, minCount, m, o + seg_env0(), o, o + kSegHead, o + seg_syl0(mm), o + seg_bur0(mm),
+               o + seg_scr0(mm), lane, nl, red, sync);
 }
 
 }  // namespace sg

@@ -37,10 +37,17 @@
 // A batch runs in chunks of consecutive sounds whose workspaces fit the cap
 // (sg_segment_params.workspace_cap, default sg::kSegWorkspaceCap); every kernel's work on a
 // sound is the same in any chunking.
+//
+// A parameter sweep (sg_segment_sweep: what optimizePars() evaluates) runs the same kernels
+// up to the raw envelope once per sound, sg_seg_smooth once per group of rows with equal
+// (windowLength, overlap), and sg_seg_sweep_tail, one workgroup per (row, sound), over chunks
+// of rows; sg_sweep_fit turns a column of the summaries into the fitness of every row.
 #include <hip/hip_runtime.h>
 
 #include <array>
 #include <memory>
+#include <string>
+#include <utility>
 
 #include "sg_dev64.h"
 #include "sg_fft64_dev.h"
@@ -76,6 +83,19 @@ struct SegItem {
 struct SegWin {
   int32_t snd, idx, first, count;
   int32_t jump, pad;  // point j is value first + j, first + j + 1 from j = jump on
+};
+// A sweep (sg_segment_sweep). Slot (group, sound): the smoothed envelope of the sound under
+// the group's (windowLength, overlap), kept once for all rows of the group
+struct SweepSlot {
+  int64_t e0;  // its cells among the envelopes: seg_env0() unused ones (sg_seg_smooth writes as into a sound's cells), then m values
+  int64_t w0;  // first cell of the sound's pair within a row's workspace
+  double timestep;
+  int32_t m, pad;
+};
+struct SweepRow {
+  sg::SegPars P;
+  int64_t w0;  // first cell of the row's workspace within its chunk
+  int32_t group, pad;
 };
 
 __device__ __forceinline__ double seg_norm(double v, const SegStat& q) {
@@ -279,6 +299,96 @@ __global__ __launch_bounds__(kTailT) void sg_seg_tail(const SegSound* __restrict
   sg::seg_sound(P, S.timestep, S.minCount, (int64_t)S.m, out + S.o0, (int)threadIdx.x, kTailT, red, WgSync());
 }
 
+// The sweep's tail: workgroup b of a chunk of rows is (row row0 + b / n_calls, sound b %
+// n_calls). The envelope is the one its row's group smoothed for the sound; the pair's head,
+// tables and scratch are cells of the chunk's workspace; the summary row goes to the output.
+// An envelope of at most lds_values values is first copied to LDS (the lanes then read it
+// there; the same values, so the same results); a longer one is read where it lies.
+__global__ __launch_bounds__(kTailT) void sg_seg_sweep_tail(const SweepSlot* __restrict__ slots,
+                                                            const SweepRow* __restrict__ rows, int64_t row0,
+                                                            int32_t n_calls, int32_t lds_values,
+                                                            const double* __restrict__ envs, double* __restrict__ work,
+                                                            double* __restrict__ out) {
+  __shared__ double red[kTailT];
+  const int64_t r = row0 + (int64_t)(blockIdx.x / (unsigned)n_calls);
+  const int c = (int)(blockIdx.x % (unsigned)n_calls);
+  const SweepRow R = rows[r];
+  const SweepSlot S = slots[(int64_t)R.group * n_calls + c];
+  const int64_t m = S.m;
+  const double* env = envs + S.e0 + sg::seg_env0();
+  if (m > 0 && m <= (int64_t)lds_values) {  // workgroup-uniform
+    double* stage = reinterpret_cast<double*>(seg_lds);
+    for (int64_t i = threadIdx.x; i < m; i += kTailT) stage[i] = env[i];
+    __syncthreads();
+    env = stage;
+  }
+  double* w = work + R.w0 + S.w0;
+  const int64_t minCount = m > 0 ? sg::seg_min_count(R.P.shortestSyl, S.timestep) : 0;
+  sg::seg_sound_at(R.P, S.timestep, minCount, m, env, w, out + (r * n_calls + c) * sg::kSegSummary,
+                   w + sg::seg_pair_syl0(), w + sg::seg_pair_bur0(m), w + sg::seg_pair_scr0(m), (int)threadIdx.x, kTailT,
+                   red, WgSync());
+}
+
+// 1 - cor(column `col` of row r, key, use = 'pairwise.complete.obs'): one wavefront per row
+// of a matrix of n_rows x n_calls x width doubles. Lane l takes the sounds l, l + 64, ...
+// in order and skips a pair with a NaN on either side; the 64 partial sums fold in wsum's
+// butterfly. Two passes: the count and the two means, then the sums of squares and of
+// products about them. The order depends on n_calls alone. NaN for fewer than two complete
+// pairs or a side without variance (all its values equal; R: NA); the correlation is
+// clamped to [-1, 1] as cov.c does.
+__global__ __launch_bounds__(kT) void sg_sweep_fit(const double* __restrict__ mat, int64_t n_rows, int64_t n_calls,
+                                                   int32_t width, int32_t col, const double* __restrict__ key,
+                                                   double* __restrict__ fit) {
+#pragma clang fp contract(off)
+  const int64_t r = (int64_t)blockIdx.x * (kT / 64) + threadIdx.x / 64;
+  if (r >= n_rows) return;  // wavefront-uniform
+  const int lane = threadIdx.x & 63;
+  const double* x = mat + r * n_calls * width + col;
+  double n = 0, sx = 0, sk = 0, lo[2] = {INFINITY, INFINITY}, hi[2] = {-INFINITY, -INFINITY};
+  for (int64_t c = lane; c < n_calls; c += 64) {
+    const double a = x[c * width], b = key[c];
+    if (a != a || b != b) continue;
+    n += 1;
+    sx += a;
+    sk += b;
+    lo[0] = fmin(lo[0], a);
+    hi[0] = fmax(hi[0], a);
+    lo[1] = fmin(lo[1], b);
+    hi[1] = fmax(hi[1], b);
+  }
+  n = wsum(n);
+  sx = wsum(sx);
+  sk = wsum(sk);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1)
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      lo[k] = fmin(lo[k], __shfl_xor(lo[k], o));
+      hi[k] = fmax(hi[k], __shfl_xor(hi[k], o));
+    }
+  const bool flat = !(lo[0] < hi[0]) || !(lo[1] < hi[1]);  // a constant side: no variance, whatever the mean rounds to
+  const double mx = sx / n, mk = sk / n;
+  double sxx = 0, skk = 0, sxk = 0;
+  for (int64_t c = lane; c < n_calls; c += 64) {
+    const double a = x[c * width], b = key[c];
+    if (a != a || b != b) continue;
+    const double da = a - mx, db = b - mk;
+    sxx += da * da;
+    skk += db * db;
+    sxk += da * db;
+  }
+  sxx = wsum(sxx);
+  skk = wsum(skk);
+  sxk = wsum(sxk);
+  if (lane != 0) return;
+  double v = NAN;
+  if (n >= 2 && !flat && sxx > 0 && skk > 0) {
+    v = sxk / (sqrt(sxx) * sqrt(skk));
+    v = v > 1 ? 1 : v < -1 ? -1 : v;
+  }
+  fit[r] = 1 - v;
+}
+
 double g_seg_ms[sg::kSegStages];  // of the last profiled launch sequence
 
 // first root of the table of an M = 2^lg-point frame (2 M roots) among the tables of 2^1 .. 2^11
@@ -291,13 +401,50 @@ void allow_lds(K kernel, int bytes) {
 }
 int lds_bytes(int M) { return (2 * M + 32) * (int)sizeof(double2); }
 
+// What a sweep launches behind the raw envelopes in place of the one smoothing and the one
+// tail: launch() on the stream, finish() once it is synchronised (ms: the device time of the
+// smoothing and of the tail, as kernel_ms[4] and [5])
+struct SegBehind {
+  virtual void launch(const std::vector<SegSound>& snds, const double* d_raw, sg::DevBuf& db, hipStream_t s,
+                      bool timed) = 0;
+  virtual void finish(double* ms) = 0;
+  virtual ~SegBehind() {}
+};
+
+// the smoothing windows of sound c behind those of the sounds in front of it
+void push_windows(std::vector<SegWin>& wins, int64_t c, const sg::SegPlan& S) {
+  if ((int64_t)wins.size() + S.m > 2147483647LL)
+    throw sg::SgError(SG_E_UNSUPPORTED, "segment: the tiles or windows of one launch exceed 2^31");
+  if ((int64_t)S.first.size() != S.m || (int64_t)S.count.size() != S.m || (int64_t)S.jump.size() != S.m)
+    throw sg::SgError(SG_E_DEVICE, "segment: a sound's plan has no windows");
+  for (int64_t i = 0; i < S.m; ++i) {
+    if (S.first[i] < 0 || S.count[i] < 1 || S.jump[i] < 0 || S.jump[i] > S.count[i] ||
+        (int64_t)S.first[i] + S.count[i] + (S.jump[i] < S.count[i]) > S.n_env)
+      throw sg::SgError(SG_E_DEVICE, "segment: a smoothing window leaves the envelope");
+    wins.push_back(SegWin{(int32_t)c, (int32_t)i, S.first[i], S.count[i], S.jump[i], 0});
+  }
+}
+
+void launch_smooth(const SegSound* d_snd, const std::vector<SegWin>& wins, const double* d_raw, double* d_out,
+                   sg::DevBuf& db, hipStream_t s) {
+  if (wins.empty()) return;
+  const SegWin* d_wins = sg::upload(db, wins, s);
+  const int64_t nwin = (int64_t)wins.size(), per = kT / 64;
+  hipLaunchKernelGGL(sg_seg_smooth, dim3((unsigned)((nwin + per - 1) / per)), dim3(kT), 0, s, d_snd, d_wins, nwin, d_raw,
+                     d_out);
+  HIPCHK(hipGetLastError());
+}
+
 }  // namespace
 
 namespace sg {
 
+// segment_device(), or with `behind` a sweep's front: the raw envelopes of the sounds (only
+// the hilbert fields of the plans are read; d_out and out_off are not), then behind->launch()
 template <typename T>
-void segment_device(const sg_segment_params& p, const std::vector<SegPlan>& plans, const T* d_x, const int64_t* offsets,
-                    int64_t n_calls, double* d_out, const int64_t* out_off, hipStream_t s, double* kernel_ms) {
+void segment_run(const sg_segment_params& p, const std::vector<SegPlan>& plans, const T* d_x, const int64_t* offsets,
+                 int64_t n_calls, double* d_out, const int64_t* out_off, hipStream_t s, double* kernel_ms,
+                 SegBehind* behind) {
   const bool env_only = p.mode == 1;
   const SegPars P = env_only ? SegPars{} : seg_pars(p);
   const int64_t cap_cells = std::max<int64_t>(1, (p.workspace_cap > 0 ? p.workspace_cap : kSegWorkspaceCap) / (int64_t)sizeof(double2));
@@ -312,15 +459,15 @@ void segment_device(const sg_segment_params& p, const std::vector<SegPlan>& plan
     SegSound& Q = snds[c];
     Q = SegSound{};
     Q.x0 = offsets[c];
-    Q.o0 = out_off[c];
+    Q.o0 = behind ? 0 : out_off[c];
+    const int64_t room = behind ? INT64_MAX : out_off[c + 1] - out_off[c];
     if (S.n1 == 0) {
-      if (out_off[c + 1] - out_off[c] < seg_cells(0)) throw SgError(SG_E_CAPACITY, "segment: a sound's cells do not fit");
+      if (room < seg_cells(0)) throw SgError(SG_E_CAPACITY, "segment: a sound's cells do not fit");
       continue;
     }
     if (S.p < 1 || S.p > kSegMaxLog2 || S.n_env > S.N || S.shift < 0 || S.shift + S.n_env > S.N || S.left + S.n1 > S.N ||
-        out_off[c + 1] - out_off[c] < seg_out_cells(p, S))
-      throw SgError(out_off[c + 1] - out_off[c] < seg_out_cells(p, S) ? SG_E_CAPACITY : SG_E_DEVICE,
-                    "segment: a sound's plan leaves its buffers");
+        room < seg_out_cells(p, S))
+      throw SgError(room < seg_out_cells(p, S) ? SG_E_CAPACITY : SG_E_DEVICE, "segment: a sound's plan leaves its buffers");
     Q.n1 = S.n1;
     Q.p = S.p;
     Q.left = (int32_t)S.left;
@@ -350,17 +497,10 @@ void segment_device(const sg_segment_params& p, const std::vector<SegPlan>& plan
     if (!env_only) {
       Q.tile0 = (int32_t)tiles.size();
       Q.ntiles = (int32_t)((S.n1 + kTile - 1) / kTile);
-      if ((int64_t)tiles.size() + Q.ntiles > 2147483647LL || (int64_t)wins.size() + S.m > 2147483647LL)
+      if ((int64_t)tiles.size() + Q.ntiles > 2147483647LL)
         throw SgError(SG_E_UNSUPPORTED, "segment: the tiles or windows of one launch exceed 2^31");
       for (int32_t t = 0; t < Q.ntiles; ++t) tiles.push_back(SegItem{(int32_t)c, t});
-      if ((int64_t)S.first.size() != S.m || (int64_t)S.count.size() != S.m || (int64_t)S.jump.size() != S.m)
-        throw SgError(SG_E_DEVICE, "segment: a sound's plan has no windows");
-      for (int64_t i = 0; i < S.m; ++i) {
-        if (S.first[i] < 0 || S.count[i] < 1 || S.jump[i] < 0 || S.jump[i] > S.count[i] ||
-            (int64_t)S.first[i] + S.count[i] + (S.jump[i] < S.count[i]) > S.n_env)
-          throw SgError(SG_E_DEVICE, "segment: a smoothing window leaves the envelope");
-        wins.push_back(SegWin{(int32_t)c, (int32_t)i, S.first[i], S.count[i], S.jump[i], 0});
-      }
+      if (!behind) push_windows(wins, c, S);
     }
   }
   chunk_end.push_back(n_calls);
@@ -452,14 +592,10 @@ void segment_device(const sg_segment_params& p, const std::vector<SegPlan>& plan
     c0 = c1;
   }
   clkB.stamp();  // smoothing
-  if (!env_only) {
-    if (!wins.empty()) {
-      const SegWin* d_wins = upload(db, wins, s);
-      const int64_t nwin = (int64_t)wins.size(), per = kT / 64;
-      hipLaunchKernelGGL(sg_seg_smooth, dim3((unsigned)((nwin + per - 1) / per)), bT, 0, s, d_snd, d_wins, nwin, d_raw,
-                         d_out);
-      HIPCHK(hipGetLastError());
-    }
+  if (behind) {
+    behind->launch(snds, d_raw, db, s, kernel_ms != nullptr);
+  } else if (!env_only) {
+    launch_smooth(d_snd, wins, d_raw, d_out, db, s);
     clkB.stamp();  // tail
     hipLaunchKernelGGL(sg_seg_tail, dim3((unsigned)n_calls), dim3(kTailT), 0, s, d_snd, P, d_out);
     HIPCHK(hipGetLastError());
@@ -476,7 +612,14 @@ void segment_device(const sg_segment_params& p, const std::vector<SegPlan>& plan
     }
     kernel_ms[4] = msB[0];
     kernel_ms[5] = msB[1];
+    if (behind) behind->finish(kernel_ms + 4);
   }
+}
+
+template <typename T>
+void segment_device(const sg_segment_params& p, const std::vector<SegPlan>& plans, const T* d_x, const int64_t* offsets,
+                    int64_t n_calls, double* d_out, const int64_t* out_off, hipStream_t s, double* kernel_ms) {
+  segment_run<T>(p, plans, d_x, offsets, n_calls, d_out, out_off, s, kernel_ms, nullptr);
 }
 
 template void segment_device<float>(const sg_segment_params&, const std::vector<SegPlan>&, const float*, const int64_t*,
@@ -486,7 +629,188 @@ template void segment_device<double>(const sg_segment_params&, const std::vector
 
 }  // namespace sg
 
+namespace {
+
+// sg_segment_sweep: n_rows parameter rows over n_calls sounds. The raw envelopes come from
+// segment_run (once per sound); per envelope group one sg_seg_smooth launch over all sounds
+// into the group's slots; then sg_seg_sweep_tail over chunks of consecutive rows whose pair
+// workspaces fit the cap. Every kernel's work on a (sound, row) pair is the same whatever
+// other rows and sounds share the launch and however the rows are chunked.
+constexpr int kSweepLdsValues = 8192;  // 64 KiB of a CU's 160: two workgroups' envelopes
+int g_sweep_staging = 1;               // sg_set_sweep_staging
+double g_sweep_ms[sg::kSegStages];     // of the last profiled sweep
+
+struct Sweep : SegBehind {
+  int64_t n_calls = 0;
+  std::vector<std::vector<sg::SegPlan>> plans;  // [group][sound]
+  std::vector<SweepSlot> slots;                 // [group * n_calls + sound]
+  std::vector<SweepRow> rows;
+  std::vector<int64_t> chunk_end;               // one past the last row of each chunk
+  int64_t env_cells = 0, work_cells = 0;
+  int32_t max_m = 0;
+  double* d_out = nullptr;
+  double ms[2] = {0, 0};
+  std::unique_ptr<sg::StageClock> clk;
+
+  void launch(const std::vector<SegSound>& snds, const double* d_raw, sg::DevBuf& db, hipStream_t s,
+              bool timed) override {
+    clk.reset(new sg::StageClock(s, timed ? ms : nullptr, 2));
+    double* d_env = db.get<double>((size_t)env_cells);
+    clk->stamp();  // smoothing, group by group
+    for (size_t g = 0; g < plans.size(); ++g) {
+      std::vector<SegSound> gs = snds;  // the group's view of the sounds: where sg_seg_smooth writes
+      std::vector<SegWin> wins;
+      for (int64_t c = 0; c < n_calls; ++c) {
+        gs[c].o0 = slots[g * n_calls + c].e0;
+        if (plans[g][c].n1 > 0) push_windows(wins, c, plans[g][c]);
+      }
+      launch_smooth(sg::upload(db, gs, s), wins, d_raw, d_env, db, s);
+    }
+    clk->stamp();  // tails, chunk by chunk
+    const SweepSlot* d_slots = sg::upload(db, slots, s);
+    const SweepRow* d_rows = sg::upload(db, rows, s);
+    double* d_work = db.get<double>((size_t)work_cells);
+    const int32_t lds_values = g_sweep_staging ? std::min(max_m, (int32_t)kSweepLdsValues) : 0;
+    const size_t lds = (size_t)lds_values * sizeof(double);
+    allow_lds(&sg_seg_sweep_tail, (int)lds);
+    int64_t r0 = 0;
+    for (int64_t r1 : chunk_end) {
+      hipLaunchKernelGGL(sg_seg_sweep_tail, dim3((unsigned)((r1 - r0) * n_calls)), dim3(kTailT), lds, s, d_slots, d_rows,
+                         r0, (int32_t)n_calls, lds_values, d_env, d_work, d_out);
+      HIPCHK(hipGetLastError());
+      r0 = r1;
+    }
+    clk->stamp();
+  }
+  void finish(double* out) override {
+    clk->finish();
+    out[0] = ms[0];
+    out[1] = ms[1];
+  }
+};
+
+std::string sweep_where(int64_t r, int64_t c) {
+  return "sg_segment_sweep: row " + std::to_string(r) + (c >= 0 ? ", sound " + std::to_string(c) : std::string()) + ": ";
+}
+
+void segment_sweep(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, const int64_t* lengths, int64_t n_calls,
+                   const sg_segment_params* prow, int64_t n_rows, double* d_out) {
+  const sg_segment_params& p0 = prow[0];
+  Sweep W;
+  W.n_calls = n_calls;
+  W.d_out = d_out;
+  W.rows.resize((size_t)n_rows);
+  std::vector<std::pair<double, double>> keys;  // a group's (windowLength, clamped overlap)
+  for (int64_t r = 0; r < n_rows; ++r) {  // every refusal comes before the first launch
+    const sg_segment_params& p = prow[r];
+    try {
+      W.rows[r].P = sg::seg_pars(p);
+    } catch (const sg::SgError& e) {
+      throw sg::SgError(e.code, sweep_where(r, -1) + e.what());
+    }
+    if (p.samplingRate != p0.samplingRate || p.mode != 0 || p.workspace_cap != p0.workspace_cap)
+      throw sg::SgError(SG_E_ARG, sweep_where(r, -1) + "samplingRate, mode = 0 and workspace_cap are those of row 0");
+    const std::pair<double, double> key(p.windowLength, std::fmin(std::fmax(p.overlap, 0.0), 99.0));
+    size_t g = 0;
+    while (g < keys.size() && keys[g] != key) ++g;
+    if (g == keys.size()) {
+      keys.push_back(key);
+      W.plans.emplace_back((size_t)n_calls);
+      for (int64_t c = 0; c < n_calls; ++c) {
+        if (lengths[c] < 3) continue;
+        try {
+          W.plans[g][c] = sg::seg_plan(p, lengths[c], true);
+        } catch (const sg::SgError& e) {
+          throw sg::SgError(e.code, sweep_where(r, c) + e.what());
+        }
+      }
+    }
+    W.rows[r].group = (int32_t)g;
+  }
+  const int64_t cap_cells =
+      std::max<int64_t>(1, (p0.workspace_cap > 0 ? p0.workspace_cap : sg::kSegWorkspaceCap) / (int64_t)sizeof(double));
+  std::vector<int64_t> row_cells(keys.size(), 0);
+  W.slots.resize(keys.size() * (size_t)n_calls);
+  for (size_t g = 0; g < keys.size(); ++g)
+    for (int64_t c = 0; c < n_calls; ++c) {
+      const sg::SegPlan& S = W.plans[g][c];
+      SweepSlot& Q = W.slots[g * n_calls + c];
+      Q = SweepSlot{W.env_cells, row_cells[g], S.timestep, (int32_t)S.m, 0};
+      W.env_cells += sg::seg_env0() + S.m;
+      row_cells[g] += sg::seg_pair_cells(S.m);
+      W.max_m = std::max(W.max_m, Q.m);
+    }
+  int64_t work = 0, first = 0;
+  for (int64_t r = 0; r < n_rows; ++r) {
+    const int64_t need = row_cells[W.rows[r].group];
+    if (r > first && (work + need > cap_cells || (r - first + 1) * n_calls > 2147483647LL)) {
+      W.chunk_end.push_back(r);  // the cap is reached: this row opens the next chunk
+      first = r;
+      work = 0;
+    }
+    W.rows[r].w0 = work;
+    work += need;
+    W.work_cells = std::max(W.work_cells, work);
+  }
+  W.chunk_end.push_back(n_rows);
+  HIPCHK(hipSetDevice(ctx->device));
+  sg::segment_run<float>(p0, W.plans[0], d_wave, offsets, n_calls, nullptr, nullptr, ctx->stream,
+                         ctx->profiling ? g_sweep_ms : nullptr, &W);
+}
+
+void sweep_fitness(sg_ctx* ctx, const double* d_matrix, int64_t n_rows, int64_t n_calls, int32_t width, int32_t column,
+                   const double* key, double* fit) {
+  HIPCHK(hipSetDevice(ctx->device));
+  sg::DevBuf db;
+  const double* d_key = sg::upload(db, std::vector<double>(key, key + n_calls), ctx->stream);
+  double* d_fit = db.get<double>((size_t)n_rows);
+  const int64_t per = kT / 64;
+  hipLaunchKernelGGL(sg_sweep_fit, dim3((unsigned)((n_rows + per - 1) / per)), dim3(kT), 0, ctx->stream, d_matrix, n_rows,
+                     n_calls, width, column, d_key, d_fit);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(fit, d_fit, (size_t)n_rows * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+}
+
+}  // namespace
+
 extern "C" {
+
+int sg_segment_sweep(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, const int64_t* lengths, int64_t n_calls,
+                     const sg_segment_params* rows, int64_t n_rows, double* d_out) {
+  return sg::guarded(ctx, [&]() {
+    if (!ctx || n_calls < 0 || n_calls > 2147483647LL || n_rows < 0 || (n_rows > 0 && !rows) ||
+        (n_calls > 0 && (!d_wave || !offsets || !lengths)) || (n_calls > 0 && n_rows > 0 && !d_out))
+      throw sg::SgError(SG_E_ARG, "sg_segment_sweep: bad arguments");
+    if (n_calls == 0 || n_rows == 0) return (int)SG_OK;
+    segment_sweep(ctx, d_wave, offsets, lengths, n_calls, rows, n_rows, d_out);
+    return (int)SG_OK;
+  });
+}
+
+int sg_sweep_fitness(sg_ctx* ctx, const double* d_matrix, int64_t n_rows, int64_t n_calls, int32_t width, int32_t column,
+                     const double* key, double* fit) {
+  return sg::guarded(ctx, [&]() {
+    if (!ctx || n_rows < 0 || n_calls < 0 || width < 1 || column < 0 || column >= width ||
+        (n_rows + 3) / 4 > 2147483647LL || (n_rows > 0 && (!fit || (n_calls > 0 && (!d_matrix || !key)))))
+      throw sg::SgError(SG_E_ARG, "sg_sweep_fitness: bad arguments");
+    if (n_rows == 0) return (int)SG_OK;
+    sweep_fitness(ctx, d_matrix, n_rows, n_calls, width, column, key, fit);
+    return (int)SG_OK;
+  });
+}
+
+int sg_set_sweep_staging(int32_t mode) {
+  if (mode != 0 && mode != 1) return SG_E_ARG;
+  g_sweep_staging = mode;
+  return SG_OK;
+}
+
+int sg_debug_sweep_kernel_ms(double* out) {
+  if (!out) return SG_E_ARG;
+  for (int k = 0; k < sg::kSegStages; ++k) out[k] = g_sweep_ms[k];
+  return SG_OK;
+}
 
 int sg_segment(sg_ctx* ctx, const double* wave, int64_t len, const sg_segment_params* p, double* out) {
   return sg::guarded(ctx, [&]() {

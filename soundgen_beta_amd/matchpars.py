@@ -143,12 +143,13 @@ def _revsort(a, ib):
 
 
 def rnorm_bounded(D, n, mean, sd, low=None, high=None, roundToInteger=False):
-    """rnorm_bounded(), R/utilities_math.R:187-231."""
+    """rnorm_bounded(), R/utilities_math.R:187-231. low / high: a number for all, or one per
+    value (optimizePars' bounds)."""
     mean = list(np.atleast_1d(np.asarray(mean, float)))
     sd = list(np.atleast_1d(np.asarray(sd, float)))
-    lo = -math.inf if low is None else low
-    hi = math.inf if high is None else high
-    mean = [min(max(m, lo), hi) for m in mean]
+    lo = np.broadcast_to(np.asarray(-math.inf if low is None else low, float), (max(n, len(mean)),))
+    hi = np.broadcast_to(np.asarray(math.inf if high is None else high, float), (max(n, len(mean)),))
+    mean = [min(max(m, lo[i]), hi[i]) for i, m in enumerate(mean)]
     if len(mean) < n:
         mean = [mean[0]] * n
     if len(sd) < n:
@@ -158,7 +159,7 @@ def rnorm_bounded(D, n, mean, sd, low=None, high=None, roundToInteger=False):
         return [rnd(m) for m in mean]
     out = [rnd(D.rnorm1(mean[i], sd[i])) for i in range(n)]
     for i in range(n):
-        while out[i] < lo or out[i] > hi:
+        while out[i] < lo[i] or out[i] > hi[i]:
             out[i] = rnd(D.rnorm1(mean[i], sd[i]))
     return out
 

@@ -163,6 +163,12 @@ def lib():
         L.sg_segment.argtypes = [vp, dp, i64, gpp, dp]
         L.sg_segment_batch.argtypes = [vp, vp, i64p, i64p, i64, gpp, vp, i64p]
         L.sg_debug_segment_kernel_ms.argtypes = [dp]
+    if hasattr(L, "sg_segment_sweep"):  # parameter sweeps of segment(): likewise additive
+        gpp = C.POINTER(_abi.sg_segment_params)
+        L.sg_segment_sweep.argtypes = [vp, vp, i64p, i64p, i64, gpp, i64, vp]
+        L.sg_sweep_fitness.argtypes = [vp, vp, i64, i64, C.c_int32, C.c_int32, dp, dp]
+        L.sg_set_sweep_staging.argtypes = [C.c_int32]
+        L.sg_debug_sweep_kernel_ms.argtypes = [dp]
     L.sg_rrng_create.argtypes = [C.c_int32, C.POINTER(vp)]
     L.sg_rrng_destroy.argtypes = [vp]
     L.sg_rrng_set_seed.argtypes = [vp, C.c_int32]
