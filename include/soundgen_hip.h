@@ -671,6 +671,43 @@ int sg_analyze_summary_batch(sg_ctx* ctx, const float* d_wave, const int64_t* of
  * SG_ANALYZE_SUMMARY_COLS doubles). Refuses what sg_analyze refuses. */
 int sg_analyze_summary_sound(sg_ctx* ctx, const double* wave, int64_t len, const sg_analyze_params_full* p, double* out,
                              double* summary);
+/* analyze()'s formant tracks (R/analyze.R:486-502; an additive extension of ABI 5): for every
+ * frame that passed cond_silence, phonTools::findformants(frame, samplingRate, verify = FALSE)
+ * with its defaults, restated from phonTools 0.2-2.1 as documented (phonTools is not in the
+ * reference tree: PARITY UNPINNED, like sg_dtw_symmetric2). Linear prediction of order
+ * round(samplingRate / 1000) + 3 (pre-emphasis at 50 Hz, minus the mean, a Hann window,
+ * autocorrelation, Levinson-Durbin where phonTools solves by LU), all roots of the predictor by
+ * the Aberth-Ehrlich iteration in fp64, formant = round(atan2(Im z, Re z) samplingRate / (2 pi),
+ * 2), bandwidth = -(samplingRate / pi) log|z|, ordered by formant, kept where bandwidth < 600 &
+ * formant > 200 & formant < samplingRate / 2. A row holds f1_freq, f1_width, f2_freq, ...:
+ * 2 nFormants doubles, NaN = NA (a frame not analysed, fewer kept roots, a frame whose
+ * autocorrelation Levinson-Durbin refuses or whose iteration does not settle in 64 steps).
+ * round(x, 2) is nearbyint(100 x) / 100 in fp64 (R multiplies in long double). A frame's row is
+ * the same bit for bit alone, in any batch and at any position of it.
+ * Host only: the order and cols = 2 nFormants. SG_E_ARG unless 1 <= nFormants <= 8;
+ * SG_E_UNSUPPORTED for an order above 64 (samplingRate >= 61.5 kHz): one root per lane of a
+ * wave. SG_E_ARG too where p's window is not longer than the order (windowLength = 1 ms at
+ * 44.1 kHz: 44 samples for order 47; the reference's solve() fails on every such frame), and
+ * what sg_analyze_frames_size refuses. Errors through sg_analyze_frames_size_error. */
+int sg_formants_size(const sg_analyze_params* p, int32_t nFormants, int32_t* order, int32_t* cols);
+/* The formant tables of n_calls sounds in DEVICE memory (as for sg_analyze_frames_batch) behind
+ * their finished tables from sg_analyze_frames_batch, sg_pitch_candidates_batch or
+ * sg_analyze_batch (d_tables, out_off, frames as those calls left them; table_cols their
+ * columns; of p only what the three share is read, and p->methods may name any of the four
+ * methods): call c's frames[c] x 2 nFormants table goes to d_fmt + fmt_off[c] in DEVICE memory.
+ * A call without frames (frames[c] == 0: not longer than the window, or failed) writes nothing.
+ * Returns when the stream has finished. */
+int sg_formants_batch(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, const int64_t* lengths, int64_t n_calls,
+                      const sg_analyze_params* p, int32_t nFormants, const double* d_tables, const int64_t* out_off,
+                      int32_t table_cols, const int32_t* frames, double* d_fmt, const int64_t* fmt_off);
+/* One sound from host memory: sg_analyze_frames for the gate, then the formants; out (host)
+ * receives frames x 2 nFormants doubles. Refuses what sg_analyze_frames refuses. */
+int sg_formants_sound(sg_ctx* ctx, const double* wave, int64_t len, const sg_analyze_params* p, int32_t nFormants, double* out);
+/* The two kernels alone on nframes caller-given frames of n samples each (host, row after row;
+ * order < n <= 4096): no gate, no normalisation, no analysis window; fs is findformants' fs.
+ * out (host) receives nframes x 2 nFormants doubles. */
+int sg_formants_frames(sg_ctx* ctx, const double* frames, int32_t n, int32_t nframes, double fs, int32_t nFormants,
+                       double* out);
 /* segment() (an additive extension of ABI 5; R/segment.R:79-219, R/utilities_segment.R):
  * the smoothed Hilbert envelope of the whole sound (seewave::env(envt = "hil", msmooth =
  * c(windowLength_points, overlap)): a transform of 2^ceiling(log2(len)) points), the
@@ -917,6 +954,10 @@ int sg_debug_track_kernel_ms(double* out);
  * sg_analyze_summary_batch / sg_analyze_summary_sound run (1 double); the stages before it
  * are sg_debug_track_kernel_ms's, unchanged. */
 int sg_debug_summary_kernel_ms(double* out);
+/* The device milliseconds of sg_fmt_lags and sg_fmt_roots in the last profiled sg_formants* run
+ * (2 doubles), and, of the last run, profiled or not (counts: 3 int64, or NULL): the frames
+ * that hit the iteration cap, the frames analysed, and the Aberth iterations those took. */
+int sg_debug_formants_kernel_ms(double* out, int64_t* counts);
 /* The same for the last sg_segment / sg_segment_batch run, summed over the chunks of a
  * batch: the normalization statistics, the forward columns with their twiddle (or the
  * whole transform of a sound of at most 2048 points), the rows (forward, the Hilbert

@@ -39,9 +39,10 @@ summary = TRUE (R/analyze.R:770-796: one row per sound, the mean, median and sd 
 acoustic variable) is summarize_table_numpy and, on the GPU, sg_anl_summary (sg_summary.h):
 analyze(summary=True), analyze_batch(summary=True), summarize_table; analyze_folder is
 analyzeFolder() (:831-930) on top of analyze_batch.
-Formants (phonTools is not in the reference tree), pathfinding = 'slow', the pitchAutocor /
-pitchCep / pitchSpec columns (so also their summary cells and the formants'), plots and
-savePath are out of scope.
+The formant columns (formants=True; phonTools::findformants restated, unpinned against R) are
+formants.py's: formants, formants_batch, find_formants_numpy, formants_numpy and
+find_formants_frames are re-exported here. pathfinding = 'slow', the pitchAutocor / pitchCep /
+pitchSpec columns (so also their summary cells), plots and savePath are out of scope.
 
 Quirks kept (what the statements do):
     * the frequency labels pass through R's character row names (spectrogram.R:176,
@@ -540,13 +541,25 @@ def _run_batch(data, offsets, lengths, samplingRate, s, frames_of, params, table
         rows = rows[:nc * len(SUMMARY_COLUMNS)].view(nc, len(SUMMARY_COLUMNS))
         if not to_host:
             return dict(out=rows, columns=SUMMARY_COLUMNS, frames=frames, tables=out, offsets=ooff[:-1].copy(), cols=cols)
-        return [dict(zip(SUMMARY_COLUMNS, (float(v) for v in r))) for r in rows.cpu().numpy()]
+        return _host_rows(rows)
     if not to_host:
         return dict(out=out, offsets=ooff[:-1].copy(), frames=frames, cols=cols,
                     columns=COLUMNS + sum(((k,) * nC for k in cand_keys), ()) + tuple(tail))
+    return _host_tables(out, frames, cols, table, nC, lens, samplingRate, s["step"])
+
+
+def _host_rows(rows):
+    """The summary matrix of a batch (n_calls x 44, on the device) as the list of per-call dicts."""
+    return [dict(zip(SUMMARY_COLUMNS, (float(v) for v in r))) for r in rows.cpu().numpy()]
+
+
+def _host_tables(out, frames, cols, table, nC, lens, samplingRate, step):
+    """The packed tables of a batch (on the device, call i's frames[i] x cols behind the ones before it) as the
+    list of per-call dicts that `table` builds."""
     h = out.cpu().numpy()
-    return [table(h[ooff[i]:ooff[i + 1]].reshape(frames[i], cols), nC, int(lens[i]), samplingRate, s["step"])
-            for i in range(nc)]
+    ooff = native.out_offsets([f * cols for f in frames])[0]
+    return [table(h[ooff[i]:ooff[i + 1]].reshape(frames[i], cols), nC, int(lens[i]), samplingRate, step)
+            for i in range(len(frames))]
 
 
 def analyze_frames(x, samplingRate=None, silence=0.04, windowLength=50, step=None, overlap=50, wn="gaussian", zp=0,
@@ -1551,7 +1564,7 @@ def analyze(x, samplingRate=None, silence=0.04, windowLength=50, step=None, over
             specPeak=0.35, specSinglePeakCert=0.4, specHNRslope=0.8, specSmooth=150, specMerge=1, shortestSyl=20,
             shortestPause=60, interpolWin=3, interpolTol=0.3, interpolCert=0.3, pathfinding="fast", certWeight=.5,
             snakeStep=0.05, snakePlot=False, smooth=1, smoothVars=SMOOTH_VARS, plot=False, device=0,
-            summary=False):
+            summary=False, formants=False, nFormants=3):
     """analyze() (R/analyze.R:153-707) on the GPU (sg_analyze, fp64): pitch_candidates()'
     dict plus pitch (the pathfinder's contour through the voiced segments, smoothed),
     voiced, amplVoiced and harmonics, with HNR and harmonics in dB, dom smoothed and the
@@ -1563,10 +1576,26 @@ def analyze(x, samplingRate=None, silence=0.04, windowLength=50, step=None, over
     True raises (with summary=True too, before anything runs). summary=True (R/analyze.R:
     770-796) returns the sound's summary row instead, a dict of the 44 floats named by
     SUMMARY_COLUMNS (see summarize_table_numpy): sg_anl_summary makes it from the table in
-    the same launch sequence (sg_analyze_summary_sound) and only the row leaves the device."""
+    the same launch sequence (sg_analyze_summary_sound) and only the row leaves the device.
+
+    formants=True (default False: the table and the row are then what they were) adds the
+    reference's formant columns f1_freq, f1_width, ..., 2 nFormants of them (R/analyze.R:486-502,
+    formants.py; unpinned against phonTools), from a second launch sequence behind the gate
+    (sg_formants_sound). With summary=True the 6 nFormants cells f1_freq_mean, f1_freq_median,
+    f1_freq_sd, f1_width_mean, ... follow the 44, reduced on the host from the formant table
+    (formants.formant_summary). nFormants is read only with formants=True."""
     sound, sr = _input(x, samplingRate)
     a = locals()
     s = repair_track(repair_pitch(sr, len(sound) / sr, **_pitch_args(a)), **_track_args(a))
+    if formants:
+        from . import formants as _fm
+        nFormants = _fm._check_n(nFormants)
+        _fm.formants_size(dict(s, pitchMethods=PITCH_METHODS), nFormants)  # refused before anything runs
+        res = analyze(**dict({k: a[k] for k in list(_pitch_args(a)) + list(_track_args(a))}, x=sound, samplingRate=sr,
+                             device=device, summary=summary))
+        ft = _fm._dict(_fm._formants_sound(sound, s, nFormants, device), nFormants)
+        res.update(_fm.formant_summary(ft, nFormants) if summary else ft)
+        return res
     if summary:
         d = track_decisions_native(len(sound), s)
         if len(sound) <= d["wl"]:
@@ -1589,7 +1618,7 @@ def analyze_batch(data, offsets, lengths, samplingRate, silence=0.04, windowLeng
                   specThres=0.3, specPeak=0.35, specSinglePeakCert=0.4, specHNRslope=0.8, specSmooth=150, specMerge=1,
                   shortestSyl=20, shortestPause=60, interpolWin=3, interpolTol=0.3, interpolCert=0.3, pathfinding="fast",
                   certWeight=.5, snakeStep=0.05, snakePlot=False, smooth=1, smoothVars=SMOOTH_VARS, plot=False,
-                  to_host=False, device=0, summary=False):
+                  to_host=False, device=0, summary=False, formants=False, nFormants=3):
     """analyze(call i, samplingRate, ...) for a batch of sounds already in HBM, laid out
     and returned as pitch_candidates_batch() does (sg_analyze_batch, one launch sequence,
     tables left in HBM). A row has 15 + 6 nCands + 4 columns: `columns` names those of
@@ -1603,9 +1632,39 @@ def analyze_batch(data, offsets, lengths, samplingRate, silence=0.04, windowLeng
     bit, whatever the batch and the call's place in it), `columns` (SUMMARY_COLUMNS) and
     `frames`, and also the tables as above under `tables`, `offsets` and `cols`. A call
     with no frames (not longer than the window, or a failed call of length < 0) has a row
-    of NaN. to_host=True then returns the list of per-call dicts of 44 named floats."""
+    of NaN. to_host=True then returns the list of per-call dicts of 44 named floats.
+
+    formants=True (default False): sg_formants_batch runs behind the finished tables (formants.py).
+    The returned dict gains `formants`, the dict formants_batch() returns (the formant tables
+    next to the main ones, in HBM); with summary=True also `formant_cells` (a host array of
+    shape (n_calls, 6 nFormants), reduced on the host from the formant tables) and
+    `formant_columns`. to_host=True: the per-call dicts gain analyze(formants=True)'s keys."""
     a = locals()
     s = repair_track(repair_pitch(samplingRate, None, **_pitch_args(a)), **_track_args(a))
+    if formants:
+        from . import formants as _fm
+        nFormants = _fm._check_n(nFormants)
+        _fm.formants_size(dict(s, pitchMethods=PITCH_METHODS), nFormants)
+        kw = dict(_pitch_args(a), **_track_args(a))
+        res = analyze_batch(data, offsets, lengths, samplingRate, to_host=False, device=device, summary=summary, **kw)
+        tabs = res["tables"] if summary else res["out"]
+        out, foff = _fm.formants_behind(data, offsets, lengths, s, nFormants, tabs, res["offsets"], res["cols"], res["frames"],
+                                        device)
+        res["formants"] = dict(out=out, offsets=foff[:-1].copy(), frames=res["frames"], cols=2 * nFormants,
+                               columns=_fm.formant_columns(nFormants))
+        if not summary and not to_host:
+            return res
+        fts = [_fm._dict(m, nFormants) for m in _fm._host_tables(out, foff, res["frames"], nFormants)]
+        if summary:
+            cells = [_fm.formant_summary(ft, nFormants) for ft in fts]
+            if not to_host:
+                res["formant_columns"] = tuple(cells[0]) if cells else ()
+                res["formant_cells"] = np.array([list(c.values()) for c in cells], float).reshape(len(cells), 6 * nFormants)
+                return res
+            return [dict(r, **c) for r, c in zip(_host_rows(res["out"]), cells)]
+        tables = _host_tables(tabs, res["frames"], res["cols"], _track_table, s["nCands"], np.asarray(lengths, dtype=np.int64),
+                              samplingRate, s["step"])
+        return [dict(t, **ft) for t, ft in zip(tables, fts)]
     return _run_batch(data, offsets, lengths, samplingRate, s, _track_frames_native, _track_params, _track_table,
                       ("autocorCand", "autocorCert") + PITCH_KEYS, "sg_analyze", to_host, device, TRACK_COLUMNS,
                       summary=bool(summary))
@@ -1776,7 +1835,7 @@ def analyze_folder(myfolder, verbose=True, samplingRate=None, silence=0.04, wind
                    specSmooth=150, specMerge=1, shortestSyl=20, shortestPause=60, interpolWin=3, interpolTol=0.3,
                    interpolCert=0.3, pathfinding="fast", annealPars=None, certWeight=.5, snakeStep=0.05, snakePlot=False,
                    smooth=1, smoothVars=SMOOTH_VARS, summary=True, plot=False, savePath=None, specPlot=None, pitchPlot=None,
-                   candPlot=None, device=0):
+                   candPlot=None, device=0, formants=False):
     """analyzeFolder() (R/analyze.R:831-930) on the GPU: analyze() for every .wav file of
     myfolder, by default (summary=True) one summary row per sound.
 
@@ -1794,9 +1853,10 @@ def analyze_folder(myfolder, verbose=True, samplingRate=None, silence=0.04, wind
     bit. summary=False: a dict from the file's full path (:926) to its analyze() table. As in
     analyze_batch(), the two repairs that need a sound's duration are not made, and a file not
     longer than the window gives a row of NaN (an empty table) where analyze() stops. verbose is
-    accepted and prints nothing; nFormants (formants are not built) and annealPars
-    (pathfinding = 'slow' raises) and the plot settings are accepted and not read; plot=True
-    and a savePath raise before any file is read."""
+    accepted and prints nothing; annealPars (pathfinding = 'slow' raises) and the plot settings
+    are accepted and not read; plot=True and a savePath raise before any file is read.
+    formants=True (default False) is passed to analyze_batch() with nFormants: the rows (or the
+    tables) gain analyze(formants=True)'s cells; nFormants is not read otherwise."""
     a = locals()
     if plot or priorPlot or snakePlot or savePath is not None:
         raise NotImplementedError("analyze_folder(plot = TRUE / savePath): plotting is out of scope")
@@ -1807,9 +1867,20 @@ def analyze_folder(myfolder, verbose=True, samplingRate=None, silence=0.04, wind
     results = [None] * len(paths)
     for g in groups:
         got = analyze_batch(g["data"], g["offsets"], g["lengths"], g["samplingRate"], to_host=True, device=device,
-                            summary=bool(summary), **kw)
+                            summary=bool(summary), formants=bool(formants), nFormants=nFormants, **kw)
         for i, r in zip(g["files"], got):
             results[i] = r
     if summary:                                                               # :918-923
         return [dict([("sound", n)] + list(r.items())) for n, r in zip(names, results)]
     return dict(zip(paths, results))                                          # :925-926
+
+
+_FORMANT_EXPORTS = ("formants", "formants_numpy", "find_formants_numpy", "formants_batch", "find_formants_frames")
+
+
+def __getattr__(name):
+    """formants.py's entry points under this module's name (formants.py imports this module)."""
+    if name in _FORMANT_EXPORTS:
+        from . import formants as _fm
+        return getattr(_fm, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

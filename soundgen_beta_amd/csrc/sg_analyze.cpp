@@ -23,6 +23,7 @@
 #include <cstring>
 #include <string>
 
+#include "sg_formants.h"
 #include "sg_rmath.h"
 
 namespace sg {
@@ -182,6 +183,27 @@ bool smooth31(int n) {
 }  // namespace
 
 AnlSetup anl_setup(const sg_analyze_params& p) { return anl_setup_m(p, 3); }
+
+AnlSetup anl_setup_any(const sg_analyze_params& p) { return anl_setup_m(p, 15); }
+
+int formants_order(double samplingRate, int nFormants) {
+  if (nFormants < 1 || nFormants > kFmtMaxFormants)
+    throw SgError(SG_E_ARG, "formants: nFormants must lie in 1.." + std::to_string(kFmtMaxFormants));
+  if (!(samplingRate > 0) || !(samplingRate < 1e9)) throw SgError(SG_E_ARG, "formants: samplingRate must be positive");
+  const int order = fmt_order(samplingRate);
+  if (order > kFmtMaxOrder)
+    throw SgError(SG_E_UNSUPPORTED, "formants: the order round(samplingRate / 1000) + 3 = " + std::to_string(order) +
+                                        " exceeds " + std::to_string(kFmtMaxOrder) +
+                                        " (one root per lane of a wave): samplingRate must stay below 61.5 kHz");
+  return order;
+}
+
+void formants_window(int wl, int order) {
+  if (wl <= order)
+    throw SgError(SG_E_ARG, "formants: windowLength gives frames of " + std::to_string(wl) + " samples; the prediction of order " +
+                                std::to_string(order) + " needs more than " + std::to_string(order) +
+                                " (the reference's solve() fails on every frame there and all rows are NA)");
+}
 
 PitchSetup pitch_setup(const sg_pitch_params& p) {
   PitchSetup S;
@@ -427,6 +449,18 @@ extern "C" int sg_analyze_frames_ampl_starts(int64_t len, const sg_analyze_param
     const int frames = sg::anl_frames(S, len);
     if (n > frames) throw sg::SgError(SG_E_ARG, "sg_analyze_frames_ampl_starts: n exceeds the frame count");
     for (int f = 0; f < n; ++f) starts[f] = sg::anl_ampl_start(S, len, frames, f);
+  });
+}
+
+extern "C" int sg_formants_size(const sg_analyze_params* p, int32_t nFormants, int32_t* order, int32_t* cols) {
+  if (!p || !order || !cols) {
+    g_anl_err = "sg_formants_size: bad arguments";
+    return SG_E_ARG;
+  }
+  return size_guard([&]() {
+    *order = sg::formants_order(p->samplingRate, nFormants);
+    *cols = 2 * nFormants;
+    sg::formants_window(sg::anl_setup_any(*p).spg.wl, *order);
   });
 }
 

@@ -37,6 +37,14 @@ struct AnlSetup {
   std::vector<double> lagf;     // label samplingRate / j of the used rows
 };
 AnlSetup anl_setup(const sg_analyze_params& p);
+// the same for any non-empty subset of the four pitch methods: what the stage, pitch_candidates and analyze() share
+// (the window, the frames, the columns up to cond_entropy), for the formants that run behind any of the three
+AnlSetup anl_setup_any(const sg_analyze_params& p);
+// the formants' order round(samplingRate / 1000) + 3 (sg_formants.h); SG_E_ARG for nFormants outside 1..8,
+// SG_E_UNSUPPORTED for an order above 64
+int formants_order(double samplingRate, int nFormants);
+// SG_E_ARG for a window of wl samples that is not longer than the order
+void formants_window(int wl, int order);
 // frames of a sound of len samples: 0 for len <= wl
 int anl_frames(const AnlSetup& S, int64_t len);
 // 0-based first sample of frame f's amplitude window of wl + 1 samples

@@ -833,6 +833,11 @@ void analyze_device(const AnlSetup& A, const T* d_x, const int64_t* offsets, con
   clk.finish();
 }
 
+// sg_formants.hip runs the stage for its gate
+template void analyze_device<double>(const AnlSetup&, const double*, const int64_t*, const int64_t*, int64_t, double*,
+                                     const int64_t*, int32_t*, hipStream_t, double*, const PitchSetup*, const TrackSetup*, double*,
+                                     double*);
+
 void path_device(const PathPars& P, int frames, int hw, double* d_rows, hipStream_t s, double* kernel_ms) {
   double ms = 0;
   StageClock clk(s, kernel_ms ? &ms : nullptr, 1);

@@ -39,6 +39,13 @@ struct SpgStat {
   int32_t scaled, pad;
 };
 
+// The normalisation statistics alone, as spectrogram_device computes them (the same kernels in
+// the same order: bit-equal), for a caller that rebuilds frames without a spectrogram
+// (sg_formants.hip). lengths[c] <= 0: an untouched entry. Synchronises the stream.
+template <typename T>
+void spg_stats_device(const T* d_x, const int64_t* offsets, const int64_t* lengths, int64_t n_calls, SpgStat* d_stat,
+                      hipStream_t s);
+
 // TN[t] = W_N^t = root64(t, N), t < N (device memory): a table of roots as fft64
 // (sg_fft64_dev.h) reads it, filled on stream s (the kernel sg_spg_roots)
 void fill_roots64(double2* d_TN, int N, hipStream_t s);

@@ -495,6 +495,36 @@ void fill_roots64(double2* d_TN, int N, hipStream_t s) {
   HIPCHK(hipGetLastError());
 }
 
+namespace {
+
+// The chunks of sound c (len samples) appended to the launch's list; returns the first of them
+int32_t stat_chunks(std::vector<SpgChunk>& chunks, int64_t c, int64_t len) {
+  const int32_t ch0 = (int32_t)chunks.size();
+  if ((int64_t)chunks.size() + len / kStatChunk + 1 > 2147483647LL)
+    throw SgError(SG_E_UNSUPPORTED, "spectrogram: the frames of one launch exceed 2^31");
+  for (int64_t k = 0; k * kStatChunk < len; ++k) chunks.push_back(SpgChunk{(int32_t)c, (int32_t)k});
+  return ch0;
+}
+
+// The normalisation statistics of n_calls sounds on stream s, nothing awaited: both passes over the chunks, each
+// folded per sound. d_stat holds kStatInit on entry; d_part: 3 doubles per chunk
+const SpgStat kStatInit{0, 1, 1, 0, 0, 0, 0};
+template <typename T>
+void stats_launch(const T* d_x, const SpgChunk* d_ch, size_t nchunks, const SpgSound* d_snd, int64_t n_calls, SpgStat* d_stat,
+                  double* d_part, hipStream_t s) {
+  for (int pass = 0; pass < 2; ++pass) {
+    if (nchunks) {
+      hipLaunchKernelGGL(sg_spg_stats<T>, dim3((unsigned)nchunks), dim3(kT), 0, s, d_x, d_ch, d_snd, d_stat, pass, d_part);
+      HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(sg_spg_stats_fold, dim3(((unsigned)n_calls + 63) / 64), dim3(64), 0, s, d_part, d_snd, (int)n_calls, pass,
+                       d_stat);
+    HIPCHK(hipGetLastError());
+  }
+}
+
+}  // namespace
+
 template <typename T>
 void spectrogram_device(const SpgSetup& S, const T* d_x, const int64_t* offsets, const int64_t* lengths,
                         int64_t n_calls, double* d_out, const int64_t* out_off, int32_t* bins_out,
@@ -524,9 +554,9 @@ void spectrogram_device(const SpgSetup& S, const T* d_x, const int64_t* offsets,
     if (S.processed && S.kFreq > nf)
       throw SgError(SG_E_ARG, "spectrogram: smoothFreq is larger than the " + std::to_string(nf) + " frames of call " +
                                   std::to_string((long long)c));
-    if ((int64_t)fr.size() + nf > 2147483647LL || (int64_t)chunks.size() + Q.len / kStatChunk + 1 > 2147483647LL)
+    if ((int64_t)fr.size() + nf > 2147483647LL)
       throw SgError(SG_E_UNSUPPORTED, "spectrogram: the frames of one launch exceed 2^31");
-    for (int64_t k = 0; k * kStatChunk < Q.len; ++k) chunks.push_back(SpgChunk{(int32_t)c, (int32_t)k});
+    stat_chunks(chunks, c, Q.len);
     for (int f = 0; f < nf; ++f) {
       const int64_t o = spg_frame_start(S, lengths[c], f);
       if (o < 0 || o + S.wl > lengths[c]) throw SgError(SG_E_DEVICE, "spectrogram: a frame leaves its sound");
@@ -548,17 +578,12 @@ void spectrogram_device(const SpgSetup& S, const T* d_x, const int64_t* offsets,
   // the keys of +Inf (no positive cell yet) and -Inf (no maximum yet)
   const unsigned long long kinf = dkey(INFINITY), kninf = dkey(-INFINITY);
   SpgRange* d_range = upload(db, std::vector<SpgRange>(n_calls, SpgRange{kinf, kninf, kninf, 0.0, 0.0, 0, 0}), s);
-  SpgStat* d_stat = upload(db, std::vector<SpgStat>(n_calls, SpgStat{0, 1, 1, 0, 0, 0, 0}), s);
+  SpgStat* d_stat = upload(db, std::vector<SpgStat>(n_calls, kStatInit), s);
   double* d_part = db.get<double>(3 * chunks.size());
   double2* d_TN = db.get<double2>((size_t)S.N);
   const dim3 gF((unsigned)F), bT(kT);
   clk.stamp();
-  for (int pass = 0; pass < 2; ++pass) {
-    hipLaunchKernelGGL(sg_spg_stats<T>, dim3((unsigned)chunks.size()), bT, 0, s, d_x, d_ch, d_snd, d_stat, pass, d_part);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(sg_spg_stats_fold, dim3((NS + 63) / 64), dim3(64), 0, s, d_part, d_snd, (int)n_calls, pass, d_stat);
-    HIPCHK(hipGetLastError());
-  }
+  stats_launch<T>(d_x, d_ch, chunks.size(), d_snd, n_calls, d_stat, d_part, s);
   if (d_stat_out)  // for a caller that goes on with the normalised samples (sg_analyze.hip)
     HIPCHK(hipMemcpyAsync(d_stat_out, d_stat, (size_t)n_calls * sizeof(SpgStat), hipMemcpyDeviceToDevice, s));
   clk.stamp();  // 1: frames
@@ -645,6 +670,28 @@ void spectrogram_device(const SpgSetup& S, const T* d_x, const int64_t* offsets,
   clk.finish();  // 'original' stops after the frames: stamps 0, 1, 2; 'processed' records all 13
 }
 
+template <typename T>
+void spg_stats_device(const T* d_x, const int64_t* offsets, const int64_t* lengths, int64_t n_calls, SpgStat* d_stat,
+                      hipStream_t s) {
+  if (n_calls == 0) return;
+  std::vector<SpgSound> snds(n_calls);
+  std::vector<SpgChunk> chunks;
+  for (int64_t c = 0; c < n_calls; ++c) {
+    const int64_t len = lengths[c] > 0 ? lengths[c] : 0;
+    snds[c] = SpgSound{offsets[c], len, {0, 0}, 0, 0, stat_chunks(chunks, c, len), 0};
+  }
+  DevBuf db;
+  const SpgSound* d_snd = upload(db, snds, s);
+  const SpgChunk* d_ch = upload(db, chunks, s);
+  const SpgStat* d_init = upload(db, std::vector<SpgStat>(n_calls, kStatInit), s);
+  double* d_part = db.get<double>(3 * chunks.size());
+  HIPCHK(hipMemcpyAsync(d_stat, d_init, (size_t)n_calls * sizeof(SpgStat), hipMemcpyDeviceToDevice, s));
+  stats_launch<T>(d_x, d_ch, chunks.size(), d_snd, n_calls, d_stat, d_part, s);
+  HIPCHK(hipStreamSynchronize(s));  // db goes away
+}
+
+template void spg_stats_device<float>(const float*, const int64_t*, const int64_t*, int64_t, SpgStat*, hipStream_t);
+template void spg_stats_device<double>(const double*, const int64_t*, const int64_t*, int64_t, SpgStat*, hipStream_t);
 template void spectrogram_device<float>(const SpgSetup&, const float*, const int64_t*, const int64_t*, int64_t, double*,
                                         const int64_t*, int32_t*, int32_t*, hipStream_t, double*, SpgStat*);
 template void spectrogram_device<double>(const SpgSetup&, const double*, const int64_t*, const int64_t*, int64_t,

@@ -153,6 +153,14 @@ def lib():
         L.sg_analyze_summary_batch.argtypes = [vp, vp, i64p, i64p, i64, fpp, vp, i64p, i32p, vp]
         L.sg_analyze_summary_sound.argtypes = [vp, dp, i64, fpp, dp, dp]
         L.sg_debug_summary_kernel_ms.argtypes = [dp]
+    if hasattr(L, "sg_formants_size"):  # analyze()'s formant tracks: likewise additive
+        i32p = C.POINTER(C.c_int32)
+        app = C.POINTER(_abi.sg_analyze_params)
+        L.sg_formants_size.argtypes = [app, C.c_int32, i32p, i32p]
+        L.sg_formants_batch.argtypes = [vp, vp, i64p, i64p, i64, app, C.c_int32, vp, i64p, C.c_int32, i32p, vp, i64p]
+        L.sg_formants_sound.argtypes = [vp, dp, i64, app, C.c_int32, dp]
+        L.sg_formants_frames.argtypes = [vp, dp, C.c_int32, C.c_int32, C.c_double, C.c_int32, dp]
+        L.sg_debug_formants_kernel_ms.argtypes = [dp, i64p]
     if hasattr(L, "sg_segment_size"):  # segment(): likewise additive
         i32p = C.POINTER(C.c_int32)
         gpp = C.POINTER(_abi.sg_segment_params)
