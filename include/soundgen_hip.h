@@ -708,6 +708,25 @@ int sg_formants_sound(sg_ctx* ctx, const double* wave, int64_t len, const sg_ana
  * out (host) receives nframes x 2 nFormants doubles. */
 int sg_formants_frames(sg_ctx* ctx, const double* frames, int32_t n, int32_t nframes, double fs, int32_t nFormants,
                        double* out);
+/* phonTools::findformants(sound, fs, verify = FALSE) on a whole sound of any length (matchPars'
+ * initial formants, R/matchPars.R:130; an additive extension of ABI 5): the steps above with
+ * the Hann window over all len samples, no gate, no normalisation, no analysis window. The
+ * sound is cut into chunks of `chunk` samples; the mean and every lag are sums of per-chunk
+ * sums folded in chunk order, so that a sound's row is the same bit for bit alone, in any
+ * batch and at any position of it. A row is 2 * 8 doubles: (formant, bandwidth) pairs in
+ * ascending order of formant, NaN behind the kept ones; more than 8 kept roots are not
+ * returned.
+ * Host only, no GPU call: the order round(fs / 1000) + 3, the chunk size and the chunks of a
+ * sound of len samples (0 for len <= 0). SG_E_UNSUPPORTED for an order above 64 and for a len
+ * whose chunk count does not fit an int32. */
+int sg_formants_whole_size(double fs, int64_t len, int32_t* order, int32_t* chunk, int64_t* nchunks);
+/* One sound from host memory; out (host) receives the 16 doubles. SG_E_ARG for len <= order. */
+int sg_formants_whole(sg_ctx* ctx, const double* wave, int64_t len, double fs, double* out);
+/* n_calls sounds in DEVICE memory (as for sg_analyze_frames_batch): call c's row goes to
+ * d_out + 16 c in DEVICE memory. A call with lengths[c] <= order (a failed call's length < 0
+ * too) gets a NaN row. Returns when the stream has finished. */
+int sg_formants_whole_batch(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, const int64_t* lengths,
+                            int64_t n_calls, double fs, double* d_out);
 /* segment() (an additive extension of ABI 5; R/segment.R:79-219, R/utilities_segment.R):
  * the smoothed Hilbert envelope of the whole sound (seewave::env(envt = "hil", msmooth =
  * c(windowLength_points, overlap)): a transform of 2^ceiling(log2(len)) points), the
@@ -958,6 +977,10 @@ int sg_debug_summary_kernel_ms(double* out);
  * (2 doubles), and, of the last run, profiled or not (counts: 3 int64, or NULL): the frames
  * that hit the iteration cap, the frames analysed, and the Aberth iterations those took. */
 int sg_debug_formants_kernel_ms(double* out, int64_t* counts);
+/* The same for the last sg_formants_whole / sg_formants_whole_batch run: the device
+ * milliseconds of the mean (chunk sums and their fold), the chunk lags, the fold of the lags
+ * and sg_fmt_roots (4 doubles), and the three counters over the sounds analysed. */
+int sg_debug_formants_whole_kernel_ms(double* out, int64_t* counts);
 /* The same for the last sg_segment / sg_segment_batch run, summed over the chunks of a
  * batch: the normalization statistics, the forward columns with their twiddle (or the
  * whole transform of a sound of at most 2048 points), the rows (forward, the Hilbert

@@ -222,6 +222,23 @@ SG_FMT_HD inline int fmt_frame(FmtShared& sh, int p, double fs, int nFormants, i
   return it;
 }
 
+// ---- findformants on a whole sound (matchPars: R/matchPars.R:130): the same steps over all N
+// samples. The sound is cut into chunks of kFmtSoundChunk samples; the mean and every lag are
+// sums of per-chunk sums, folded in chunk order (sg_formants.hip: sg_fmt_sound_*).
+// Inside a chunk a lag's sum is split into segments, summed in index order and folded in
+// segment order: as many segments as a workgroup of kFmtSoundThreads threads can give to
+// each group of kFmtSoundLagWidth lags, of an odd number of samples (the device's LDS banks).
+constexpr int kFmtSoundChunk = 4096;
+constexpr int kFmtSoundThreads = 256;
+constexpr int kFmtSoundLagWidth = 8;
+SG_FMT_HD inline int64_t fmt_sound_chunks(int64_t n) { return n <= 0 ? 0 : (n + kFmtSoundChunk - 1) / kFmtSoundChunk; }
+SG_FMT_HD inline int fmt_sound_groups(int p) { return (p + kFmtSoundLagWidth) / kFmtSoundLagWidth; }  // covering 0..p
+SG_FMT_HD inline int fmt_sound_segments(int p) { return kFmtSoundThreads / fmt_sound_groups(p); }
+SG_FMT_HD inline int fmt_sound_seglen(int p) { return ((kFmtSoundChunk + fmt_sound_segments(p) - 1) / fmt_sound_segments(p)) | 1; }
+// the window and steps 2-4 with the sample's index in a sound longer than an int holds
+SG_FMT_HD inline double fmt_hann(int64_t i, int64_t n) { return 0.5 * (1 - cos(kFmtTwoPi * (double)i / (double)(n - 1))); }
+SG_FMT_HD inline double fmt_shape(double y, double mean, int64_t i, int64_t n) { return (y - mean) * fmt_hann(i, n); }
+
 // the one lane of the host
 struct FmtHostOps {
   void sync() const {}
@@ -243,6 +260,44 @@ inline void fmt_lags_host(const double* x, int n, double fs, int p, double* y, d
     double s = 0;
     for (int i = 0; i + k < n; ++i) s += y[i] * y[i + k];
     r[k] = s;
+  }
+}
+
+// The lags of a whole sound of n samples on the host, in the device's chunk order: the mean
+// from the chunks' sums of the pre-emphasised samples, folded in chunk order; lag k from the
+// chunks' partial sums over the i of the chunk (y[i + k] read across the chunk's end, nothing
+// past the sound's), folded in chunk order; a chunk's partial sum in the device's segments.
+// y: n doubles of work space; r[0..p]. What is left to differ from the device: the order
+// inside a chunk's sum for the mean, and the device's fused multiply-adds.
+inline void fmt_sound_lags_host(const double* x, int64_t n, double fs, int p, double* y, double* r) {
+  const double coeff = fmt_preemph_coeff(fs);
+  const int64_t nchunks = fmt_sound_chunks(n);
+  double mean = 0;
+  for (int64_t c = 0; c < nchunks; ++c) {
+    const int64_t i0 = c * kFmtSoundChunk, i1 = i0 + kFmtSoundChunk < n ? i0 + kFmtSoundChunk : n;
+    double s = 0;
+    for (int64_t i = i0; i < i1; ++i) {
+      y[i] = i == 0 ? x[i] : x[i] + coeff * x[i - 1];
+      s += y[i];
+    }
+    mean += s;
+  }
+  mean /= (double)n;
+  for (int64_t i = 0; i < n; ++i) y[i] = fmt_shape(y[i], mean, i, n);
+  for (int k = 0; k <= p; ++k) r[k] = 0;
+  const int S = fmt_sound_segments(p), L = fmt_sound_seglen(p);
+  for (int64_t c = 0; c < nchunks; ++c) {
+    const int64_t i0 = c * kFmtSoundChunk, i1 = i0 + kFmtSoundChunk < n ? i0 + kFmtSoundChunk : n;
+    for (int k = 0; k <= p; ++k) {
+      double s = 0;
+      for (int g = 0; g < S; ++g) {
+        const int64_t a = i0 + (int64_t)g * L < i1 ? i0 + (int64_t)g * L : i1, b = a + L < i1 ? a + L : i1;
+        double t = 0;
+        for (int64_t i = a; i < b && i + k < n; ++i) t += y[i] * y[i + k];
+        s += t;
+      }
+      r[k] += s;
+    }
   }
 }
 

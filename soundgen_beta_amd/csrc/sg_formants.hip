@@ -15,6 +15,8 @@
 //                 the conversion, the rank-counting sort and the selection. The waves of a
 //                 workgroup never meet: every synchronisation is the wave's own
 // A frame that Levinson-Durbin refuses or that hits the iteration cap gets a NaN row.
+// findformants on a whole sound (matchPars' initial formants) does not fit that LDS:
+// sg_fmt_sound_* below cut the sound into chunks and feed the same sg_fmt_roots.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -242,9 +244,278 @@ void formants_device(const sg::AnlSetup& A, int order, int nFormants, const T* d
   formants_launch<T>(d_x, fr, d_stat, d_win, d_tables, make_k(wl, order, nFormants, 1, A.spg.sr), d_fmt, s, kernel_ms);
 }
 
+// ---------------------------------------------------------------- a whole sound
+// findformants on all N samples of a sound (matchPars, R/matchPars.R:130). The frame no longer
+// fits LDS, so the sound is cut into chunks of kC = sg::kFmtSoundChunk samples:
+//   sg_fmt_sound_sums   one workgroup per chunk: the sum of its pre-emphasised samples
+//   sg_fmt_sound_mean   one thread per sound: its chunks' sums in chunk order, over N
+//   sg_fmt_sound_lags   one workgroup per chunk: the chunk and a halo of order + kSndPad
+//                       samples behind it, shaped with the sample's index in the sound (zeros
+//                       past the sound's end), into LDS; then the chunk's part of r[0..order]
+//   sg_fmt_sound_fold   one workgroup per sound: lag k over its chunks in chunk order, into
+//                       the row sg_fmt_roots reads; a sound not longer than the order gets NaN
+//   sg_fmt_roots        as for frames, gate -1, nFormants = kFmtMaxFormants
+// sg_fmt_sound_lags: the lags go in groups of kSndW = 8, G = ceil((order + 1) / 8) of them, and
+// the chunk's samples in S = 256 / G segments of L = ceil(kC / S) | 1 samples (odd: the lanes'
+// segment starts then fall on different LDS banks). Thread t < G S sums segment t % S of lag
+// group t / S in index order, the eight lags' window sliding through registers (2 LDS reads
+// for 8 multiply-adds); thread k <= order then folds lag k's S segment sums in index order.
+// Every order depends on (N, order, kC) alone: no atomics, the same bits in any batch.
+constexpr int kC = sg::kFmtSoundChunk;
+constexpr int kSndW = sg::kFmtSoundLagWidth;  // lags of a group
+constexpr int kSndPad = kSndW - 1;        // the last group's later lags run this far behind the halo
+constexpr int kSndY = kC + sg::kFmtMaxOrder + kSndPad + 1;  // doubles of the shaped chunk
+constexpr int kSndGroupsMax = (sg::kFmtMaxOrder + kSndW) / kSndW;
+constexpr int kSndPart = kSndW * kT + kSndW * kSndGroupsMax;  // kSndW G (S | 1) <= this
+constexpr int kFmtWholeStages = 4;        // sg_debug_formants_whole_kernel_ms
+static_assert(kT == sg::kFmtSoundThreads &&(kSndY + kSndPart + kT) * sizeof(double) <= 65536, "sg_fmt_sound_lags: LDS");
+
+struct FmtChunk {
+  int64_t x0;  // first sample of the chunk's sound in the input buffer
+  int64_t n;   // samples of that sound
+  int64_t i0;  // first sample of the chunk in the sound
+  int32_t snd, pad;
+};
+
+struct FmtSound {
+  int64_t n;       // samples; analysed when n > order
+  int64_t chunk0;  // its first chunk in the launch
+  int32_t chunks;
+  int32_t row;     // its row of lags (the frame index of sg_fmt_roots); -1: not analysed
+};
+
+// pre-emphasised sample i of the sound at xs
+template <typename T>
+__device__ __forceinline__ double snd_preemph(const T* __restrict__ xs, int64_t i, double coeff) {
+  const double cur = (double)xs[i];
+  return i == 0 ? cur : cur + coeff * (double)xs[i - 1];
+}
+
+template <typename T>
+__global__ __launch_bounds__(kT) void sg_fmt_sound_sums(const T* __restrict__ x, const FmtChunk* __restrict__ chunks,
+                                                        double coeff, double* __restrict__ sums) {
+  __shared__ double red[kT];
+  const FmtChunk Q = chunks[blockIdx.x];
+  const T* xs = x + Q.x0;
+  const int nc = (int)min((int64_t)kC, Q.n - Q.i0);
+  double acc = 0;
+  for (int l = threadIdx.x; l < nc; l += kT) acc += snd_preemph(xs, Q.i0 + l, coeff);
+  const double s = block_reduce<kT>(acc, 0, red);
+  if (threadIdx.x == 0) sums[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(kT) void sg_fmt_sound_mean(const FmtSound* __restrict__ sounds, int nsounds,
+                                                        const double* __restrict__ sums, double* __restrict__ mean) {
+  const int c = blockIdx.x * kT + threadIdx.x;
+  if (c >= nsounds) return;
+  const FmtSound Sd = sounds[c];
+  double s = 0;
+  for (int j = 0; j < Sd.chunks; ++j) s += sums[Sd.chunk0 + j];
+  mean[c] = Sd.n > 0 ? s / (double)Sd.n : 0.0;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kT) void sg_fmt_sound_lags(const T* __restrict__ x, const FmtChunk* __restrict__ chunks,
+                                                        const double* __restrict__ mean, int p, double coeff,
+                                                        double* __restrict__ partial) {
+  __shared__ double y[kSndY];
+  __shared__ double part[kSndPart];
+  const FmtChunk Q = chunks[blockIdx.x];
+  const T* xs = x + Q.x0;
+  const double mu = mean[Q.snd];
+  const int nc = (int)min((int64_t)kC, Q.n - Q.i0);  // samples of the chunk, >= 1
+  const int G = sg::fmt_sound_groups(p);             // groups of kSndW lags covering 0..p
+  const int S = sg::fmt_sound_segments(p);           // segments of the chunk
+  const int L = sg::fmt_sound_seglen(p);             // samples of a segment
+  const int PS = S | 1;                              // a lag's row of segment sums
+  const int ny = kC + p + kSndPad + 1;               // what the sums below may read: <= kSndY
+  for (int l = threadIdx.x; l < ny; l += kT) {
+    const int64_t i = Q.i0 + l;
+    y[l] = i < Q.n ? sg::fmt_shape(snd_preemph(xs, i, coeff), mu, i, Q.n) : 0.0;  // nothing past the sound's end
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < G * S) {
+    const int g = threadIdx.x / S, s = threadIdx.x % S;
+    const int i0 = min(s * L, nc), i1 = min(i0 + L, nc);
+    const double* q = y + kSndW * g;  // reads up to q[i1 - 1 + kSndPad] = y[<= nc - 1 + p + kSndPad]
+    double acc[kSndW], w[kSndW];
+#pragma unroll
+    for (int j = 0; j < kSndW; ++j) acc[j] = 0;
+#pragma unroll
+    for (int j = 0; j < kSndPad; ++j) w[j] = q[i0 + j];
+#pragma unroll 8
+    for (int i = i0; i < i1; ++i) {
+      const double a = y[i];
+      w[kSndPad] = q[i + kSndPad];
+#pragma unroll
+      for (int j = 0; j < kSndW; ++j) acc[j] += a * w[j];
+#pragma unroll
+      for (int j = 0; j < kSndPad; ++j) w[j] = w[j + 1];
+    }
+    double* o = part + (kSndW * g) * PS + s;
+#pragma unroll
+    for (int j = 0; j < kSndW; ++j) o[j * PS] = acc[j];
+  }
+  __syncthreads();
+  if ((int)threadIdx.x <= p) {
+    const double* o = part + threadIdx.x * PS;
+    double s = 0;
+    for (int j = 0; j < S; ++j) s += o[j];
+    partial[(int64_t)blockIdx.x * (sg::kFmtMaxOrder + 1) + threadIdx.x] = s;
+  }
+}
+
+__global__ __launch_bounds__(128) void sg_fmt_sound_fold(const FmtSound* __restrict__ sounds, const double* __restrict__ partial,
+                                                         int p, double* __restrict__ lags, double* __restrict__ out) {
+  const FmtSound Sd = sounds[blockIdx.x];
+  const int k = threadIdx.x;
+  if (Sd.row < 0) {
+    if (k < 2 * sg::kFmtMaxFormants) out[(int64_t)blockIdx.x * 2 * sg::kFmtMaxFormants + k] = NAN;
+    return;
+  }
+  if (k > p) return;
+  const double* q = partial + Sd.chunk0 * (sg::kFmtMaxOrder + 1) + k;
+  double s = 0;
+  for (int j = 0; j < Sd.chunks; ++j) s += q[(int64_t)j * (sg::kFmtMaxOrder + 1)];
+  lags[(int64_t)Sd.row * (sg::kFmtMaxOrder + 1) + k] = s;
+}
+
+double g_fmtw_ms[kFmtWholeStages];  // of the last profiled run
+int64_t g_fmtw_count[3];            // of the last run: capped, analysed, iterations
+
+// the order of findformants at fs; refuses what the wave cannot hold
+int whole_order(double fs) {
+  if (!(fs > 0) || !(fs < 1e9)) throw sg::SgError(SG_E_ARG, "formants: fs must be positive");
+  const int order = sg::fmt_order(fs);
+  if (order > sg::kFmtMaxOrder)
+    throw sg::SgError(SG_E_UNSUPPORTED, "formants: the order round(fs / 1000) + 3 = " + std::to_string(order) + " exceeds " +
+                                            std::to_string(sg::kFmtMaxOrder) + " (one root per lane of a wave)");
+  return order;
+}
+
+int64_t whole_chunks(int64_t len) {
+  const int64_t nc = sg::fmt_sound_chunks(len);
+  if (nc > 2147483647LL) throw sg::SgError(SG_E_UNSUPPORTED, "formants: the chunks of a sound exceed 2^31");
+  return nc;
+}
+
+// The five kernels on the stream for n_calls sounds of d_x; rows of 16 doubles to d_out; synchronises
+template <typename T>
+void formants_whole_device(const T* d_x, const int64_t* offsets, const int64_t* lengths, int64_t n_calls, int order, double fs,
+                           double* d_out, hipStream_t s, double* kernel_ms) {
+  sg::StageClock clk(s, kernel_ms, kFmtWholeStages);
+  clk.zero();
+  for (int k = 0; k < 3; ++k) g_fmtw_count[k] = 0;
+  if (n_calls == 0) return;
+  std::vector<FmtSound> snd((size_t)n_calls);
+  std::vector<FmtChunk> ch;
+  std::vector<FmtFrame> fr;
+  for (int64_t c = 0; c < n_calls; ++c) {
+    const int64_t n = lengths[c];
+    if (n <= order) {
+      snd[c] = FmtSound{n, (int64_t)ch.size(), 0, -1};
+      continue;
+    }
+    const int64_t nc = whole_chunks(n);
+    snd[c] = FmtSound{n, (int64_t)ch.size(), (int32_t)nc, (int32_t)fr.size()};
+    if ((int64_t)ch.size() + nc > 2147483647LL) throw sg::SgError(SG_E_UNSUPPORTED, "formants: the chunks of one launch exceed 2^31");
+    for (int64_t j = 0; j < nc; ++j) ch.push_back(FmtChunk{offsets[c], n, j * kC, (int32_t)c, 0});
+    fr.push_back(FmtFrame{offsets[c], -1, c * 2 * sg::kFmtMaxFormants, (int32_t)c, 0});
+  }
+  const int64_t F = (int64_t)fr.size(), NC = (int64_t)ch.size();
+  const FmtK K = make_k(0, order, sg::kFmtMaxFormants, 0, fs);
+  DevBuf db;
+  const FmtSound* d_snd = upload(db, snd, s);
+  const FmtChunk* d_ch = upload(db, ch, s);
+  const FmtFrame* d_fr = upload(db, fr, s);
+  double* d_sums = db.get<double>((size_t)NC);
+  double* d_mean = db.get<double>((size_t)n_calls);
+  double* d_part = db.get<double>((size_t)NC * (sg::kFmtMaxOrder + 1));
+  double* d_lags = db.get<double>((size_t)F * (sg::kFmtMaxOrder + 1));
+  FmtCount* d_count = upload(db, std::vector<FmtCount>(1, FmtCount{0, 0, 0}), s);
+  clk.stamp();  // 0: the mean
+  if (NC > 0) {
+    hipLaunchKernelGGL(sg_fmt_sound_sums<T>, dim3((unsigned)NC), dim3(kT), 0, s, d_x, d_ch, K.coeff, d_sums);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(sg_fmt_sound_mean, dim3((unsigned)((n_calls + kT - 1) / kT)), dim3(kT), 0, s, d_snd, (int)n_calls, d_sums,
+                       d_mean);
+    HIPCHK(hipGetLastError());
+  }
+  clk.stamp();  // 1: the chunks' lags
+  if (NC > 0) {
+    hipLaunchKernelGGL(sg_fmt_sound_lags<T>, dim3((unsigned)NC), dim3(kT), 0, s, d_x, d_ch, d_mean, order, K.coeff, d_part);
+    HIPCHK(hipGetLastError());
+  }
+  clk.stamp();  // 2: their fold, and the NaN rows
+  hipLaunchKernelGGL(sg_fmt_sound_fold, dim3((unsigned)n_calls), dim3(128), 0, s, d_snd, d_part, order, d_lags, d_out);
+  HIPCHK(hipGetLastError());
+  clk.stamp();  // 3: the predictor, the roots, the formants
+  if (F > 0) {
+    hipLaunchKernelGGL(sg_fmt_roots, dim3((unsigned)((F + kRootWaves - 1) / kRootWaves)), dim3(kRootWaves * 64), 0, s, d_fr, (int)F,
+                       (const double*)nullptr, d_lags, K, d_out, d_count);
+    HIPCHK(hipGetLastError());
+  }
+  clk.stamp();
+  FmtCount h{0, 0, 0};
+  HIPCHK(hipMemcpyAsync(&h, d_count, sizeof h, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  clk.finish();
+  g_fmtw_count[0] = (int64_t)h.capped;
+  g_fmtw_count[1] = (int64_t)h.analysed;
+  g_fmtw_count[2] = (int64_t)h.iterations;
+}
+
 }  // namespace
 
 extern "C" {
+
+int sg_formants_whole_size(double fs, int64_t len, int32_t* order, int32_t* chunk, int64_t* nchunks) {
+  return sg::guarded(nullptr, [&]() {
+    if (!order || !chunk || !nchunks) throw sg::SgError(SG_E_ARG, "sg_formants_whole_size: bad arguments");
+    *order = whole_order(fs);
+    *chunk = kC;
+    *nchunks = whole_chunks(len);
+    return (int)SG_OK;
+  });
+}
+
+int sg_formants_whole(sg_ctx* ctx, const double* wave, int64_t len, double fs, double* out) {
+  return sg::guarded(ctx, [&]() {
+    if (!ctx || !wave || !out) throw sg::SgError(SG_E_ARG, "sg_formants_whole: bad arguments");
+    const int order = whole_order(fs);
+    if (len <= order)
+      throw sg::SgError(SG_E_ARG, "sg_formants_whole: the sound must have more than order = " + std::to_string(order) + " samples");
+    whole_chunks(len);
+    HIPCHK(hipSetDevice(ctx->device));
+    const int64_t off = 0;
+    sg::single_sound(ctx, wave, len, 2 * sg::kFmtMaxFormants, out, [&](const double* d, double* d_o) {
+      formants_whole_device<double>(d, &off, &len, 1, order, fs, d_o, ctx->stream, ctx->profiling ? g_fmtw_ms : nullptr);
+    });
+    return (int)SG_OK;
+  });
+}
+
+int sg_formants_whole_batch(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, const int64_t* lengths, int64_t n_calls,
+                            double fs, double* d_out) {
+  return sg::guarded(ctx, [&]() {
+    if (!ctx || n_calls < 0 || n_calls > 2147483647LL || (n_calls > 0 && (!d_wave || !offsets || !lengths || !d_out)))
+      throw sg::SgError(SG_E_ARG, "sg_formants_whole_batch: bad arguments");
+    const int order = whole_order(fs);
+    for (int64_t c = 0; c < n_calls; ++c) whole_chunks(lengths[c]);
+    if (n_calls == 0) return (int)SG_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    formants_whole_device<float>(d_wave, offsets, lengths, n_calls, order, fs, d_out, ctx->stream,
+                                 ctx->profiling ? g_fmtw_ms : nullptr);
+    return (int)SG_OK;
+  });
+}
+
+int sg_debug_formants_whole_kernel_ms(double* out, int64_t* counts) {
+  if (!out) return SG_E_ARG;
+  for (int k = 0; k < kFmtWholeStages; ++k) out[k] = g_fmtw_ms[k];
+  for (int k = 0; counts && k < 3; ++k) counts[k] = g_fmtw_count[k];
+  return SG_OK;
+}
 
 int sg_formants_batch(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, const int64_t* lengths, int64_t n_calls,
                       const sg_analyze_params* p, int32_t nFormants, const double* d_tables, const int64_t* out_off,

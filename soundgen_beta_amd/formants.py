@@ -31,8 +31,11 @@ nearbyint(100 x) / 100 in fp64. The two differ only where 100 x lies within an u
 - formants / formants_batch / find_formants_frames: the same on the GPU (sg_formants.hip:
   sg_fmt_lags, one workgroup per frame; sg_fmt_roots, one wave per frame, one root per lane).
   The order is limited to 64 (samplingRate < 61.5 kHz): SoundgenError(SG_E_UNSUPPORTED) above.
-Out of scope: matchPars()' initial formants from a whole sound (a frame of that length does
-not fit the lag kernel), formants in the device summary kernel (analyze(summary=True,
+- find_formants_sound / find_formants_sounds_batch: findformants on a whole sound of any
+  length (matchPars()' initial formants, R/matchPars.R:130): the sound does not fit a frame's
+  LDS, so sg_fmt_sound_* cut it into chunks of 4096 samples whose sums are folded in chunk
+  order, then sg_fmt_roots. At most 8 kept rows are returned.
+Out of scope: formants in the device summary kernel (analyze(summary=True,
 formants=True) reduces the formant table on the host), the R binding, smoothVars on formants.
 """
 import ctypes as C
@@ -369,6 +372,72 @@ def find_formants_frames(frames, fs, nFormants=3, device=0):
     _check(native.lib().sg_formants_frames(ctx.ptr, fr.ctypes.data_as(dp), fr.shape[1], fr.shape[0], float(fs), nFormants,
                                            out.ctypes.data_as(dp)), ctx.ptr)
     return out
+
+
+# ------------------------------------------- a whole sound (matchPars; sg_fmt_sound_*)
+def formants_whole_size(fs, length):
+    """sg_formants_whole_size (host only, no GPU call): (order, chunk, nchunks) for a sound of
+    `length` samples at fs. SoundgenError(SG_E_UNSUPPORTED) for an order above 64 or more than
+    2^31 - 1 chunks."""
+    L = native.lib()
+    order, chunk, nchunks = C.c_int32(), C.c_int32(), C.c_int64()
+    native.check(L.sg_formants_whole_size(float(fs), int(length), C.byref(order), C.byref(chunk), C.byref(nchunks)))
+    return order.value, chunk.value, nchunks.value
+
+
+def _kept_rows(row):
+    m = np.asarray(row, dtype=np.float64).reshape(MAX_FORMANTS, 2)
+    return m[~np.isnan(m[:, 0])].copy()
+
+
+def find_formants_sound(x, fs, device=0):
+    """phonTools::findformants(x, fs, verify = FALSE) on a whole sound of any length on the GPU
+    (sg_formants_whole, fp64: the chunked kernels sg_fmt_sound_* of sg_formants.hip, then
+    sg_fmt_roots): the kept (formant, bandwidth) rows in ascending order of formant, an array of
+    shape (n_kept, 2). At most 8 rows are returned (a stated limit; matchPars reads 3).
+    find_formants_numpy(x, fs) is the host restatement. ValueError for a sound not longer than
+    the order; SoundgenError(SG_E_UNSUPPORTED) for an order above 64."""
+    from .analyze import _check
+    x = np.ascontiguousarray(np.asarray(x, dtype=np.float64).ravel())
+    order = formants_whole_size(fs, len(x))[0]  # the refusals that need no device
+    if len(x) <= order:
+        raise ValueError("find_formants_sound: the sound must have more than order = %d samples" % order)
+    ctx = native.default_context(device)
+    out = np.zeros(2 * MAX_FORMANTS)
+    dp = C.POINTER(C.c_double)
+    _check(native.lib().sg_formants_whole(ctx.ptr, x.ctypes.data_as(dp), len(x), float(fs), out.ctypes.data_as(dp)), ctx.ptr)
+    return _kept_rows(out)
+
+
+def find_formants_sounds_batch(data, offsets, lengths, fs, to_host=False, device=0):
+    """find_formants_sound(call i, fs) for a batch of sounds already in HBM (`data`: a float32 CUDA
+    tensor, call i at offsets[i], lengths[i] samples -- the layout of batch.synthesize_packed)
+    in one launch sequence (sg_formants_whole_batch): an fp64 CUDA tensor of shape (n_calls, 16),
+    a call's row (formant, bandwidth) pairs with NaN behind the kept ones; all NaN for a call not
+    longer than the order (a failed call of length < 0 too). A call's row is the same bit for
+    bit alone, in any batch and at any position of it. to_host=True returns the list of per-call
+    (n_kept, 2) arrays find_formants_sound() returns."""
+    from .analyze import _check
+    offs, lens, nc, p_offs, p_lens = native.batch_layout(offsets, lengths)
+    formants_whole_size(fs, int(lens.max()) if nc else 0)  # the refusals that need no device
+    ctx = native.default_context(device)
+    out = native.device_out(data, nc * 2 * MAX_FORMANTS)
+    _check(native.lib().sg_formants_whole_batch(ctx.ptr, C.c_void_p(data.data_ptr()), p_offs, p_lens, nc, float(fs),
+                                                C.c_void_p(out.data_ptr())), ctx.ptr)
+    out = out[:nc * 2 * MAX_FORMANTS].reshape(nc, 2 * MAX_FORMANTS)
+    if not to_host:
+        return out
+    return [_kept_rows(r) for r in out.cpu().numpy()]
+
+
+def formants_whole_profile():
+    """sg_debug_formants_whole_kernel_ms: (the device milliseconds of the mean, the chunk lags,
+    their fold and the roots in the last profiled run, (capped, analysed, iterations) of the last
+    run)."""
+    ms = (C.c_double * 4)()
+    n = (C.c_int64 * 3)()
+    native.lib().sg_debug_formants_whole_kernel_ms(ms, n)
+    return dict(zip(("mean", "chunk_lags", "fold", "roots"), (float(v) for v in ms))), (int(n[0]), int(n[1]), int(n[2]))
 
 
 def formants_counts():

@@ -24,10 +24,19 @@ after morph().
   through rrng.RRng), synthesize, keep a mutant that improves the similarity by
   more than minExpectedDelta, stop after maxIter non-improving candidates in a
   row. Each generation's `pop` mutants are planned and synthesized as ONE GPU
-  batch (pop = 1 is R's loop draw for draw). The starting point comes from the
-  caller (`init`): R derives it from analyze() / segment() /
-  phonTools::findformants(), the acoustic-analysis stack that is out of scope
-  (SURVEY §2).
+  batch (pop = 1 is R's loop draw for draw).
+- The starting point: match_pars_init() analyses the target as R/matchPars.R:127-153
+  does -- segment(), analyze() and phonTools::findformants() on the whole sound
+  (formants.find_formants_sound: the chunked kernels of sg_formants.hip), then nSyl,
+  sylLen, pauseLen, pitchAnchors (downsample(), R/utilities_math.R:98-106) and up
+  to three formants. match_pars_init_numpy() is the host restatement,
+  match_pars_init_batch() the same for many targets in HBM, and
+  match_pars(analyzeTarget=True) applies the updates between defaults[pars] and
+  `init`. analyzeTarget defaults to False: the start then comes from the caller
+  alone, as before. findformants is restated and unpinned against phonTools; at
+  most 8 of its rows are returned; a target without a syllable raises 'Invalid
+  initial pars' and a single syllable leaves pauseLen at its default (see
+  match_pars_init_numpy).
 Parity: restated from the sources; no R here, so the similarity values are
 checked against hand-derived cases (tests/test_matchpars.py).
 """
@@ -469,14 +478,146 @@ def compare_sounds_batch(targetSpec, data, offsets, lengths, samplingRate, metho
     return {m: out[:, k] for k, m in enumerate(_METHOD_ORDER) if m in method}, summ
 
 
+# ------------------------------------------- matchPars' starting point from the target
+def _r_seq_len(frm, to, n):
+    """seq(from, to, length.out = n) (seq.default): from, from + (1..n - 2) by, to with by =
+    (to - from) / (n - 1), in fp64."""
+    n = int(n)
+    if n <= 0:
+        return np.zeros(0)
+    if n == 1:
+        return np.array([float(frm)])
+    if n == 2 or frm == to:
+        return np.array([float(frm), float(to)]) if n == 2 else np.full(n, float(frm))
+    by = (float(to) - float(frm)) / (n - 1)
+    return np.concatenate([[float(frm)], float(frm) + np.arange(1, n - 1, dtype=np.float64) * by, [float(to)]])
+
+
+def downsample(s, srNew=10, srOld=120, minLen=3):
+    """downsample(), R/utilities_math.R:98-106: s[seq(1, l, length.out = min(l, max(minLen,
+    round(l / srOld * srNew))))], the input itself unless srNew < srOld. round is R's (half to
+    even); a fractional index of seq() is truncated, as R's `[` truncates it."""
+    s = np.asarray(s, dtype=np.float64)
+    if not srNew < srOld:
+        return s
+    l = len(s)
+    dur = l / srOld
+    idx = _r_seq_len(1, l, min(l, max(minLen, _r_round(dur * srNew))))
+    return s[np.trunc(idx).astype(np.int64) - 1]
+
+
+def _init_updates(syllables, bursts, pitch, found, step):
+    """R/matchPars.R:132-153 from segment()'s tables, analyze()'s pitch and findformants' rows."""
+    out = {"nSyl": max(len(bursts["time"]), 1)}                              # :132
+    if "sylLen" not in syllables or len(syllables["sylLen"]) == 0:
+        raise ValueError("Invalid initial pars")  # sylLen = round(mean(NULL)) is NA: soundgen() fails, :168-171
+    from .segment import r_mean, r_median
+    out["sylLen"] = _r_round(r_mean(syllables["sylLen"]))                    # :133
+    pl = np.asarray(syllables["pauseLen"], dtype=np.float64)
+    pl = pl[~np.isnan(pl)]
+    if len(pl):                                                              # :134-137
+        out["pauseLen"] = _r_round(r_median(pl))
+    p = np.asarray(pitch, dtype=np.float64)
+    p = downsample(p[~np.isnan(p)], srNew=5, srOld=1 / step * 1000)          # :139-140
+    if len(p) > 1:                                                           # :141-145
+        out["pitchAnchors"] = {"time": [float(np.round(t, 2)) for t in _r_seq_len(0, 1, len(p))],
+                               "value": [_r_round(v) for v in p]}
+    found = np.asarray(found, dtype=np.float64).reshape(-1, 2)
+    if len(found):                                                           # :146-153
+        out["formants"] = {"f%d" % (f + 1): {"time": 0, "freq": _r_round(found[f, 0]), "amp": 30,
+                                             "width": _r_round(found[f, 1])} for f in range(min(3, len(found)))}
+    return out
+
+
+def _init_step(windowLength, overlap, step):
+    return windowLength * (1 - overlap / 100) if step is None else step
+
+
+def match_pars_init_numpy(target, samplingRate, windowLength=40, overlap=50, step=None):
+    """matchPars' analysis of the target (R/matchPars.R:127-153) restated on the host from
+    segment_numpy(), analyze_numpy() and find_formants_numpy(), each with its defaults on the
+    whole sound: the dict of updates to the starting parameters,
+
+        nSyl          max(number of bursts, 1)
+        sylLen        round(mean(sylLen))
+        pauseLen      round(median(pauseLen, na.rm = TRUE))
+        pitchAnchors  {"time": round(seq(0, 1, length.out = n), 2), "value": round(p)}, p the
+                      non-NA pitch of analyze() downsampled to 5 Hz; only when n > 1
+        formants      {"f1": {"time": 0, "freq": round(f), "amp": 30, "width": round(bw)}, ...}
+                      for the first min(3, kept) rows of findformants; only when a row is kept
+
+    Quirk kept: downsample() is told srOld = 1000 / step with matchPars' own step (windowLength
+    (1 - overlap / 100) = 20 ms by default), although the pitch contour comes from analyze()
+    with its defaults, whose step is 25 ms.
+    Two cases the sources do not settle without R, decided here:
+        * a target without a syllable: sylLen = round(mean(NULL)) is NA, soundgen() fails and
+          the reference stops with 'Invalid initial pars': ValueError("Invalid initial pars");
+        * a single syllable: its pauseLen is NA, the median over no values is NA:
+          pauseLen is not in the dict (the default stays).
+    findformants is restated, unpinned against phonTools (formants.py)."""
+    from .analyze import analyze_numpy
+    from .formants import find_formants_numpy
+    from .segment import segment_numpy
+    seg = segment_numpy(target, samplingRate)                                # :128
+    aa = analyze_numpy(target, samplingRate)                                 # :129
+    af = find_formants_numpy(np.asarray(target, dtype=np.float64).ravel(), samplingRate)  # :130
+    return _init_updates(seg["syllables"], seg["bursts"], aa["pitch"], af, _init_step(windowLength, overlap, step))
+
+
+def match_pars_init(target, samplingRate, windowLength=40, overlap=50, step=None, device=0):
+    """match_pars_init_numpy() from segment(), analyze() and find_formants_sound() on the GPU
+    (the whole-sound formants: sg_formants_whole, at most 8 rows of which 3 are read)."""
+    from .analyze import analyze
+    from .formants import find_formants_sound
+    from .segment import segment
+    seg = segment(target, samplingRate, device=device)
+    aa = analyze(target, samplingRate, device=device)
+    af = find_formants_sound(target, samplingRate, device=device)
+    return _init_updates(seg["syllables"], seg["bursts"], aa["pitch"], af, _init_step(windowLength, overlap, step))
+
+
+def match_pars_init_batch(data, offsets, lengths, samplingRate, windowLength=40, overlap=50, step=None, device=0):
+    """match_pars_init() for many targets already in HBM (`data`: a float32 CUDA tensor, target i
+    at offsets[i], lengths[i] samples -- the layout of batch.synthesize_packed): one
+    segment_batch(), one analyze_batch() and one find_formants_sounds_batch(); the small
+    reductions of R/matchPars.R:132-153 run on the host. Returns a list of dicts, None where
+    match_pars_init() of that sound would raise. An entry equals match_pars_init() of the sound's
+    float32-rounded samples."""
+    from .analyze import analyze_batch
+    from .formants import find_formants_sounds_batch, formant_order
+    from .segment import segment_batch
+    seg = segment_batch(data, offsets, lengths, samplingRate, to_host=True, device=device)
+    aa = analyze_batch(data, offsets, lengths, samplingRate, to_host=True, device=device)
+    af = find_formants_sounds_batch(data, offsets, lengths, samplingRate, to_host=True, device=device)
+    st = _init_step(windowLength, overlap, step)
+    order = formant_order(samplingRate)
+    out = []
+    for i, n in enumerate(np.asarray(lengths, dtype=np.int64)):
+        if seg[i] is None or n <= order or len(aa[i]["pitch"]) == 0:
+            out.append(None)
+            continue
+        try:
+            out.append(_init_updates(seg[i]["syllables"], seg[i]["bursts"], aa[i]["pitch"], af[i], st))
+        except ValueError:
+            out.append(None)
+    return out
+
+
 # ---------------------------------------------------------------- matchPars
 def match_pars(target, samplingRate, pars, init=None, method=("cor", "cosine", "pixel", "dtw"), probMutation=.25,
                stepVariance=0.1, maxIter=50, minExpectedDelta=0.001, windowLength=40, overlap=50, step=None,
-               penalizeLengthDif=True, throwaway=-120, maxFreq=None, rng=None, pop=1, device=0, verbose=False):
+               penalizeLengthDif=True, throwaway=-120, maxFreq=None, rng=None, pop=1, device=0, verbose=False,
+               analyzeTarget=False):
     """matchPars(), R/matchPars.R:81-311, with each generation's `pop` mutants
     synthesized as one GPU batch. `rng` (rrng.RRng) supplies every draw (the
     mutations and soundgen()'s own) in R's order for pop = 1. Returns
-    {"history": [{"pars", "sim"}...], "pars": best, "evaluated": candidates}."""
+    {"history": [{"pars", "sim"}...], "pars": best, "evaluated": candidates}.
+    analyzeTarget=True: the starting point is updated from the target as the reference does
+    (:127-153, match_pars_init()) after defaults[pars] and before `init` overrides it: nSyl,
+    sylLen, pauseLen, pitchAnchors and formants are set even where `pars` does not list them
+    (formants then holds only the found ones), and `pars` may be empty when maxIter <= 1
+    ("match pars based on acoustic analysis alone"). The default False takes the starting
+    point from defaults[pars] and `init` alone, as before."""
     from . import batch
     from .rrng import RRng
     rng = rng if rng is not None else RRng(1)
@@ -486,6 +627,15 @@ def match_pars(target, samplingRate, pars, init=None, method=("cor", "cosine", "
     targetSpec = get_mel_spec_gpu(target, samplingRate, windowLength, overlap, step, throwaway, maxFreq, device)
     defaults = MATCHPARS_DEFAULTS
     parDefault = {p: copy.deepcopy(defaults[p]) for p in pars}
+    if analyzeTarget:
+        if maxIter > 1 and len(pars) < 1:
+            raise ValueError("No parameters for optimization are specified! Either list them in 'pars' or set "
+                             "'maxIter = 0'")
+        for k, v in match_pars_init(target, samplingRate, windowLength, overlap, step, device).items():
+            if k == "formants" and isinstance(parDefault.get("formants"), dict):
+                parDefault["formants"].update(v)  # parDefault$formants[[f]] = ...: the others stay
+            else:
+                parDefault[k] = v
     for k, v in (init or {}).items():
         if k not in defaults:
             raise ValueError("init parameter not recognized: %s" % k)

@@ -161,6 +161,12 @@ def lib():
         L.sg_formants_sound.argtypes = [vp, dp, i64, app, C.c_int32, dp]
         L.sg_formants_frames.argtypes = [vp, dp, C.c_int32, C.c_int32, C.c_double, C.c_int32, dp]
         L.sg_debug_formants_kernel_ms.argtypes = [dp, i64p]
+    if hasattr(L, "sg_formants_whole_size"):  # findformants on a whole sound (matchPars): likewise additive
+        i32p = C.POINTER(C.c_int32)
+        L.sg_formants_whole_size.argtypes = [C.c_double, i64, i32p, i32p, i64p]
+        L.sg_formants_whole.argtypes = [vp, dp, i64, C.c_double, dp]
+        L.sg_formants_whole_batch.argtypes = [vp, vp, i64p, i64p, i64, C.c_double, vp]
+        L.sg_debug_formants_whole_kernel_ms.argtypes = [dp, i64p]
     if hasattr(L, "sg_segment_size"):  # segment(): likewise additive
         i32p = C.POINTER(C.c_int32)
         gpp = C.POINTER(_abi.sg_segment_params)
