@@ -816,6 +816,50 @@ int sg_sweep_fitness(sg_ctx* ctx, const double* d_matrix, int64_t n_rows, int64_
  * the default; an envelope of more than 8192 values is read in place either way) or reads
  * it in place (0). The results are the same bit for bit; for measurements. */
 int sg_set_sweep_staging(int32_t mode);
+/* A parameter sweep of analyze(summary = TRUE) (an additive extension of ABI 5; what
+ * optimizePars() evaluates for analyzeFolder, R/optimize.R:95-108, :206-234): n_rows parameter
+ * rows over n_calls sounds laid out as for sg_analyze_batch. d_out (device memory): n_rows x
+ * n_calls x SG_ANALYZE_SUMMARY_COLS doubles, the row of sound c under rows[r] at (r * n_calls
+ * + c) * 44; a sound without frames under a row has 44 NaN. Each stage runs once per distinct
+ * set of the resolved decisions it reads, never of the raw arguments (step = NaN with overlap
+ * = 50 and windowLength = 50 is step = 25; autocorSmooth = NaN is its default):
+ *   frame group      equal window, step in points, window type and bins: the spectrogram, the
+ *                    amplitudes and min(ampl) once; frame groups run one after another
+ *   store group      within a frame group, for rows with 'autocor': also equal gates (silence,
+ *                    entropyThres, the entropy band) and lag band. Where two candidate groups or
+ *                    more share one and its nlag doubles per frame fit workspace_cap, the first
+ *                    keeps the gated frames' corrected autocorrelations and the others only pick
+ *                    their peaks (autocorThres, autocorSmooth, nCands) from them
+ *   candidate group  within a frame group: every decision of the per-frame kernels equal; one
+ *                    table of 15 + 6 nCands columns per sound, which the tail never rewrites
+ * The tail (path, harmonics, summary) runs for all (row, sound) pairs of a chunk of rows in one
+ * launch each; workspace_cap (bytes; 0: 1 GiB) bounds a store and the pair tables of a chunk
+ * (at least one row runs). A pair's 44 cells are sg_analyze_summary_batch's bit for bit,
+ * whatever rows and sounds share the sweep, in whatever order, under any cap, with the store on
+ * or off. Every row must have rows[0]'s samplingRate. A row that sg_analyze_size refuses (for
+ * any sound: the smoothing window) refuses the sweep before anything is launched; the text
+ * names the row ("row r: ", "row r, sound c: "). */
+int sg_analyze_sweep(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, const int64_t* lengths, int64_t n_calls,
+                     const sg_analyze_params_full* rows, int64_t n_rows, int64_t workspace_cap, double* d_out);
+/* Host only, no device: the three group numbers of every row (n_rows int32 each), numbered by
+ * first appearance; store_group is -1 for a row without 'autocor'. Store and candidate groups
+ * are numbered over the whole sweep; each lies within one frame group. Refuses what
+ * sg_analyze_sweep refuses from the rows alone; errors through sg_analyze_frames_size_error. */
+int sg_analyze_sweep_plan(const sg_analyze_params_full* rows, int64_t n_rows, int32_t* frame_group, int32_t* store_group,
+                          int32_t* cand_group);
+/* Host only: bytes[0] = the device memory the largest frame group keeps while it runs (its |X|
+ * frames and candidate tables), bytes[1] = the largest store the sweep would build (one that
+ * two candidate groups or more share; 0 if there is none), bytes[2] = the largest tail
+ * workspace of one row (its pair tables and scratch over all sounds). Also refuses a smoothing
+ * window above 64 frames for any (row, sound). */
+int sg_analyze_sweep_size(const int64_t* lengths, int64_t n_calls, const sg_analyze_params_full* rows, int64_t n_rows,
+                          int64_t* bytes);
+/* Process-wide, for measurements and tests; the results are the same bit for bit under every
+ * mode. Bit 0 (default on): the autocorrelation store; off, every candidate group computes its
+ * own autocorrelations. Bit 1: the amplitudes are computed into a frame group's first candidate
+ * table and copied into the others (default: computed into each). Bit 2: the peak picker runs
+ * as one wave per frame (default: 256 lanes). */
+int sg_set_analyze_sweep_store(int32_t mode);
 /* Process-wide policy of the fp64 filter path for later sg_plan_batch calls:
  * mode 0 never, 1 when the conditioning estimate exceeds rho (default 100),
  * 2 every filtered bout. SG_E_ARG for an invalid mode or rho. */
@@ -990,6 +1034,12 @@ int sg_debug_segment_kernel_ms(double* out);
 /* The same six stages for the last sg_segment_sweep: the first four once per sound, the
  * smoothing summed over the envelope groups, the tail summed over the chunks of rows. */
 int sg_debug_sweep_kernel_ms(double* out);
+/* The device milliseconds of the last profiled sg_analyze_sweep, summed over its frame groups,
+ * candidate groups and chunks of rows (10 doubles): spectrogram, amplitude, descriptives and
+ * dom, autocorrelation (full: sg_anl_acf with or without the store), autocorrelation (peaks
+ * only: sg_anl_acf_peaks from the store), cepstrum, BaNa, path, harmonics, summary. A stage runs
+ * from its stamp to the next stage's: it carries the host's preparation of the next launch. */
+int sg_debug_analyze_sweep_kernel_ms(double* out);
 
 #ifdef __cplusplus
 }

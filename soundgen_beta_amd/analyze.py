@@ -1875,6 +1875,108 @@ def analyze_folder(myfolder, verbose=True, samplingRate=None, silence=0.04, wind
     return dict(zip(paths, results))                                          # :925-926
 
 
+# ------------------------------------------------------------ parameter sweeps of analyze()
+SWEEP_STAGES = ("spectrogram", "amplitude", "descriptives", "autocorrelation (full)", "autocorrelation (peaks only)",
+                "cepstrum", "BaNa", "path", "harmonics", "summary")
+
+
+def _sweep_params(samplingRate, rows):
+    """The C array of sg_analyze_params_full for `rows`, dicts of analyze()'s arguments (absent:
+    the default), each repaired as analyze_batch() repairs its own. What is out of scope raises
+    here, the text naming the row. A row may carry its own samplingRate (the library then
+    refuses the sweep)."""
+    import inspect
+
+    from . import _abi
+    formals = inspect.signature(analyze_batch).parameters
+    defaults = {k: p.default for k, p in formals.items() if p.default is not inspect.Parameter.empty}
+    P = (_abi.sg_analyze_params_full * max(len(rows), 1))()
+    for r, kw in enumerate(rows):
+        unknown = [k for k in kw if k not in defaults and k != "samplingRate"]
+        if unknown:
+            raise ValueError("analyze_sweep: row %d: unused argument: %s" % (r, ", ".join(unknown)))
+        a = dict(defaults, **kw)
+        try:
+            if a["formants"]:
+                raise NotImplementedError("the formant columns are not part of a sweep")
+            if "summary" in kw and not kw["summary"]:
+                raise ValueError("a sweep gives summary rows: summary = FALSE has none")
+            if a["pathfinding"] == "slow":
+                raise NotImplementedError(_SLOW)
+            s = repair_track(repair_pitch(a.get("samplingRate", samplingRate), None, **_pitch_args(a)), **_track_args(a))
+        except (ValueError, NotImplementedError) as e:
+            raise type(e)("analyze_sweep: row %d: %s" % (r, e)) from e
+        P[r] = _track_params(s)
+    return P
+
+
+def sweep_plan(samplingRate, rows):
+    """What the rows of an analyze_sweep() share (sg_analyze_sweep_plan; host only, no GPU):
+    (frame_group, store_group, cand_group), three integer arrays with one entry per row,
+    numbered by first appearance. Rows of one frame group share the spectrogram and the
+    amplitudes; of one store group (-1: the row has no 'autocor') the autocorrelations; of one
+    candidate group everything in front of the pathfinder. The keys are the resolved decisions,
+    not the raw arguments."""
+    L = native.lib()
+    P = _sweep_params(samplingRate, rows)
+    n = len(rows)
+    g = [np.zeros(max(n, 1), dtype=np.int32) for _ in range(3)]
+    rc = L.sg_analyze_sweep_plan(P, n, *[v.ctypes.data_as(C.POINTER(C.c_int32)) for v in g])
+    if rc < 0:
+        _raise(rc, L.sg_analyze_frames_size_error().decode())
+    return tuple(v[:n] for v in g)
+
+
+def sweep_size(lengths, samplingRate, rows):
+    """sg_analyze_sweep_size (host only): the bytes of the largest frame group's spectrogram and
+    candidate tables, of the largest autocorrelation store the sweep would build (0: none is
+    shared), and of the largest tail workspace of one row: what workspace_cap is compared with.
+    Refuses what analyze_sweep() refuses for these lengths."""
+    L = native.lib()
+    P = _sweep_params(samplingRate, rows)
+    lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64))
+    out = np.zeros(3, dtype=np.int64)
+    i64p = C.POINTER(C.c_int64)
+    rc = L.sg_analyze_sweep_size(lens.ctypes.data_as(i64p), len(lens), P, len(rows), out.ctypes.data_as(i64p))
+    if rc < 0:
+        _raise(rc, L.sg_analyze_frames_size_error().decode())
+    return dict(frame_group=int(out[0]), store=int(out[1]), row=int(out[2]))
+
+
+def analyze_sweep(data, offsets, lengths, samplingRate, rows, to_host=False, workspace_cap=0, device=0):
+    """analyze(call i, samplingRate, summary = TRUE) under every row of `rows` for a batch of
+    sounds already in HBM (the layout of analyze_batch()), as one launch sequence
+    (sg_analyze_sweep): what optimizePars() evaluates for analyzeFolder. rows: a list of dicts of
+    analyze()'s arguments (absent: the default). Each stage runs once per distinct set of the
+    decisions it reads (sweep_plan()): the spectrogram and amplitudes per frame group, the
+    autocorrelations per store group, the candidates per candidate group, and the pathfinder,
+    the harmonics and the summary for all (row, sound) pairs of a chunk of rows in one launch
+    each. Returns the fp64 CUDA tensor of shape (rows, sounds, 44), the cells named by
+    SUMMARY_COLUMNS; row r of sound i equals analyze_batch(summary=True) under rows[r] bit for
+    bit, whatever the other rows and sounds, their order and workspace_cap (bytes of a store
+    and of the pair tables of a chunk of rows; 0: the library's default). to_host=True: a list
+    per row of per-sound dicts. formants=True, plot=True, summary=False and pathfinding='slow'
+    raise before anything runs; a row the library refuses refuses the sweep, the text naming
+    the row."""
+    P = _sweep_params(samplingRate, rows)
+    offs, lens, nc, p_offs, p_lens = native.batch_layout(offsets, lengths)
+    ctx = native.default_context(device)
+    width = len(SUMMARY_COLUMNS)
+    out = native.device_out(data, len(rows) * nc * width)
+    _check(native.lib().sg_analyze_sweep(ctx.ptr, C.c_void_p(data.data_ptr()), p_offs, p_lens, nc, P, len(rows),
+                                         int(workspace_cap), C.c_void_p(out.data_ptr())), ctx.ptr)
+    out = out[:len(rows) * nc * width].reshape(len(rows), nc, width)
+    return [_host_rows(m) for m in out] if to_host else out
+
+
+def sweep_kernel_ms():
+    """The device milliseconds of the stages of the last profiled analyze_sweep(), named by
+    SWEEP_STAGES (sg_debug_analyze_sweep_kernel_ms)."""
+    ms = np.zeros(len(SWEEP_STAGES))
+    native.lib().sg_debug_analyze_sweep_kernel_ms(ms.ctypes.data_as(C.POINTER(C.c_double)))
+    return dict(zip(SWEEP_STAGES, (float(v) for v in ms)))
+
+
 _FORMANT_EXPORTS = ("formants", "formants_numpy", "find_formants_numpy", "formants_batch", "find_formants_frames")
 
 

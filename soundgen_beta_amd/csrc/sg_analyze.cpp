@@ -384,6 +384,109 @@ std::vector<double> anl_filter(const AnlSetup& S) {
   return out;
 }
 
+namespace {
+
+bool same_frames(const SpgSetup& a, const SpgSetup& b) {
+  return a.sr == b.sr && a.step == b.step && a.by == b.by && a.wl == b.wl && a.pad == b.pad && a.N == b.N && a.bins == b.bins &&
+         a.wn == b.wn;
+}
+
+// what the autocorrelation of a frame and the gate in front of it read
+bool same_store(const AnlSetup& a, const AnlSetup& b) {
+  return a.silence == b.silence && a.entropyThres == b.entropyThres && a.rowLow == b.rowLow && a.rowHigh == b.rowHigh &&
+         a.lag0 == b.lag0 && a.nlag == b.nlag;
+}
+
+// every field the per-frame kernels read (the label tables follow from the ones compared)
+bool same_cands(const PitchSetup& a, const PitchSetup& b) {
+  return same_store(a, b) && a.domThres == b.domThres && a.autocorThres == b.autocorThres && a.nCands == b.nCands &&
+         a.do_autocor == b.do_autocor && a.do_dom == b.do_dom && a.cut0 == b.cut0 && a.ncut == b.ncut && a.pf_idx == b.pf_idx &&
+         a.domW == b.domW && a.acW == b.acW && a.do_cep == b.do_cep && a.do_spec == b.do_spec && a.pitchFloor == b.pitchFloor &&
+         a.pitchCeiling == b.pitchCeiling && a.cepThres == b.cepThres && a.specThres == b.specThres && a.specPeak == b.specPeak &&
+         a.specSinglePeakCert == b.specSinglePeakCert && a.specMerge == b.specMerge && a.cepL == b.cepL && a.cepPad == b.cepPad &&
+         a.cepW == b.cepW && a.cepl == b.cepl && a.cep0 == b.cep0 && a.ncep == b.ncep && a.specW == b.specW;
+}
+
+std::string sweep_row(int64_t r, int64_t c = -1) {
+  return "sg_analyze_sweep: row " + std::to_string(r) + (c >= 0 ? ", sound " + std::to_string(c) : std::string()) + ": ";
+}
+
+}  // namespace
+
+SweepPlan anl_sweep_plan(const sg_analyze_params_full* rows, int64_t n_rows) {
+  SweepPlan W;
+  W.S.reserve((size_t)n_rows);
+  W.frame_group.resize((size_t)n_rows);
+  W.store_group.resize((size_t)n_rows);
+  W.cand_group.resize((size_t)n_rows);
+  std::vector<int64_t> first_f, first_s, first_c;  // the row a group was first seen in
+  for (int64_t r = 0; r < n_rows; ++r) {
+    try {
+      W.S.push_back(track_setup(rows[r]));
+    } catch (const SgError& e) {
+      throw SgError(e.code, sweep_row(r) + e.what());
+    }
+    if (rows[r].p.a.samplingRate != rows[0].p.a.samplingRate)
+      throw SgError(SG_E_ARG, sweep_row(r) + "samplingRate is that of row 0");
+    const TrackSetup& S = W.S.back();
+    size_t f = 0, s = 0, c = 0;
+    while (f < first_f.size() && !same_frames(W.S[first_f[f]].spg, S.spg)) ++f;
+    if (f == first_f.size()) first_f.push_back(r);
+    W.frame_group[r] = (int32_t)f;
+    if (S.do_autocor) {
+      while (s < first_s.size() && !(W.frame_group[first_s[s]] == (int32_t)f && same_store(W.S[first_s[s]], S))) ++s;
+      if (s == first_s.size()) first_s.push_back(r);
+      W.store_group[r] = (int32_t)s;
+    } else {
+      W.store_group[r] = -1;
+    }
+    while (c < first_c.size() && !(W.frame_group[first_c[c]] == (int32_t)f && same_cands(W.S[first_c[c]], S))) ++c;
+    if (c == first_c.size()) first_c.push_back(r);
+    W.cand_group[r] = (int32_t)c;
+  }
+  W.n_frame = (int)first_f.size();
+  W.n_store = (int)first_s.size();
+  W.n_cand = (int)first_c.size();
+  return W;
+}
+
+void anl_sweep_bytes(const SweepPlan& W, const int64_t* lengths, int64_t n_calls, int64_t* bytes) {
+  const int64_t n_rows = (int64_t)W.S.size();
+  bytes[0] = bytes[1] = bytes[2] = 0;
+  std::vector<int64_t> frames((size_t)W.n_frame, 0), persist((size_t)W.n_frame, 0);
+  std::vector<int> seen_c((size_t)W.n_cand, 0), users((size_t)std::max(W.n_store, 1), 0);
+  std::vector<int> seen_f((size_t)W.n_frame, 0);
+  for (int64_t r = 0; r < n_rows; ++r) {
+    const TrackSetup& S = W.S[r];
+    const int f = W.frame_group[r];
+    int64_t F = 0;
+    for (int64_t c = 0; c < n_calls; ++c) {
+      const int nf = anl_frames(S, lengths[c]);
+      try {
+        (void)track_hw(S.smooth, S.spg.sr, lengths[c], nf);
+      } catch (const SgError& e) {
+        throw SgError(e.code, sweep_row(r, c) + e.what());
+      }
+      F += nf;
+    }
+    if (!seen_f[f]) {
+      seen_f[f] = 1;
+      frames[f] = F;
+      persist[f] = F * S.spg.bins * (int64_t)sizeof(double);
+    }
+    if (!seen_c[W.cand_group[r]]) {
+      seen_c[W.cand_group[r]] = 1;
+      persist[f] += F * (S.cols - kPathCols) * (int64_t)sizeof(double);
+      if (W.store_group[r] >= 0) ++users[W.store_group[r]];
+    }
+    bytes[2] = std::max(bytes[2], F * (S.cols + path_stride(S.nCands)) * (int64_t)sizeof(double));
+  }
+  for (int f = 0; f < W.n_frame; ++f) bytes[0] = std::max(bytes[0], persist[f]);
+  for (int64_t r = 0; r < n_rows; ++r)
+    if (W.store_group[r] >= 0 && users[W.store_group[r]] >= 2)
+      bytes[1] = std::max(bytes[1], frames[W.frame_group[r]] * W.S[r].nlag * (int64_t)sizeof(double));
+}
+
 }  // namespace sg
 
 namespace {
@@ -541,6 +644,31 @@ extern "C" int sg_analyze_size(int64_t len, const sg_analyze_params_full* p, int
       std::memcpy(extra, e, sizeof e);
     }
   });
+}
+
+extern "C" int sg_analyze_sweep_plan(const sg_analyze_params_full* rows, int64_t n_rows, int32_t* frame_group,
+                                     int32_t* store_group, int32_t* cand_group) {
+  if (n_rows < 0 || (n_rows > 0 && (!rows || !frame_group || !store_group || !cand_group))) {
+    g_anl_err = "sg_analyze_sweep_plan: bad arguments";
+    return SG_E_ARG;
+  }
+  return size_guard([&]() {
+    const sg::SweepPlan W = sg::anl_sweep_plan(rows, n_rows);
+    for (int64_t r = 0; r < n_rows; ++r) {
+      frame_group[r] = W.frame_group[r];
+      store_group[r] = W.store_group[r];
+      cand_group[r] = W.cand_group[r];
+    }
+  });
+}
+
+extern "C" int sg_analyze_sweep_size(const int64_t* lengths, int64_t n_calls, const sg_analyze_params_full* rows,
+                                     int64_t n_rows, int64_t* bytes) {
+  if (n_rows < 0 || n_calls < 0 || !bytes || (n_rows > 0 && !rows) || (n_calls > 0 && !lengths)) {
+    g_anl_err = "sg_analyze_sweep_size: bad arguments";
+    return SG_E_ARG;
+  }
+  return size_guard([&]() { sg::anl_sweep_bytes(sg::anl_sweep_plan(rows, n_rows), lengths, n_calls, bytes); });
 }
 
 extern "C" const char* sg_analyze_frames_size_error(void) { return g_anl_err.c_str(); }

@@ -109,4 +109,25 @@ void analyze_device(const AnlSetup& S, const T* d_x, const int64_t* offsets, con
 // the path stage alone on n rows of P.cols doubles already on the device (sg_pitch_path)
 void path_device(const PathPars& P, int frames, int hw, double* d_rows, hipStream_t s, double* kernel_ms);
 
+// A parameter sweep of analyze(summary = TRUE) (sg_analyze_sweep): what the rows may share, decided from the
+// resolved setups alone. Groups are numbered by first appearance.
+//   frame group: equal SpgSetup, so equal frames and amplitude windows; owns |X|, the statistics, min(ampl)
+//   store group (within a frame group; -1 without 'autocor'): also equal gates (silence, entropyThres, rowLow,
+//     rowHigh) and lag band (lag0, nlag); owns the corrected autocorrelations of the gated frames
+//   candidate group (within a frame group): every field of AnlSetup and PitchSetup equal; owns one candidate
+//     table of kAnlFixed + 6 nCands columns per sound
+constexpr int kSweepStages = 10;  // sg_debug_analyze_sweep_kernel_ms
+constexpr int64_t kSweepWorkspaceCap = 1ll << 30;  // bytes of a store and of a chunk's pair tables, workspace_cap = 0
+struct SweepPlan {
+  std::vector<TrackSetup> S;  // per row
+  std::vector<int32_t> frame_group, store_group, cand_group;
+  int n_frame = 0, n_store = 0, n_cand = 0;
+};
+// every row through track_setup(); SG_E_* with "row r: " in front of the text for a refused row and for a row whose
+// samplingRate is not rows[0]'s
+SweepPlan anl_sweep_plan(const sg_analyze_params_full* rows, int64_t n_rows);
+// the bytes sg_analyze_sweep_size reports: bytes[0] the largest frame group's |X| and candidate tables, bytes[1] the
+// largest store that at least two candidate groups share (0: none), bytes[2] the largest tail workspace of one row
+void anl_sweep_bytes(const SweepPlan& W, const int64_t* lengths, int64_t n_calls, int64_t* bytes);
+
 }  // namespace sg

@@ -34,6 +34,18 @@
 //   sg_anl_summary one 256-lane workgroup per sound (sg::sum_sound, sg_summary.h): duration,
 //                 the proportion of voiced frames, and the mean, median and sd of the 14
 //                 acoustic variables over their non-NA frames, from the finished table
+// A parameter sweep (sg_analyze_sweep: what optimizePars() evaluates for analyzeFolder) runs the
+// same kernels once per distinct set of the decisions each reads (sg_analyze.h, SweepPlan): the
+// spectrogram and sg_anl_ampl per frame group; sg_anl_spec, sg_anl_cep, sg_anl_bana per candidate
+// group into that group's candidate table; sg_anl_acf<T, true> once per store group, keeping the
+// gated frames' corrected autocorrelations in HBM, and for the store's other candidate groups
+//   sg_anl_acf_peaks  one workgroup per cond_entropy frame: the stored values to LDS, then the
+//                 peak picker (SG_ACF_PEAKS, the tail of sg_anl_acf) under the group's own
+//                 autocorThres, autocorSmooth and nCands
+// and then, for all (row, sound) pairs of a chunk of rows in one launch each,
+//   sg_anl_sweep_path  sg::path_sound_at from the shared candidate table into the pair's own
+//   sg_anl_sweep_harm  sg_anl_harm on grid (frames, rows of the chunk)
+// and sg_anl_summary once per row. A pair's cells are those of sg_analyze_summary_batch bit for bit.
 // Cumulative sums run in index order: a thread sums a contiguous run, one thread
 // folds the 256 run sums in order, and the runs are rescanned from their offsets,
 // so a frame's result does not depend on the launch it is in.
@@ -265,13 +277,82 @@ __global__ __launch_bounds__(kT) void sg_anl_spec(const AnlFrame* __restrict__ f
   }
 }
 
+// What getPitchAutocor (:250-324) makes of a frame's nl corrected autocorrelations and the dom
+// certainty behind it (:151-159): HNR = max(a$amp); the peaks (a centred window of acW rows whose
+// first maximum is its middle and exceeds autocorThres), the 0.975 rule, the 1.8 rule, the
+// ordered candidates, the HNR >= 1 clamp. The tail of sg_anl_acf and the body of
+// sg_anl_acf_peaks, for a workgroup of NT threads; it reads the names of the kernel it stands
+// in: amp (nl doubles of LDS), pk (room for nl ints of LDS), npk (an int of LDS), red (NT
+// doubles of LDS), nl, K, lagf, row. The peak list is unordered; every use is decided by
+// (value, index), not by the list's order. Every value written is a copy of one of amp[] or
+// lagf[] and every decision a comparison, so the result depends neither on NT nor on who
+// computed amp[].
+// A macro and not a function: as a __device__ function (forced inline or not, the constants by
+// reference, by value or as scalars: twenty variants) sg_anl_acf compiled to 46 VGPRs where
+// the one-piece kernel has 44; as text it is the one-piece kernel.
+#define SG_ACF_PEAKS(NT)                                                                                  \
+  if (threadIdx.x == 0) npk = 0;                                                                          \
+  __syncthreads();                                                                                        \
+  double hn = -INFINITY;                                                                                  \
+  for (int i = threadIdx.x; i < nl; i += NT) hn = fmax(hn, amp[i]);                                       \
+  hn = block_reduce<NT>(hn, 2, red);                                                                      \
+  const int h = K.acW / 2;                                                                                \
+  for (int c = h + threadIdx.x; c < nl - h; c += NT) {                                                    \
+    const double v = amp[c];                                                                              \
+    if (!(v > K.autocorThres)) continue;                                                                  \
+    bool ok = true;                                                                                       \
+    for (int j = c - h; j < c && ok; ++j) ok = amp[j] < v || amp[j] != amp[j];                            \
+    for (int j = c + 1; j <= c + h && ok; ++j) ok = amp[j] <= v || amp[j] != amp[j];                      \
+    if (ok) pk[atomicAdd(&npk, 1)] = c; /* at most nl - 2 h entries */                                    \
+  }                                                                                                       \
+  __syncthreads();                                                                                        \
+  if (threadIdx.x != 0) return;                                                                           \
+  const int P = npk;                                                                                      \
+  double HNR = hn > -INFINITY ? hn : NAN;                                                                 \
+  if (P > 0) {                                                                                            \
+    double pmax = -INFINITY;                                                                              \
+    for (int q = 0; q < P; ++q) pmax = fmax(pmax, amp[pk[q]]);                                            \
+    int ibest = nl; /* which(amp > 0.975 * max(amp))[1] */                                                \
+    for (int q = 0; q < P; ++q)                                                                           \
+      if (amp[pk[q]] > 0.975 * pmax && pk[q] < ibest) ibest = pk[q];                                      \
+    const double cutf = lagf[ibest] / 1.8; /* peaks with freq > bestFreq / 1.8 */                         \
+    /* order(amp, decreasing = TRUE): the larger first, the earlier row on ties */                        \
+    double lastv = INFINITY;                                                                              \
+    int lasti = -1;                                                                                       \
+    for (int n = 0; n < K.nCands; ++n) {                                                                  \
+      int bi = -1;                                                                                        \
+      double bv = -INFINITY;                                                                              \
+      for (int q = 0; q < P; ++q) {                                                                       \
+        const int i = pk[q];                                                                              \
+        const double v = amp[i];                                                                          \
+        if (!(lagf[i] > cutf)) continue;                                                                  \
+        if (!(v < lastv || (v == lastv && i > lasti))) continue; /* already taken */                      \
+        if (bi < 0 || v > bv || (v == bv && i < bi)) {                                                    \
+          bi = i;                                                                                         \
+          bv = v;                                                                                         \
+        }                                                                                                 \
+      }                                                                                                   \
+      if (bi < 0) break;                                                                                  \
+      row[sg::kAnlFixed + n] = lagf[bi];                                                                  \
+      row[sg::kAnlFixed + K.nCands + n] = bv;                                                             \
+      lastv = bv;                                                                                         \
+      lasti = bi;                                                                                         \
+    }                                                                                                     \
+  }                                                                                                       \
+  if (HNR >= 1.0) HNR = 0.9999;                                                                           \
+  row[sg::kHNR] = HNR;                                                                                    \
+  if (row[sg::kDom] == row[sg::kDom] && HNR == HNR) row[sg::kDomCert] = 1.0 / (1.0 + exp(3.0 * HNR - 1.0));
+
 // LDS: wl + 4 doubles (the demeaned windowed frame and 4 zeros, later the peak list), nlag
-// doubles (the corrected autocorrelation)
-template <typename T>
+// doubles (the corrected autocorrelation). kStore (a sweep's first candidate group of a store
+// group): the frame's nlag corrected values also go to store + blockIdx.x * nlag, for
+// sg_anl_acf_peaks
+template <typename T, bool kStore>
 __global__ __launch_bounds__(kT) void sg_anl_acf(const T* __restrict__ x, const AnlFrame* __restrict__ frames,
                                                  const AnlSound* __restrict__ snds, const SpgStat* __restrict__ stat,
                                                  const double* __restrict__ win, const double* __restrict__ filt,
-                                                 const double* __restrict__ lagf, AnlK K, double* __restrict__ out) {
+                                                 const double* __restrict__ lagf, AnlK K, double* __restrict__ out,
+                                                 double* __restrict__ store) {
   extern __shared__ double lds_acf[];
   __shared__ double red[kT];
   __shared__ int npk;
@@ -337,65 +418,37 @@ __global__ __launch_bounds__(kT) void sg_anl_acf(const T* __restrict__ x, const 
         double a = (s[r] / (double)wl) / (se * se);
         a = a > 1.0 ? 1.0 : (a < -1.0 ? -1.0 : a);  // as acf()'s C code clamps
         amp[i] = a / filt[i];
+        if (kStore) store[(int64_t)blockIdx.x * nl + i] = amp[i];
       }
     }
   }
-  if (threadIdx.x == 0) npk = 0;
-  __syncthreads();
-  // HNR = max(a$amp); the peaks: a centred window of acW rows whose first maximum is
-  // its middle and exceeds autocorThres. The peak list is unordered; every use below
-  // is decided by (value, index), not by the list's order
-  double hn = -INFINITY;
-  for (int i = threadIdx.x; i < nl; i += kT) hn = fmax(hn, amp[i]);
-  hn = block_reduce<kT>(hn, 2, red);
-  int* pk = reinterpret_cast<int*>(xw);  // xw is dead (block_reduce's barriers are behind every read)
-  const int h = K.acW / 2;
-  for (int c = h + threadIdx.x; c < nl - h; c += kT) {
-    const double v = amp[c];
-    if (!(v > K.autocorThres)) continue;
-    bool ok = true;
-    for (int j = c - h; j < c && ok; ++j) ok = amp[j] < v || amp[j] != amp[j];
-    for (int j = c + 1; j <= c + h && ok; ++j) ok = amp[j] <= v || amp[j] != amp[j];
-    if (ok) pk[atomicAdd(&npk, 1)] = c;  // at most nl - 2 h <= wl entries
-  }
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  const int P = npk;
-  double HNR = hn > -INFINITY ? hn : NAN;
-  if (P > 0) {
-    double pmax = -INFINITY;
-    for (int q = 0; q < P; ++q) pmax = fmax(pmax, amp[pk[q]]);
-    int ibest = nl;  // which(amp > 0.975 * max(amp))[1]
-    for (int q = 0; q < P; ++q)
-      if (amp[pk[q]] > 0.975 * pmax && pk[q] < ibest) ibest = pk[q];
-    const double cutf = lagf[ibest] / 1.8;  // peaks with freq > bestFreq / 1.8
-    // order(amp, decreasing = TRUE): the larger first, the earlier row on ties
-    double lastv = INFINITY;
-    int lasti = -1;
-    for (int n = 0; n < K.nCands; ++n) {
-      int bi = -1;
-      double bv = -INFINITY;
-      for (int q = 0; q < P; ++q) {
-        const int i = pk[q];
-        const double v = amp[i];
-        if (!(lagf[i] > cutf)) continue;
-        if (!(v < lastv || (v == lastv && i > lasti))) continue;  // already taken
-        if (bi < 0 || v > bv || (v == bv && i < bi)) {
-          bi = i;
-          bv = v;
-        }
-      }
-      if (bi < 0) break;
-      row[sg::kAnlFixed + n] = lagf[bi];
-      row[sg::kAnlFixed + K.nCands + n] = bv;
-      lastv = bv;
-      lasti = bi;
-    }
-  }
-  if (HNR >= 1.0) HNR = 0.9999;
-  row[sg::kHNR] = HNR;
-  if (row[sg::kDom] == row[sg::kDom] && HNR == HNR) row[sg::kDomCert] = 1.0 / (1.0 + exp(3.0 * HNR - 1.0));
+  int* pk = reinterpret_cast<int*>(xw);  // xw is dead behind the first barrier below: at most nl - 2 h <= wl entries
+  SG_ACF_PEAKS(kT)
 }
+
+// A sweep's later candidate groups of a store group: the frame's corrected autocorrelations
+// from the store sg_anl_acf<T, true> filled, then SG_ACF_PEAKS under this group's autocorThres,
+// autocorSmooth and nCands. The gate is the store group's, so the frame was stored.
+// LDS: nlag doubles, then nlag ints (the peak list)
+template <int NT>
+__global__ __launch_bounds__(NT) void sg_anl_acf_peaks(const AnlFrame* __restrict__ frames, const AnlSound* __restrict__ snds,
+                                                       const double* __restrict__ store, const double* __restrict__ lagf,
+                                                       AnlK K, double* __restrict__ out) {
+  extern __shared__ double lds_pk[];
+  __shared__ double red[NT];
+  __shared__ int npk;
+  const AnlFrame F = frames[blockIdx.x];
+  const AnlSound S = snds[F.snd];
+  double* row = out + S.row0 + (int64_t)F.f * K.cols;
+  if (row[sg::kCondEntropy] != 1.0) return;  // workgroup-uniform; written by sg_anl_spec
+  const int nl = K.nlag;
+  const double* src = store + (int64_t)blockIdx.x * nl;
+  double* amp = lds_pk;
+  int* pk = reinterpret_cast<int*>(lds_pk + nl);
+  for (int i = threadIdx.x; i < nl; i += NT) amp[i] = src[i];
+  SG_ACF_PEAKS(NT)  // its first barrier publishes amp[]
+}
+#undef SG_ACF_PEAKS
 
 // the constants of the two trackers pitch_candidates adds
 struct PitchK {
@@ -642,7 +695,131 @@ __global__ __launch_bounds__(kSumT) void sg_anl_summary(const sg::SumSound* __re
                 kSumT, sh, WgSync());
 }
 
+// A sweep (sg_analyze_sweep). A pair is (row of the chunk, sound): workgroup b of a tail kernel
+// is pair b = row_in_chunk * n_calls + sound. Its candidates are the sound's table of the row's
+// candidate group, which the tail leaves untouched; its own table and scratch lie in the chunk's
+// workspace.
+struct SweepPair {
+  int64_t src0;  // first double of the sound's candidate table
+  int64_t dst0;  // first double of the pair's table in the workspace
+  int64_t scr0;  // first double of its frames' scratch there
+  int32_t nf, hw, cols, row;  // frames, half the smoothing window, doubles of a row of its table, the row's PathPars
+};
+
+// dst's kAmpl column from src's: the candidate tables of a frame group share their amplitudes
+__global__ __launch_bounds__(kT) void sg_anl_sweep_ampl(const AnlFrame* __restrict__ frames, const AnlSound* __restrict__ src_snds,
+                                                        const AnlSound* __restrict__ dst_snds, int64_t n_frames, int src_cols,
+                                                        int dst_cols, const double* __restrict__ src, double* __restrict__ dst) {
+  const int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x;
+  if (i >= n_frames) return;
+  const AnlFrame F = frames[i];
+  dst[dst_snds[F.snd].row0 + (int64_t)F.f * dst_cols + sg::kAmpl] = src[src_snds[F.snd].row0 + (int64_t)F.f * src_cols + sg::kAmpl];
+}
+
+// sg_anl_path for a pair: sg::path_sound_at from the shared candidates into the pair's table
+__global__ __launch_bounds__(kPathT) void sg_anl_sweep_path(const SweepPair* __restrict__ pairs,
+                                                            const sg::PathPars* __restrict__ pars,
+                                                            const double* __restrict__ cands, double* __restrict__ work) {
+  __shared__ double red[kPathT];
+  __shared__ int64_t sh[3];
+  const SweepPair R = pairs[blockIdx.x];
+  if (R.nf <= 0) return;  // workgroup-uniform
+  const sg::PathPars P = pars[R.row];
+  sg::path_sound_at(P, R.nf, R.hw, cands + R.src0, P.cols - sg::kPathCols, work + R.dst0, work + R.scr0, (int)threadIdx.x,
+                    kPathT, red, sh, WgSync());
+}
+
+// sg_anl_harm for frame blockIdx.x of the frame group under row blockIdx.y of the chunk
+__global__ __launch_bounds__(kT) void sg_anl_sweep_harm(const AnlFrame* __restrict__ frames, const AnlSound* __restrict__ snds,
+                                                        const SweepPair* __restrict__ pairs, int n_calls,
+                                                        const double* __restrict__ Z, const double* __restrict__ lab, int B,
+                                                        double* __restrict__ work) {
+  __shared__ double red[kT];
+  const AnlFrame F = frames[blockIdx.x];
+  const AnlSound S = snds[F.snd];
+  const SweepPair R = pairs[(int64_t)blockIdx.y * n_calls + F.snd];
+  const int cols = R.cols;
+  double* row = work + R.dst0 + (int64_t)F.f * cols;
+  const double pitch = row[cols - sg::kPathCols + sg::kPathPitch];
+  if (pitch != pitch) return;  // workgroup-uniform
+  const double threshold = 1.25 * pitch / 1000;
+  const double* z = Z + S.z0 + (int64_t)F.f * B;
+  double above = 0, all = 0;
+  for (int b = threadIdx.x; b < B; b += kT) {
+    const double v = z[b];
+    all += v;
+    if (lab[b] > threshold) above += v;
+  }
+  above = block_reduce<kT>(above, 0, red);
+  all = block_reduce<kT>(all, 0, red);
+  if (threadIdx.x == 0) row[cols - sg::kPathCols + sg::kPathHarmonics] = sg::path_to_dB(above / all);
+}
+
+// the launch's constants from the setup: `cols` doubles a row, of which sg_anl_spec blanks the first `fill`
+AnlK launch_consts(const sg::AnlSetup& A, int cols, int fill) {
+  AnlK K;
+  K.wl = A.spg.wl;
+  K.B = A.spg.bins;
+  K.cols = cols;
+  K.fill = fill;
+  K.nCands = A.nCands;
+  K.rowLow = A.rowLow - 1;
+  K.rowHigh = A.rowHigh - 1;
+  K.cut0 = A.cut0;
+  K.ncut = A.ncut;
+  K.pf_idx = A.pf_idx;
+  K.domW = A.domW;
+  K.acW = A.acW;
+  K.lag0 = A.lag0;
+  K.nlag = A.nlag;
+  K.do_dom = A.do_dom;
+  K.do_autocor = A.do_autocor;
+  K.silence = A.silence;
+  K.entropyThres = A.entropyThres;
+  K.domThres = A.domThres;
+  K.autocorThres = A.autocorThres;
+  K.sxx = A.sxx;
+  return K;
+}
+
+PitchK launch_consts(const sg::PitchSetup& Q, int cols) {
+  PitchK X;
+  X.B = Q.spg.bins;
+  X.cols = cols;
+  X.nCands = Q.nCands;
+  X.L = Q.cepL;
+  X.odd = Q.cepL % 2;
+  X.M = X.odd ? Q.cepL : Q.cepL / 2;
+  X.pad = Q.cepPad;
+  X.l = Q.cepl;
+  X.c0 = Q.cep0;
+  X.nc = Q.ncep;
+  X.cepW = Q.cepW;
+  X.specW = Q.specW;
+  X.cepThres = Q.cepThres;
+  X.specPeak = Q.specPeak;
+  X.bana = sg::BanaPars{Q.pitchFloor, Q.pitchCeiling, Q.specSinglePeakCert, Q.specThres, Q.specMerge, Q.nCands};
+  return X;
+}
+
+// the checks of a setup against its frame, before anything is launched
+void check_setup(const sg::AnlSetup& A, const sg::PitchSetup* pitch) {
+  const int B = A.spg.bins, wl = A.spg.wl;
+  if (A.rowLow < 1 || A.rowHigh > B || A.rowLow > A.rowHigh || A.cut0 < 0 || A.cut0 + A.ncut > B || A.lag0 < 0 ||
+      A.lag0 + A.nlag > wl || B > sg::kSpgMaxBins || A.nCands > sg::kAnlMaxCands)
+    throw sg::SgError(SG_E_DEVICE, "analyze: the setup leaves the frame");
+  if (pitch && pitch->do_cep) {
+    const sg::PitchSetup& Q = *pitch;
+    const int M = Q.cepL % 2 ? Q.cepL : Q.cepL / 2;
+    if (Q.cepL != B + 2 * Q.cepPad || Q.cepPad < 0 || M < 1 || M > sg::kSpgMaxBins || Q.cepl != Q.cepL / 2 || Q.cep0 < 0 ||
+        Q.ncep < 1 || Q.cep0 + Q.ncep > Q.cepl || (int)Q.cepf.size() != Q.ncep || Q.cepW < 1)
+      throw sg::SgError(SG_E_DEVICE, "analyze: the cepstrum's setup leaves the frame");
+  }
+}
+
 double g_anl_ms[sg::kAnlStages];  // of the last profiled launch sequence
+double g_sweep_ms[sg::kSweepStages];
+int g_sweep_mode = 1;  // sg_set_analyze_sweep_store
 double g_summary_ms[1];
 double g_pitch_ms[sg::kPitchStages];
 double g_track_ms[sg::kTrackStages];
@@ -708,16 +885,7 @@ void analyze_device(const AnlSetup& A, const T* d_x, const int64_t* offsets, con
     if (d_summary) summary_device(ss, A.cols, P.sr, d_out, d_summary, s, summary_ms);
     return;
   }
-  if (A.rowLow < 1 || A.rowHigh > B || A.rowLow > A.rowHigh || A.cut0 < 0 || A.cut0 + A.ncut > B || A.lag0 < 0 ||
-      A.lag0 + A.nlag > wl || B > kSpgMaxBins || A.nCands > kAnlMaxCands)
-    throw SgError(SG_E_DEVICE, "analyze: the setup leaves the frame");
-  if (pitch && pitch->do_cep) {
-    const PitchSetup& Q = *pitch;
-    const int M = Q.cepL % 2 ? Q.cepL : Q.cepL / 2;
-    if (Q.cepL != B + 2 * Q.cepPad || Q.cepPad < 0 || M < 1 || M > kSpgMaxBins || Q.cepl != Q.cepL / 2 || Q.cep0 < 0 ||
-        Q.ncep < 1 || Q.cep0 + Q.ncep > Q.cepl || (int)Q.cepf.size() != Q.ncep || Q.cepW < 1)
-      throw SgError(SG_E_DEVICE, "analyze: the cepstrum's setup leaves the frame");
-  }
+  check_setup(A, pitch);
   DevBuf db;
   double* d_Z = db.get<double>((size_t)cells);
   SpgStat* d_stat = db.get<SpgStat>((size_t)n_calls);
@@ -732,28 +900,7 @@ void analyze_device(const AnlSetup& A, const T* d_x, const int64_t* offsets, con
   const double* d_freq = upload(db, A.freq, s);
   const double* d_xc = upload(db, A.xc, s);
   unsigned long long* d_min = upload(db, std::vector<unsigned long long>(n_calls, dkey(INFINITY)), s);
-  AnlK K;
-  K.wl = wl;
-  K.B = B;
-  K.cols = A.cols;
-  K.fill = track ? A.cols - kPathCols : A.cols;
-  K.nCands = A.nCands;
-  K.rowLow = A.rowLow - 1;
-  K.rowHigh = A.rowHigh - 1;
-  K.cut0 = A.cut0;
-  K.ncut = A.ncut;
-  K.pf_idx = A.pf_idx;
-  K.domW = A.domW;
-  K.acW = A.acW;
-  K.lag0 = A.lag0;
-  K.nlag = A.nlag;
-  K.do_dom = A.do_dom;
-  K.do_autocor = A.do_autocor;
-  K.silence = A.silence;
-  K.entropyThres = A.entropyThres;
-  K.domThres = A.domThres;
-  K.autocorThres = A.autocorThres;
-  K.sxx = A.sxx;
+  const AnlK K = launch_consts(A, A.cols, track ? A.cols - kPathCols : A.cols);
   const dim3 gF((unsigned)F), bT(kT);
   clk.stamp();  // 1: amplitudes
   hipLaunchKernelGGL(sg_anl_ampl<T>, gF, bT, 0, s, d_x, d_fr, d_snd, d_stat, wl, A.cols, d_out, d_min);
@@ -768,30 +915,16 @@ void analyze_device(const AnlSetup& A, const T* d_x, const int64_t* offsets, con
     const double* d_lagf = upload(db, A.lagf, s);
     const int lds = (wl + 4 + A.nlag) * (int)sizeof(double);
     if (lds > 48 * 1024)
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&sg_anl_acf<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 lds));
-    hipLaunchKernelGGL(sg_anl_acf<T>, gF, bT, (size_t)lds, s, d_x, d_fr, d_snd, d_stat, d_win, d_filt, d_lagf, K, d_out);
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&sg_anl_acf<T, false>),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    hipLaunchKernelGGL((sg_anl_acf<T, false>), gF, bT, (size_t)lds, s, d_x, d_fr, d_snd, d_stat, d_win, d_filt, d_lagf, K, d_out,
+                       (double*)nullptr);
     HIPCHK(hipGetLastError());
   }
   clk.stamp();  // 4: the cepstrum and its peaks
   if (pitch) {
     const PitchSetup& Q = *pitch;
-    PitchK X;
-    X.B = B;
-    X.cols = A.cols;
-    X.nCands = A.nCands;
-    X.L = Q.cepL;
-    X.odd = Q.cepL % 2;
-    X.M = X.odd ? Q.cepL : Q.cepL / 2;
-    X.pad = Q.cepPad;
-    X.l = Q.cepl;
-    X.c0 = Q.cep0;
-    X.nc = Q.ncep;
-    X.cepW = Q.cepW;
-    X.specW = Q.specW;
-    X.cepThres = Q.cepThres;
-    X.specPeak = Q.specPeak;
-    X.bana = BanaPars{Q.pitchFloor, Q.pitchCeiling, Q.specSinglePeakCert, Q.specThres, Q.specMerge, A.nCands};
+    const PitchK X = launch_consts(Q, A.cols);
     if (Q.do_cep) {
       const int N = X.odd ? 2 * X.M : X.L;  // fft64 reads W_N^t, t < 2 M
       double2* d_TN = db.get<double2>((size_t)N);
@@ -886,6 +1019,272 @@ int frames_batch(sg_ctx* ctx, const sg::AnlSetup& S, const sg::PitchSetup* pitch
   sg::analyze_device<float>(S, d_wave, offsets, lengths, n_calls, d_out, out_off, frames_out, ctx->stream,
                             ctx->profiling ? ms : nullptr, pitch, track);
   return SG_OK;
+}
+
+// the stages of sg_debug_analyze_sweep_kernel_ms
+enum SweepStage { kSwSpg = 0, kSwAmpl, kSwSpec, kSwAcf, kSwPeaks, kSwCep, kSwBana, kSwPath, kSwHarm, kSwSummary };
+static_assert(kSwSummary + 1 == sg::kSweepStages, "ten stages");
+
+template <class K>
+void allow_dyn_lds(K kernel, int lds) {
+  if (lds > 48 * 1024)
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+}
+
+// sg_analyze_sweep: n_rows parameter rows over n_calls sounds (the header's text). Frame groups run one after
+// another; within one, the candidate groups in the order of their store groups, so that a store's users follow each
+// other and one buffer serves every store; then the tail over chunks of the frame group's rows. Every kernel's work
+// on a frame or a pair is what sg_analyze_summary_batch's kernels do on it, whatever shares the launch.
+void analyze_sweep(sg_ctx* ctx, const float* d_x, const int64_t* offsets, const int64_t* lengths, int64_t n_calls,
+                   const sg_analyze_params_full* prow, int64_t n_rows, int64_t workspace_cap, double* d_out) {
+  using namespace sg;
+  const SweepPlan W = anl_sweep_plan(prow, n_rows);  // every refusal comes before the first launch
+  int64_t bytes[3];
+  anl_sweep_bytes(W, lengths, n_calls, bytes);  // the smoothing window of every (row, sound)
+  std::vector<PathPars> pars((size_t)n_rows);
+  for (int64_t r = 0; r < n_rows; ++r) {
+    const TrackSetup& S = W.S[r];
+    check_setup(S, &S);
+    if (S.path.cols != S.cols || S.cols != kAnlFixed + 6 * S.nCands + kPathCols || (int)S.lab.size() != S.spg.bins)
+      throw SgError(SG_E_DEVICE, "analyze: the tail's setup leaves the row");
+    pars[r] = S.path;
+  }
+  const int64_t cap = workspace_cap > 0 ? workspace_cap : kSweepWorkspaceCap;
+  const bool use_store = g_sweep_mode & 1, copy_ampl = g_sweep_mode & 2, wave_peaks = g_sweep_mode & 4;
+  hipStream_t s = ctx->stream;
+  HIPCHK(hipSetDevice(ctx->device));
+  StageClock clk(s, ctx->profiling ? g_sweep_ms : nullptr, kSweepStages);
+  clk.zero();
+  auto timed = [&](int stage, auto&& launch) {  // what follows up to the next stamp (an upload at most) counts with it
+    clk.stamp(stage);
+    launch();
+    HIPCHK(hipGetLastError());
+  };
+  DevBuf top;
+  const PathPars* d_pars = upload(top, pars, s);
+  for (int fg = 0; fg < W.n_frame; ++fg) {
+    // the frame group's candidate groups, ordered by store group (-1 first), then by number; its rows behind them
+    std::vector<int> cgs;
+    std::vector<int64_t> rep;  // a row of each
+    for (int64_t r = 0; r < n_rows; ++r)
+      if (W.frame_group[r] == fg && std::find(cgs.begin(), cgs.end(), W.cand_group[r]) == cgs.end()) {
+        cgs.push_back(W.cand_group[r]);
+        rep.push_back(r);
+      }
+    std::vector<size_t> order(cgs.size());
+    for (size_t i = 0; i < order.size(); ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(),
+                     [&](size_t a, size_t b) { return W.store_group[rep[a]] < W.store_group[rep[b]]; });
+    std::vector<int64_t> frows;
+    for (size_t i : order)
+      for (int64_t r = 0; r < n_rows; ++r)
+        if (W.cand_group[r] == cgs[i]) frows.push_back(r);
+    const TrackSetup& A = W.S[frows[0]];
+    const SpgSetup& P = A.spg;
+    const int B = P.bins, wl = P.wl;
+    // the frames, as analyze_device lists them
+    std::vector<AnlFrame> fr;
+    std::vector<int64_t> lens(n_calls), zoff(n_calls), foff(n_calls);
+    std::vector<int32_t> nfs(n_calls);
+    int64_t cells = 0;
+    for (int64_t c = 0; c < n_calls; ++c) {
+      const int nf = anl_frames(A, lengths[c]);
+      lens[c] = nf ? lengths[c] : 0;
+      zoff[c] = cells;
+      foff[c] = (int64_t)fr.size();
+      nfs[c] = nf;
+      if ((int64_t)fr.size() + nf > 2147483647LL) throw SgError(SG_E_UNSUPPORTED, "analyze: the frames of one launch exceed 2^31");
+      for (int f = 0; f < nf; ++f) {
+        const int64_t o = spg_frame_start(P, lengths[c], f), a = anl_ampl_start(A, lengths[c], nf, f);
+        if (o < 0 || o + wl > lengths[c] || a < 0 || a + wl + 1 > lengths[c])
+          throw SgError(SG_E_DEVICE, "analyze: a frame leaves its sound");
+        fr.push_back(AnlFrame{o, a, (int32_t)c, f});
+      }
+      cells += (int64_t)nf * B;
+    }
+    const int64_t F = (int64_t)fr.size();
+    const dim3 gF((unsigned)F), bT(kT);
+    DevBuf db;
+    // where each candidate group's tables lie in the one buffer, and its view of the sounds
+    std::vector<int64_t> cand0(cgs.size());
+    int64_t cand_cells = 0;
+    for (size_t i : order) {
+      cand0[i] = cand_cells;
+      cand_cells += F * (W.S[rep[i]].cols - kPathCols);
+    }
+    // the tail: chunks of consecutive rows whose pair tables and scratch fit the cap, at least one row
+    const int64_t cap_cells = std::max<int64_t>(1, cap / (int64_t)sizeof(double));
+    auto row_cells = [&](int64_t r) { return F * (W.S[r].cols + path_stride(W.S[r].nCands)); };
+    std::vector<size_t> chunk_end;
+    int64_t work = 0, work_cells = 0;
+    size_t first = 0;
+    for (size_t k = 0; k < frows.size(); ++k) {
+      const int64_t need = row_cells(frows[k]);
+      if (k > first && (work + need > cap_cells || k - first >= 65535 || (int64_t)(k - first + 1) * n_calls > 2147483647LL)) {
+        chunk_end.push_back(k);
+        first = k;
+        work = 0;
+      }
+      work += need;
+      work_cells = std::max(work_cells, work);
+    }
+    chunk_end.push_back(frows.size());
+    double* d_cand = db.get<double>((size_t)(cand_cells + work_cells));  // the candidate tables, then a chunk's workspace
+    double* d_work = d_cand + cand_cells;
+    double* d_Z = nullptr;
+    const AnlFrame* d_fr = nullptr;
+    const AnlSound* d_snd0 = nullptr;  // the first candidate group's
+    const double* d_lab = nullptr;
+    if (F > 0) {
+      d_Z = db.get<double>((size_t)cells);
+      SpgStat* d_stat = db.get<SpgStat>((size_t)n_calls);
+      std::vector<int32_t> b_o(n_calls), f_o(n_calls);
+      timed(kSwSpg, [&]() {
+        spectrogram_device<float>(P, d_x, offsets, lens.data(), n_calls, d_Z, zoff.data(), b_o.data(), f_o.data(), s, nullptr,
+                                  d_stat);
+      });
+      for (int64_t c = 0; c < n_calls; ++c)
+        if (f_o[c] != nfs[c]) throw SgError(SG_E_DEVICE, "analyze: the spectrogram's frame count differs");
+      d_fr = upload(db, fr, s);
+      d_lab = upload(db, A.lab, s);
+      const double* d_freq = upload(db, A.freq, s);
+      const double* d_win = upload(db, spg_window(wl, P.wn), s);
+      unsigned long long* d_min = upload(db, std::vector<unsigned long long>(n_calls, dkey(INFINITY)), s);
+      // one buffer for the stores that are built: shared by two candidate groups or more, and within the cap
+      std::vector<int> users((size_t)std::max(W.n_store, 1), 0);
+      int64_t store_cells = 0;
+      for (size_t i : order)
+        if (W.store_group[rep[i]] >= 0) ++users[W.store_group[rep[i]]];
+      auto built = [&](int64_t r) {
+        return use_store && W.store_group[r] >= 0 && users[W.store_group[r]] >= 2 &&
+               F * W.S[r].nlag * (int64_t)sizeof(double) <= cap;
+      };
+      for (size_t i : order)
+        if (built(rep[i])) store_cells = std::max(store_cells, F * W.S[rep[i]].nlag);
+      double* d_store = store_cells ? db.get<double>((size_t)store_cells) : nullptr;
+      int filled = -1;  // the store group whose values d_store holds
+      int first_cols = 0;
+      for (size_t i : order) {
+        const TrackSetup& S = W.S[rep[i]];
+        const int cols = S.cols - kPathCols;
+        std::vector<AnlSound> snds(n_calls);
+        for (int64_t c = 0; c < n_calls; ++c)
+          snds[c] = AnlSound{offsets[c], lens[c], zoff[c], cand0[i] + foff[c] * cols, nfs[c], 0};
+        const AnlSound* d_snd = upload(db, snds, s);
+        const AnlK K = launch_consts(S, cols, cols);
+        if (!d_snd0 || !copy_ampl) {
+          timed(kSwAmpl, [&]() {
+            hipLaunchKernelGGL(sg_anl_ampl<float>, gF, bT, 0, s, d_x, d_fr, d_snd, d_stat, wl, cols, d_cand, d_min);
+          });
+        } else {
+          timed(kSwAmpl, [&]() {
+            hipLaunchKernelGGL(sg_anl_sweep_ampl, dim3((unsigned)((F + kT - 1) / kT)), bT, 0, s, d_fr, d_snd0, d_snd, F,
+                               first_cols, cols, d_cand, d_cand);
+          });
+        }
+        if (!d_snd0) {
+          d_snd0 = d_snd;
+          first_cols = cols;
+        }
+        const double* d_xc = upload(db, S.xc, s);
+        timed(kSwSpec, [&]() { hipLaunchKernelGGL(sg_anl_spec, gF, bT, 0, s, d_fr, d_snd, d_Z, d_freq, d_xc, d_min, K, d_cand); });
+        if (S.do_autocor) {
+          const double* d_lagf = upload(db, S.lagf, s);
+          const int sgp = W.store_group[rep[i]];
+          if (built(rep[i]) && filled == sgp) {
+            const int lds = S.nlag * (int)(sizeof(double) + sizeof(int));
+            timed(kSwPeaks, [&]() {
+              if (wave_peaks) {
+                allow_dyn_lds(&sg_anl_acf_peaks<64>, lds);
+                hipLaunchKernelGGL(sg_anl_acf_peaks<64>, gF, dim3(64), (size_t)lds, s, d_fr, d_snd, d_store, d_lagf, K, d_cand);
+              } else {
+                allow_dyn_lds(&sg_anl_acf_peaks<kT>, lds);
+                hipLaunchKernelGGL(sg_anl_acf_peaks<kT>, gF, bT, (size_t)lds, s, d_fr, d_snd, d_store, d_lagf, K, d_cand);
+              }
+            });
+          } else {
+            const double* d_filt = upload(db, anl_filter(S), s);
+            const int lds = (wl + 4 + S.nlag) * (int)sizeof(double);
+            timed(kSwAcf, [&]() {
+              if (built(rep[i])) {
+                allow_dyn_lds(&sg_anl_acf<float, true>, lds);
+                hipLaunchKernelGGL((sg_anl_acf<float, true>), gF, bT, (size_t)lds, s, d_x, d_fr, d_snd, d_stat, d_win, d_filt,
+                                   d_lagf, K, d_cand, d_store);
+                filled = sgp;
+              } else {
+                allow_dyn_lds(&sg_anl_acf<float, false>, lds);
+                hipLaunchKernelGGL((sg_anl_acf<float, false>), gF, bT, (size_t)lds, s, d_x, d_fr, d_snd, d_stat, d_win, d_filt,
+                                   d_lagf, K, d_cand, (double*)nullptr);
+              }
+            });
+          }
+        }
+        const PitchK X = launch_consts(S, cols);
+        if (S.do_cep) {
+          const int N = X.odd ? 2 * X.M : X.L;  // fft64 reads W_N^t, t < 2 M
+          double2* d_TN = db.get<double2>((size_t)N);
+          const double* d_cepf = upload(db, S.cepf, s);
+          fill_roots64(d_TN, N, s);
+          const int lds = (2 * X.M + 32) * (int)sizeof(double2) + (X.l + 1) * (int)sizeof(double);
+          allow_dyn_lds(&sg_anl_cep, lds);
+          timed(kSwCep,
+                [&]() { hipLaunchKernelGGL(sg_anl_cep, gF, bT, (size_t)lds, s, d_fr, d_snd, d_Z, d_TN, d_cepf, X, d_cand); });
+        }
+        if (S.do_spec)
+          timed(kSwBana, [&]() { hipLaunchKernelGGL(sg_anl_bana, gF, bT, 0, s, d_fr, d_snd, d_Z, d_freq, X, d_cand); });
+      }
+    }
+    const AnlSound* d_zs = nullptr;  // the sounds' |X| frames (z0) for sg_anl_sweep_harm
+    if (F > 0) d_zs = d_snd0;
+    size_t k0 = 0;
+    for (size_t k1 : chunk_end) {
+      std::vector<SweepPair> pairs;
+      pairs.reserve((k1 - k0) * (size_t)n_calls);
+      int64_t at = 0;
+      for (size_t k = k0; k < k1; ++k) {
+        const int64_t r = frows[k];
+        const TrackSetup& S = W.S[r];
+        const int ccols = S.cols - kPathCols, pstride = path_stride(S.nCands);
+        const size_t i = (size_t)(std::find(cgs.begin(), cgs.end(), W.cand_group[r]) - cgs.begin());
+        for (int64_t c = 0; c < n_calls; ++c) {
+          SweepPair R;
+          R.src0 = cand0[i] + foff[c] * ccols;
+          R.dst0 = at;
+          R.scr0 = at + (int64_t)nfs[c] * S.cols;
+          R.nf = nfs[c];
+          R.hw = track_hw(S.smooth, P.sr, lengths[c], nfs[c]);
+          R.cols = S.cols;
+          R.row = (int32_t)r;
+          at = R.scr0 + (int64_t)nfs[c] * pstride;
+          pairs.push_back(R);
+        }
+      }
+      if (at > work_cells) throw SgError(SG_E_DEVICE, "analyze: a chunk leaves its workspace");
+      const SweepPair* d_pairs = upload(db, pairs, s);
+      const dim3 gP((unsigned)pairs.size());
+      if (F > 0) {
+        timed(kSwPath, [&]() { hipLaunchKernelGGL(sg_anl_sweep_path, gP, dim3(kPathT), 0, s, d_pairs, d_pars, d_cand, d_work); });
+        timed(kSwHarm, [&]() {
+          hipLaunchKernelGGL(sg_anl_sweep_harm, dim3((unsigned)F, (unsigned)(k1 - k0)), bT, 0, s, d_fr, d_zs, d_pairs,
+                             (int)n_calls, d_Z, d_lab, B, d_work);
+        });
+      }
+      // sg_anl_summary itself, once per row: its workgroups write consecutive rows of the output, and a second
+      // kernel around sg::sum_sound costs the first one registers (41 -> 48 VGPRs)
+      std::vector<SumSound> ss(pairs.size());
+      for (size_t b = 0; b < pairs.size(); ++b) ss[b] = SumSound{pairs[b].dst0, lengths[b % (size_t)n_calls], pairs[b].nf, 0};
+      const SumSound* d_ss = upload(db, ss, s);
+      timed(kSwSummary, [&]() {
+        for (size_t k = k0; k < k1; ++k)
+          hipLaunchKernelGGL(sg_anl_summary, dim3((unsigned)n_calls), dim3(kSumT), 0, s, d_ss + (k - k0) * (size_t)n_calls,
+                             W.S[frows[k]].cols, P.sr, d_work, d_out + frows[k] * n_calls * kSumCols);
+      });
+      k0 = k1;
+    }
+    clk.stamp(-1);
+    HIPCHK(hipStreamSynchronize(s));  // before the frame group's buffers go
+  }
+  clk.finish();
 }
 
 }  // namespace
@@ -1041,6 +1440,34 @@ int sg_analyze_summary_sound(sg_ctx* ctx, const double* wave, int64_t len, const
     HIPCHK(hipMemcpy(summary, d_sum, sg::kSumCols * sizeof(double), hipMemcpyDeviceToHost));
     return (int)SG_OK;
   });
+}
+
+int sg_analyze_sweep(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, const int64_t* lengths, int64_t n_calls,
+                     const sg_analyze_params_full* rows, int64_t n_rows, int64_t workspace_cap, double* d_out) {
+  return guarded(ctx, [&]() {
+    if (!ctx || n_calls < 0 || n_calls > 2147483647LL || n_rows < 0 || workspace_cap < 0 || (n_rows > 0 && !rows) ||
+        (n_calls > 0 && (!d_wave || !offsets || !lengths)) || (n_calls > 0 && n_rows > 0 && !d_out))
+      throw sg::SgError(SG_E_ARG, "sg_analyze_sweep: bad arguments");
+    if (n_rows == 0) return (int)SG_OK;
+    if (n_calls == 0) {
+      (void)sg::anl_sweep_plan(rows, n_rows);  // the rows are still judged
+      return (int)SG_OK;
+    }
+    analyze_sweep(ctx, d_wave, offsets, lengths, n_calls, rows, n_rows, workspace_cap, d_out);
+    return (int)SG_OK;
+  });
+}
+
+int sg_set_analyze_sweep_store(int32_t mode) {
+  if (mode < 0 || mode > 7) return SG_E_ARG;
+  g_sweep_mode = mode;
+  return SG_OK;
+}
+
+int sg_debug_analyze_sweep_kernel_ms(double* out) {
+  if (!out) return SG_E_ARG;
+  for (int k = 0; k < sg::kSweepStages; ++k) out[k] = g_sweep_ms[k];
+  return SG_OK;
 }
 
 int sg_debug_summary_kernel_ms(double* out) {

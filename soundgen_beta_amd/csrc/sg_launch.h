@@ -100,8 +100,25 @@ class StageClock {
     e_.push_back(v);
     HIPCHK(hipEventRecord(v, s_));
   }
+  // A sequence that visits its stages many times and out of order (a sweep): what follows
+  // this stamp, up to the next one, is added to ms[stage]; stage < 0: to none. Not to be
+  // mixed with stamp() on one clock.
+  void stamp(int stage) {
+    if (!ms_) return;
+    stamp();
+    label_.push_back(stage);
+  }
   void finish() {
     zero();
+    if (!label_.empty()) {
+      for (size_t k = 0; k + 1 < e_.size(); ++k) {
+        float ms = 0;
+        if (label_[k] < 0 || label_[k] >= n_) continue;
+        HIPCHK(hipEventElapsedTime(&ms, e_[k], e_[k + 1]));
+        ms_[label_[k]] += ms;
+      }
+      return;
+    }
     for (int k = 0; k + 1 < (int)e_.size() && k < n_; ++k) {
       float ms = 0;
       HIPCHK(hipEventElapsedTime(&ms, e_[k], e_[k + 1]));
@@ -114,6 +131,7 @@ class StageClock {
   double* ms_;
   int n_;
   std::vector<hipEvent_t> e_;
+  std::vector<int> label_;
 };
 
 // len doubles of host memory into a buffer of db, complete on return

@@ -4,8 +4,10 @@
 // findGrad), medianSmoother and the final columns. The scalar routines are plain
 // functions; path_sound() drives them for one sound with `nl` cooperating lanes: the 64
 // lanes of sg_anl_path's workgroup on the device, one lane (and a sync that does nothing)
-// on the host (tests/cpp/path_pins.cpp). No HIP header is needed on the host side, no
-// dynamic memory anywhere.
+// on the host (tests/cpp/path_pins.cpp). path_sound_at() is the same with the candidates in a
+// table apart that it leaves untouched (a sweep's pairs, sg_anl_sweep_path;
+// tests/cpp/path_at_pins.cpp). No HIP header is needed on the host side, no dynamic memory
+// anywhere.
 //
 // A frame's candidates live in global scratch, path_stride() doubles per frame: W = 2 +
 // 3 nCands log2 pitches (dom, autocor[.], cep[.], spec[.] as pitch_matrices packs them,
@@ -282,18 +284,22 @@ SG_PATH_HD inline double path_reduce(double v, int op, int lane, int nl, double*
   return r;
 }
 
-// One sound: nf rows of P.cols doubles (the candidates as pitch_candidates leaves them)
-// -> pitch, amplVoiced, voiced (harmonics NaN: sg_anl_harm fills it), the smoothed dom,
-// the blanked quartiles, HNR in dB. scr: nf * path_stride() doubles; red: nl doubles and
-// sh: 3 int64 shared by the lanes; hw: floor(smoothing_ww / 2). Every lane must call it.
+// One sound: nf rows of src_cols doubles at src_rows (the candidates as pitch_candidates
+// leaves them, in their first P.cols - kPathCols columns) -> nf rows of P.cols doubles at
+// rows: those columns, then pitch, amplVoiced, voiced (harmonics NaN: sg_anl_harm fills it),
+// with the smoothed dom, the blanked quartiles and HNR in dB. src_rows may be rows itself
+// (src_cols == P.cols: the table is rewritten in place, path_sound) or a table apart that
+// stays untouched (a sweep's shared candidates, sg_anl_sweep_path). scr: nf * path_stride()
+// doubles; red: nl doubles and sh: 3 int64 shared by the lanes; hw: floor(smoothing_ww / 2).
+// Every lane must call it.
 template <class Sync>
-SG_PATH_HD inline void path_sound(const PathPars& P, int nf, int hw, double* rows, double* scr, int lane, int nl,
-                                  double* red, int64_t* sh, Sync sync) {
+SG_PATH_HD inline void path_sound_at(const PathPars& P, int nf, int hw, const double* src_rows, int src_cols, double* rows,
+                                     double* scr, int lane, int nl, double* red, int64_t* sh, Sync sync) {
   const int W = path_width(P.nCands), S = path_stride(P.nCands), X = 2 * W;
   const int c0 = P.cols - kPathCols;
   // pitch_matrices (:578-591), log2 (pathfinder :39), the prior (:598-612), the centre of gravity (:43-49)
   for (int f = lane; f < nf; f += nl) {
-    const double* row = rows + (int64_t)f * P.cols;
+    const double* row = src_rows + (int64_t)f * src_cols;
     double* c = scr + (int64_t)f * S;
     int cnt = 0;
     for (int j = 0; j < 1 + 3 * P.nCands; ++j) {
@@ -424,6 +430,10 @@ SG_PATH_HD inline void path_sound(const PathPars& P, int nf, int hw, double* row
   // medianSmoother (:670-681, reading the unsmoothed copies) and the final columns (:685-703)
   for (int f = lane; f < nf; f += nl) {
     double* row = rows + (int64_t)f * P.cols;
+    if (src_rows != rows) {  // a table apart: the pair's own copy of the columns in front
+      const double* src = src_rows + (int64_t)f * src_cols;
+      for (int q = 0; q < c0; ++q) row[q] = src[q];
+    }
     const double* c = scr + (int64_t)f * S;
     const int a = f - hw < 0 ? 0 : f - hw, b = f + hw > nf - 1 ? nf - 1 : f + hw;
     double pitch = c[X + kSlotHz], dom = c[X + kSlotDom];
@@ -441,6 +451,13 @@ SG_PATH_HD inline void path_sound(const PathPars& P, int nf, int hw, double* row
       for (int q = kPathQ25; q <= kPathQ75; ++q) row[q] = NAN;
     row[kPathHNR] = path_to_dB(row[kPathHNR]);
   }
+}
+
+// One sound whose table is rewritten in place: rows holds the candidates and receives the result
+template <class Sync>
+SG_PATH_HD inline void path_sound(const PathPars& P, int nf, int hw, double* rows, double* scr, int lane, int nl,
+                                  double* red, int64_t* sh, Sync sync) {
+  path_sound_at(P, nf, hw, rows, P.cols, rows, scr, lane, nl, red, sh, sync);
 }
 
 }  // namespace sg

@@ -183,6 +183,14 @@ def lib():
         L.sg_sweep_fitness.argtypes = [vp, vp, i64, i64, C.c_int32, C.c_int32, dp, dp]
         L.sg_set_sweep_staging.argtypes = [C.c_int32]
         L.sg_debug_sweep_kernel_ms.argtypes = [dp]
+    if hasattr(L, "sg_analyze_sweep"):  # parameter sweeps of analyze(): likewise additive
+        i32p = C.POINTER(C.c_int32)
+        fpp = C.POINTER(_abi.sg_analyze_params_full)
+        L.sg_analyze_sweep.argtypes = [vp, vp, i64p, i64p, i64, fpp, i64, i64, vp]
+        L.sg_analyze_sweep_plan.argtypes = [fpp, i64, i32p, i32p, i32p]
+        L.sg_analyze_sweep_size.argtypes = [i64p, i64, fpp, i64, i64p]
+        L.sg_set_analyze_sweep_store.argtypes = [C.c_int32]
+        L.sg_debug_analyze_sweep_kernel_ms.argtypes = [dp]
     L.sg_rrng_create.argtypes = [C.c_int32, C.POINTER(vp)]
     L.sg_rrng_destroy.argtypes = [vp]
     L.sg_rrng_set_seed.argtypes = [vp, C.c_int32]

@@ -6,8 +6,13 @@ segmentFolder a set of parameter vectors is one sweep (sg_segment_sweep, sg_segm
 the raw Hilbert envelope once per sound, the smoothed one once per sound and
 (windowLength, overlap), the tail of all (sound, vector) pairs in one launch, the summaries
 left in HBM; the default fitness (1 - Pearson correlation with the key over the complete
-pairs) is computed there too (sg_sweep_fitness). For analyzeFolder a vector is one
-analyze_batch(summary=True) per sampling rate, the rows left in HBM likewise.
+pairs) is computed there too (sg_sweep_fitness). For analyzeFolder a set of vectors is one
+sweep per sampling rate likewise (analyze.analyze_sweep, sg_analyze_sweep in sg_analyze.hip):
+the spectrogram and the amplitudes once per distinct window and step, the autocorrelations
+once per distinct gates and lag band, the candidates once per distinct set of the per-frame
+decisions, and the pathfinder, the harmonics and the summary of all (sound, vector) pairs in
+one launch each. Only a vector whose otherPars ask for the formant columns is still one
+analyze_batch(summary=True).
 
 A vector's summaries and fitness do not depend on the vectors it shares a sweep with (the
 same bits), so the Nelder-Mead restarts can evaluate their candidates ahead of time and
@@ -485,9 +490,16 @@ class _Folder:
             where = torch.as_tensor(g["files"], dtype=torch.int64, device=dev)
             if self.myfun == "segmentFolder":
                 m = _sweep(g["data"], g["offsets"], g["lengths"], g["samplingRate"], rows, device=self.device)
-            else:
-                m = torch.stack([AN.analyze_batch(g["data"], g["offsets"], g["lengths"], g["samplingRate"], to_host=False,
-                                                  device=self.device, summary=True, **kw)["out"] for kw in rows])
+            else:  # one sweep; a row that asks for the formant columns runs on its own, as before
+                m = torch.empty((len(rows), len(g["files"]), len(self.columns)), dtype=torch.float64, device=dev)
+                swept = [r for r, kw in enumerate(rows) if not kw.get("formants")]
+                if swept:
+                    m[swept] = AN.analyze_sweep(g["data"], g["offsets"], g["lengths"], g["samplingRate"],
+                                                [rows[r] for r in swept], device=self.device)
+                for r, kw in enumerate(rows):
+                    if kw.get("formants"):
+                        m[r] = AN.analyze_batch(g["data"], g["offsets"], g["lengths"], g["samplingRate"], to_host=False,
+                                                device=self.device, summary=True, **kw)["out"]
             out[:, where, :] = m
         return out
 
@@ -520,8 +532,8 @@ def optimize_pars(myfolder, key, myfun, pars, bounds=None, fitnessPar=None, fitn
     file) and returns a number; bounds: dict(low=[...], high=[...]) or None; otherPars:
     further arguments of the folder function (plot = TRUE raises; verbose, reportEvery and
     summary = TRUE are accepted). The files are read and uploaded once. For segmentFolder a
-    set of vectors is one sweep per sampling rate (see the module's text); for analyzeFolder
-    one analyze_batch(summary=True) per vector and rate.
+    set of vectors is one sweep per sampling rate, and so it is for analyzeFolder (see the
+    module's text).
 
     mygrid (option 1): a dict of equally long columns whose first len(pars) names are pars;
     every row is evaluated (no bounds, as in the reference) and the grid comes back as a
