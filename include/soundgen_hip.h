@@ -854,11 +854,10 @@ int sg_analyze_sweep_plan(const sg_analyze_params_full* rows, int64_t n_rows, in
  * window above 64 frames for any (row, sound). */
 int sg_analyze_sweep_size(const int64_t* lengths, int64_t n_calls, const sg_analyze_params_full* rows, int64_t n_rows,
                           int64_t* bytes);
-/* Process-wide, for measurements and tests; the results are the same bit for bit under every
- * mode. Bit 0 (default on): the autocorrelation store; off, every candidate group computes its
- * own autocorrelations. Bit 1: the amplitudes are computed into a frame group's first candidate
- * table and copied into the others (default: computed into each). Bit 2: the peak picker runs
- * as one wave per frame (default: 256 lanes). */
+/* Process-wide, for measurements and tests; the results are the same bit for bit under either
+ * mode. 1 (the default): the autocorrelation store; 0: every candidate group computes its own
+ * autocorrelations, as it does where a store does not fit workspace_cap. SG_E_ARG for any other
+ * mode, which leaves the mode in force. */
 int sg_set_analyze_sweep_store(int32_t mode);
 /* Process-wide policy of the fp64 filter path for later sg_plan_batch calls:
  * mode 0 never, 1 when the conditioning estimate exceeds rho (default 100),

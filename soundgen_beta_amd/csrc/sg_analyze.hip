@@ -46,6 +46,10 @@
 //   sg_anl_sweep_path  sg::path_sound_at from the shared candidate table into the pair's own
 //   sg_anl_sweep_harm  sg_anl_harm on grid (frames, rows of the chunk)
 // and sg_anl_summary once per row. A pair's cells are those of sg_analyze_summary_batch bit for bit.
+// On the host the two sequences (analyze_device, analyze_sweep) share what they decide alike: the frames of a
+// launch and both of their refusals (list_frames), the spectrogram behind them (list_spectra), and the five
+// candidate stages of one table with their LDS sizes and the cepstrum's roots (candidate_stages), which
+// analyze_device runs once and a sweep once per candidate group; each brings its own clock.
 // Cumulative sums run in index order: a thread sums a contiguous run, one thread
 // folds the 256 run sums in order, and the runs are rescanned from their offsets,
 // so a frame's result does not depend on the launch it is in.
@@ -144,6 +148,15 @@ __device__ __forceinline__ int first_crossing(const double* cum, int n, double v
       break;
     }
   return block_min_int(best, redi);
+}
+
+// a centred window of 2 h + 1 values of a[] whose first maximum is its middle, v = a[c]: the values before it are
+// smaller, those behind it not larger; NaN passes
+__device__ __forceinline__ bool peak_at(const double* a, int c, int h, double v) {
+  bool ok = true;
+  for (int j = c - h; j < c && ok; ++j) ok = a[j] < v || a[j] != a[j];
+  for (int j = c + 1; j <= c + h && ok; ++j) ok = a[j] <= v || a[j] != a[j];
+  return ok;
 }
 
 template <typename T>
@@ -264,10 +277,7 @@ __global__ __launch_bounds__(kT) void sg_anl_spec(const AnlFrame* __restrict__ f
     if (c + 1 <= K.pf_idx) continue;
     const double v = cum[c];
     if (!(v > K.domThres)) continue;
-    bool ok = true;
-    for (int j = c - h; j < c && ok; ++j) ok = cum[j] < v || cum[j] != cum[j];
-    for (int j = c + 1; j <= c + h && ok; ++j) ok = cum[j] <= v || cum[j] != cum[j];
-    if (ok) best = c;
+    if (peak_at(cum, c, h, v)) best = c;
   }
   best = block_min_int(best, redi);
   if (threadIdx.x == 0 && best < B) {
@@ -281,29 +291,26 @@ __global__ __launch_bounds__(kT) void sg_anl_spec(const AnlFrame* __restrict__ f
 // certainty behind it (:151-159): HNR = max(a$amp); the peaks (a centred window of acW rows whose
 // first maximum is its middle and exceeds autocorThres), the 0.975 rule, the 1.8 rule, the
 // ordered candidates, the HNR >= 1 clamp. The tail of sg_anl_acf and the body of
-// sg_anl_acf_peaks, for a workgroup of NT threads; it reads the names of the kernel it stands
-// in: amp (nl doubles of LDS), pk (room for nl ints of LDS), npk (an int of LDS), red (NT
-// doubles of LDS), nl, K, lagf, row. The peak list is unordered; every use is decided by
-// (value, index), not by the list's order. Every value written is a copy of one of amp[] or
-// lagf[] and every decision a comparison, so the result depends neither on NT nor on who
-// computed amp[].
+// sg_anl_acf_peaks; it reads the names of the kernel it stands in: amp (nl doubles of LDS), pk
+// (room for nl ints of LDS), npk (an int of LDS), red (kT doubles of LDS), nl, K, lagf, row. The
+// peak list is unordered; every use is decided by (value, index), not by the list's order. Every
+// value written is a copy of one of amp[] or lagf[] and every decision a comparison, so the
+// result does not depend on who computed amp[].
 // A macro and not a function: as a __device__ function (forced inline or not, the constants by
 // reference, by value or as scalars: twenty variants) sg_anl_acf compiled to 46 VGPRs where
-// the one-piece kernel has 44; as text it is the one-piece kernel.
-#define SG_ACF_PEAKS(NT)                                                                                  \
+// the one-piece kernel has 44; as text it is the one-piece kernel. (peak_at, the window test
+// alone, costs it nothing: the same registers, LDS and occupancy in all four kernels that call it.)
+#define SG_ACF_PEAKS                                                                                      \
   if (threadIdx.x == 0) npk = 0;                                                                          \
   __syncthreads();                                                                                        \
   double hn = -INFINITY;                                                                                  \
-  for (int i = threadIdx.x; i < nl; i += NT) hn = fmax(hn, amp[i]);                                       \
-  hn = block_reduce<NT>(hn, 2, red);                                                                      \
+  for (int i = threadIdx.x; i < nl; i += kT) hn = fmax(hn, amp[i]);                                       \
+  hn = block_reduce<kT>(hn, 2, red);                                                                      \
   const int h = K.acW / 2;                                                                                \
-  for (int c = h + threadIdx.x; c < nl - h; c += NT) {                                                    \
+  for (int c = h + threadIdx.x; c < nl - h; c += kT) {                                                    \
     const double v = amp[c];                                                                              \
     if (!(v > K.autocorThres)) continue;                                                                  \
-    bool ok = true;                                                                                       \
-    for (int j = c - h; j < c && ok; ++j) ok = amp[j] < v || amp[j] != amp[j];                            \
-    for (int j = c + 1; j <= c + h && ok; ++j) ok = amp[j] <= v || amp[j] != amp[j];                      \
-    if (ok) pk[atomicAdd(&npk, 1)] = c; /* at most nl - 2 h entries */                                    \
+    if (peak_at(amp, c, h, v)) pk[atomicAdd(&npk, 1)] = c; /* at most nl - 2 h entries */                 \
   }                                                                                                       \
   __syncthreads();                                                                                        \
   if (threadIdx.x != 0) return;                                                                           \
@@ -423,19 +430,18 @@ __global__ __launch_bounds__(kT) void sg_anl_acf(const T* __restrict__ x, const 
     }
   }
   int* pk = reinterpret_cast<int*>(xw);  // xw is dead behind the first barrier below: at most nl - 2 h <= wl entries
-  SG_ACF_PEAKS(kT)
+  SG_ACF_PEAKS
 }
 
 // A sweep's later candidate groups of a store group: the frame's corrected autocorrelations
 // from the store sg_anl_acf<T, true> filled, then SG_ACF_PEAKS under this group's autocorThres,
 // autocorSmooth and nCands. The gate is the store group's, so the frame was stored.
 // LDS: nlag doubles, then nlag ints (the peak list)
-template <int NT>
-__global__ __launch_bounds__(NT) void sg_anl_acf_peaks(const AnlFrame* __restrict__ frames, const AnlSound* __restrict__ snds,
+__global__ __launch_bounds__(kT) void sg_anl_acf_peaks(const AnlFrame* __restrict__ frames, const AnlSound* __restrict__ snds,
                                                        const double* __restrict__ store, const double* __restrict__ lagf,
                                                        AnlK K, double* __restrict__ out) {
   extern __shared__ double lds_pk[];
-  __shared__ double red[NT];
+  __shared__ double red[kT];
   __shared__ int npk;
   const AnlFrame F = frames[blockIdx.x];
   const AnlSound S = snds[F.snd];
@@ -445,8 +451,8 @@ __global__ __launch_bounds__(NT) void sg_anl_acf_peaks(const AnlFrame* __restric
   const double* src = store + (int64_t)blockIdx.x * nl;
   double* amp = lds_pk;
   int* pk = reinterpret_cast<int*>(lds_pk + nl);
-  for (int i = threadIdx.x; i < nl; i += NT) amp[i] = src[i];
-  SG_ACF_PEAKS(NT)  // its first barrier publishes amp[]
+  for (int i = threadIdx.x; i < nl; i += kT) amp[i] = src[i];
+  SG_ACF_PEAKS  // its first barrier publishes amp[]
 }
 #undef SG_ACF_PEAKS
 
@@ -528,10 +534,7 @@ __global__ __launch_bounds__(kT) void sg_anl_cep(const AnlFrame* __restrict__ fr
   for (int c = h + threadIdx.x; c < nl - h; c += kT) {
     const double v = amp[c];
     if (!(v > K.cepThres)) continue;
-    bool ok = true;
-    for (int j = c - h; j < c && ok; ++j) ok = amp[j] < v || amp[j] != amp[j];
-    for (int j = c + 1; j <= c + h && ok; ++j) ok = amp[j] <= v || amp[j] != amp[j];
-    if (ok) pk[atomicAdd(&npk, 1)] = c;  // at most nc <= l <= 2 M entries of 4 bytes in 32 M bytes
+    if (peak_at(amp, c, h, v)) pk[atomicAdd(&npk, 1)] = c;  // at most nc <= l <= 2 M entries of 4 bytes in 32 M bytes
   }
   __syncthreads();
   if (threadIdx.x != 0) return;
@@ -606,10 +609,7 @@ __global__ __launch_bounds__(kT) void sg_anl_bana(const AnlFrame* __restrict__ f
       if (c <= last) continue;
       const double v = fr[c];
       if (!(v > K.specPeak)) continue;
-      bool ok = true;
-      for (int j = c - h; j < c && ok; ++j) ok = fr[j] < v || fr[j] != fr[j];
-      for (int j = c + 1; j <= c + h && ok; ++j) ok = fr[j] <= v || fr[j] != fr[j];
-      if (ok) best = c;
+      if (peak_at(fr, c, h, v)) best = c;
     }
     best = block_min_int(best, redi);  // every thread gets it: the loop is workgroup-uniform
     if (best == B) break;
@@ -657,20 +657,13 @@ __global__ __launch_bounds__(kPathT) void sg_anl_path(const PathSound* __restric
   sg::path_sound(P, S.nf, S.hw, out + S.row0, scr + S.scr0, (int)threadIdx.x, kPathT, red, sh, WgSync());
 }
 
-// `harmonics` (R/analyze.R:694-703) for one frame per workgroup: the share of the frame's
-// |X| above 1.25 * pitch (labels in kHz, strictly above), in dB; sg_anl_path has left NaN
-// where pitch is NaN
-__global__ __launch_bounds__(kT) void sg_anl_harm(const AnlFrame* __restrict__ frames, const AnlSound* __restrict__ snds,
-                                                  const double* __restrict__ Z, const double* __restrict__ lab, int B,
-                                                  int cols, double* __restrict__ out) {
-  __shared__ double red[kT];
-  const AnlFrame F = frames[blockIdx.x];
-  const AnlSound S = snds[F.snd];
-  double* row = out + S.row0 + (int64_t)F.f * cols;
+// `harmonics` (R/analyze.R:694-703) for the frame of a workgroup, its row of `cols` doubles at row and its |X| at z:
+// the share of |X| above 1.25 * pitch (labels in kHz, strictly above), in dB; the path kernel has left NaN where
+// pitch is NaN
+__device__ __forceinline__ void harm_frame(double* row, int cols, const double* z, const double* lab, int B, double* red) {
   const double pitch = row[cols - sg::kPathCols + sg::kPathPitch];
   if (pitch != pitch) return;  // workgroup-uniform
   const double threshold = 1.25 * pitch / 1000;
-  const double* z = Z + S.z0 + (int64_t)F.f * B;
   double above = 0, all = 0;
   for (int b = threadIdx.x; b < B; b += kT) {
     const double v = z[b];
@@ -680,6 +673,15 @@ __global__ __launch_bounds__(kT) void sg_anl_harm(const AnlFrame* __restrict__ f
   above = block_reduce<kT>(above, 0, red);
   all = block_reduce<kT>(all, 0, red);
   if (threadIdx.x == 0) row[cols - sg::kPathCols + sg::kPathHarmonics] = sg::path_to_dB(above / all);
+}
+
+__global__ __launch_bounds__(kT) void sg_anl_harm(const AnlFrame* __restrict__ frames, const AnlSound* __restrict__ snds,
+                                                  const double* __restrict__ Z, const double* __restrict__ lab, int B,
+                                                  int cols, double* __restrict__ out) {
+  __shared__ double red[kT];
+  const AnlFrame F = frames[blockIdx.x];
+  const AnlSound S = snds[F.snd];
+  harm_frame(out + S.row0 + (int64_t)F.f * cols, cols, Z + S.z0 + (int64_t)F.f * B, lab, B, red);
 }
 
 constexpr int kSumT = 256;
@@ -706,16 +708,6 @@ struct SweepPair {
   int32_t nf, hw, cols, row;  // frames, half the smoothing window, doubles of a row of its table, the row's PathPars
 };
 
-// dst's kAmpl column from src's: the candidate tables of a frame group share their amplitudes
-__global__ __launch_bounds__(kT) void sg_anl_sweep_ampl(const AnlFrame* __restrict__ frames, const AnlSound* __restrict__ src_snds,
-                                                        const AnlSound* __restrict__ dst_snds, int64_t n_frames, int src_cols,
-                                                        int dst_cols, const double* __restrict__ src, double* __restrict__ dst) {
-  const int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x;
-  if (i >= n_frames) return;
-  const AnlFrame F = frames[i];
-  dst[dst_snds[F.snd].row0 + (int64_t)F.f * dst_cols + sg::kAmpl] = src[src_snds[F.snd].row0 + (int64_t)F.f * src_cols + sg::kAmpl];
-}
-
 // sg_anl_path for a pair: sg::path_sound_at from the shared candidates into the pair's table
 __global__ __launch_bounds__(kPathT) void sg_anl_sweep_path(const SweepPair* __restrict__ pairs,
                                                             const sg::PathPars* __restrict__ pars,
@@ -729,30 +721,16 @@ __global__ __launch_bounds__(kPathT) void sg_anl_sweep_path(const SweepPair* __r
                     kPathT, red, sh, WgSync());
 }
 
-// sg_anl_harm for frame blockIdx.x of the frame group under row blockIdx.y of the chunk
+// sg_anl_harm for frame blockIdx.x of the frame group under row blockIdx.y of the chunk; snds: any candidate
+// group's of the frame group (for z0)
 __global__ __launch_bounds__(kT) void sg_anl_sweep_harm(const AnlFrame* __restrict__ frames, const AnlSound* __restrict__ snds,
                                                         const SweepPair* __restrict__ pairs, int n_calls,
                                                         const double* __restrict__ Z, const double* __restrict__ lab, int B,
                                                         double* __restrict__ work) {
   __shared__ double red[kT];
   const AnlFrame F = frames[blockIdx.x];
-  const AnlSound S = snds[F.snd];
   const SweepPair R = pairs[(int64_t)blockIdx.y * n_calls + F.snd];
-  const int cols = R.cols;
-  double* row = work + R.dst0 + (int64_t)F.f * cols;
-  const double pitch = row[cols - sg::kPathCols + sg::kPathPitch];
-  if (pitch != pitch) return;  // workgroup-uniform
-  const double threshold = 1.25 * pitch / 1000;
-  const double* z = Z + S.z0 + (int64_t)F.f * B;
-  double above = 0, all = 0;
-  for (int b = threadIdx.x; b < B; b += kT) {
-    const double v = z[b];
-    all += v;
-    if (lab[b] > threshold) above += v;
-  }
-  above = block_reduce<kT>(above, 0, red);
-  all = block_reduce<kT>(all, 0, red);
-  if (threadIdx.x == 0) row[cols - sg::kPathCols + sg::kPathHarmonics] = sg::path_to_dB(above / all);
+  harm_frame(work + R.dst0 + (int64_t)F.f * R.cols, R.cols, Z + snds[F.snd].z0 + (int64_t)F.f * B, lab, B, red);
 }
 
 // the launch's constants from the setup: `cols` doubles a row, of which sg_anl_spec blanks the first `fill`
@@ -817,9 +795,146 @@ void check_setup(const sg::AnlSetup& A, const sg::PitchSetup* pitch) {
   }
 }
 
+// a row of the tail: the candidates' columns and sg_path.h's four, as the path's constants have it; `also`: what else
+// the caller requires
+void check_tail_row(const sg::PathPars& P, int cols, int nCands, bool also) {
+  if (P.cols != cols || cols != sg::kAnlFixed + 6 * nCands + sg::kPathCols || !also)
+    throw sg::SgError(SG_E_DEVICE, "analyze: the tail's setup leaves the row");
+}
+
+template <class K>
+void allow_dyn_lds(K kernel, int lds) {
+  if (lds > 48 * 1024)
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+}
+
+// The frames of the sounds of one launch sequence, sound after sound, and where each sound's lie
+struct FrameList {
+  std::vector<AnlFrame> fr;
+  std::vector<int64_t> lens;  // a sound's samples; 0 without frames: a sound of exactly wl samples has a spectrogram frame but no analysis
+  std::vector<int64_t> zoff;  // the first cell of its |X| frames
+  std::vector<int64_t> foff;  // its first frame in fr
+  std::vector<int32_t> nfs;
+  int64_t cells = 0;  // of all |X| frames
+};
+
+// per_sound(c, frames, first frame) runs before sound c's frames are listed: analyze_device refuses a smoothing
+// window there, so that of two refusals the one of the earlier sound is reported
+template <class PerSound>
+FrameList list_frames(const sg::AnlSetup& A, const int64_t* lengths, int64_t n_calls, PerSound&& per_sound) {
+  const sg::SpgSetup& P = A.spg;
+  FrameList L;
+  L.lens.resize(n_calls), L.zoff.resize(n_calls), L.foff.resize(n_calls), L.nfs.resize(n_calls);
+  for (int64_t c = 0; c < n_calls; ++c) {
+    const int nf = sg::anl_frames(A, lengths[c]);
+    L.lens[c] = nf ? lengths[c] : 0;
+    L.zoff[c] = L.cells;
+    L.foff[c] = (int64_t)L.fr.size();
+    L.nfs[c] = nf;
+    per_sound(c, nf, L.foff[c]);
+    if (L.foff[c] + nf > 2147483647LL) throw sg::SgError(SG_E_UNSUPPORTED, "analyze: the frames of one launch exceed 2^31");
+    for (int f = 0; f < nf; ++f) {
+      const int64_t o = sg::spg_frame_start(P, lengths[c], f), a = sg::anl_ampl_start(A, lengths[c], nf, f);
+      if (o < 0 || o + P.wl > lengths[c] || a < 0 || a + P.wl + 1 > lengths[c])
+        throw sg::SgError(SG_E_DEVICE, "analyze: a frame leaves its sound");
+      L.fr.push_back(AnlFrame{o, a, (int32_t)c, f});
+    }
+    L.cells += (int64_t)nf * P.bins;
+  }
+  return L;
+}
+
+// the listed sounds' |X| frames to d_Z (at L.zoff) and their statistics to d_stat
+template <typename T>
+void list_spectra(const sg::SpgSetup& P, const T* d_x, const int64_t* offsets, const FrameList& L, double* d_Z,
+                  SpgStat* d_stat, hipStream_t s) {
+  const int64_t n_calls = (int64_t)L.nfs.size();
+  std::vector<int32_t> b_o(n_calls), f_o(n_calls);
+  sg::spectrogram_device<T>(P, d_x, offsets, L.lens.data(), n_calls, d_Z, L.zoff.data(), b_o.data(), f_o.data(), s, nullptr,
+                            d_stat);
+  for (int64_t c = 0; c < n_calls; ++c)
+    if (f_o[c] != L.nfs[c]) throw sg::SgError(SG_E_DEVICE, "analyze: the spectrogram's frame count differs");
+}
+
+// What the candidate tables of a frame group share: device memory, but for F
+template <typename T>
+struct FrameGroup {
+  const T* x;
+  const AnlFrame* fr;
+  int64_t F;
+  const SpgStat* stat;
+  const double* Z;
+  const double* freq;
+  const double* win;  // nullptr: uploaded by the first table that computes autocorrelations
+  unsigned long long* minampl;
+};
+
+enum CandStage { kCsAmpl = 0, kCsSpec, kCsAcf, kCsPeaks, kCsCep, kCsBana };
+// sg_anl_acf alone; sg_anl_acf that also fills d_store; sg_anl_acf_peaks from d_store
+enum AcfRun { kAcfPlain, kAcfStore, kAcfFromStore };
+
+// The candidate stages for one table of a frame group: rows of `cols` doubles, of which sg_anl_spec blanks the first
+// `fill`, sound c's at d_out + snds[c].row0. pitch: nullptr without the cepstral and the spectral tracker.
+// mark(stage, false) at every stage's boundary in stage order, launched or not (kCsAcf for either autocorrelation
+// kernel; kCsCep and kCsBana only with pitch), then mark(stage, true) right before the stage's launch, behind the host
+// work that prepares it: the caller's clock stamps at the one or at the other.
+template <typename T, class Mark>
+void candidate_stages(DevBuf& db, hipStream_t s, FrameGroup<T>& G, const sg::AnlSetup& A, const sg::PitchSetup* pitch, int cols,
+                      int fill, const AnlSound* d_snd, double* d_out, AcfRun acf, double* d_store, Mark&& mark) {
+  const int wl = A.spg.wl;
+  const dim3 gF((unsigned)G.F), bT(kT);
+  const AnlK K = launch_consts(A, cols, fill);
+  const double* d_xc = upload(db, A.xc, s);
+  auto launch = [&](int stage, auto&& go) {
+    mark(stage, true);
+    go();
+    HIPCHK(hipGetLastError());
+  };
+  mark(kCsAmpl, false);
+  launch(kCsAmpl, [&]() { hipLaunchKernelGGL(sg_anl_ampl<T>, gF, bT, 0, s, G.x, G.fr, d_snd, G.stat, wl, cols, d_out, G.minampl); });
+  mark(kCsSpec, false);
+  launch(kCsSpec, [&]() { hipLaunchKernelGGL(sg_anl_spec, gF, bT, 0, s, G.fr, d_snd, G.Z, G.freq, d_xc, G.minampl, K, d_out); });
+  mark(kCsAcf, false);
+  if (A.do_autocor) {
+    const double* d_lagf = upload(db, A.lagf, s);
+    if (acf == kAcfFromStore) {
+      const int lds = A.nlag * (int)(sizeof(double) + sizeof(int));
+      launch(kCsPeaks, [&]() {
+        allow_dyn_lds(&sg_anl_acf_peaks, lds);
+        hipLaunchKernelGGL(sg_anl_acf_peaks, gF, bT, (size_t)lds, s, G.fr, d_snd, d_store, d_lagf, K, d_out);
+      });
+    } else {
+      if (!G.win) G.win = upload(db, sg::spg_window(wl, A.spg.wn), s);
+      const double* d_filt = upload(db, sg::anl_filter(A), s);
+      const int lds = (wl + 4 + A.nlag) * (int)sizeof(double);
+      const auto kernel = acf == kAcfStore ? &sg_anl_acf<T, true> : &sg_anl_acf<T, false>;
+      launch(kCsAcf, [&]() {
+        allow_dyn_lds(kernel, lds);
+        hipLaunchKernelGGL(kernel, gF, bT, (size_t)lds, s, G.x, G.fr, d_snd, G.stat, G.win, d_filt, d_lagf, K, d_out,
+                           acf == kAcfStore ? d_store : nullptr);
+      });
+    }
+  }
+  mark(kCsCep, false);
+  if (!pitch) return;
+  const sg::PitchSetup& Q = *pitch;
+  const PitchK X = launch_consts(Q, cols);
+  if (Q.do_cep) {
+    const int N = X.odd ? 2 * X.M : X.L;  // fft64 reads W_N^t, t < 2 M
+    double2* d_TN = db.get<double2>((size_t)N);
+    const double* d_cepf = upload(db, Q.cepf, s);
+    sg::fill_roots64(d_TN, N, s);
+    const int lds = (2 * X.M + 32) * (int)sizeof(double2) + (X.l + 1) * (int)sizeof(double);
+    allow_dyn_lds(&sg_anl_cep, lds);
+    launch(kCsCep, [&]() { hipLaunchKernelGGL(sg_anl_cep, gF, bT, (size_t)lds, s, G.fr, d_snd, G.Z, d_TN, d_cepf, X, d_out); });
+  }
+  mark(kCsBana, false);
+  if (Q.do_spec) launch(kCsBana, [&]() { hipLaunchKernelGGL(sg_anl_bana, gF, bT, 0, s, G.fr, d_snd, G.Z, G.freq, X, d_out); });
+}
+
 double g_anl_ms[sg::kAnlStages];  // of the last profiled launch sequence
 double g_sweep_ms[sg::kSweepStages];
-int g_sweep_mode = 1;  // sg_set_analyze_sweep_store
+int g_sweep_store = 1;  // sg_set_analyze_sweep_store
 double g_summary_ms[1];
 double g_pitch_ms[sg::kPitchStages];
 double g_track_ms[sg::kTrackStages];
@@ -851,35 +966,23 @@ void analyze_device(const AnlSetup& A, const T* d_x, const int64_t* offsets, con
                     double* d_out, const int64_t* out_off, int32_t* frames_out, hipStream_t s, double* kernel_ms,
                     const PitchSetup* pitch, const TrackSetup* track, double* d_summary, double* summary_ms) {
   const SpgSetup& P = A.spg;
-  const int B = P.bins, wl = P.wl;
-  std::vector<AnlSound> snds(n_calls);
-  std::vector<AnlFrame> fr;
-  std::vector<int64_t> lens(n_calls), zoff(n_calls);
+  const int B = P.bins;
   std::vector<PathSound> ps(track ? n_calls : 0);
-  std::vector<SumSound> ss(d_summary ? n_calls : 0);
   const int pstride = track ? path_stride(track->path.nCands) : 0;
-  int64_t cells = 0;
-  for (int64_t c = 0; c < n_calls; ++c) {
-    const int nf = anl_frames(A, lengths[c]);
-    lens[c] = nf ? lengths[c] : 0;  // a sound of exactly wl samples has a spectrogram frame but no analysis
-    zoff[c] = cells;
-    snds[c] = AnlSound{offsets[c], lens[c], cells, out_off[c], nf, 0};
+  const FrameList L = list_frames(A, lengths, n_calls, [&](int64_t c, int nf, int64_t f0) {
     frames_out[c] = nf;
     if (track)  // the smoothing window is refused before anything is launched
-      ps[c] = PathSound{out_off[c], (int64_t)fr.size() * pstride, nf, track_hw(track->smooth, P.sr, lengths[c], nf)};
-    if (d_summary) ss[c] = SumSound{out_off[c], lengths[c], nf, 0};
-    if ((int64_t)fr.size() + nf > 2147483647LL) throw SgError(SG_E_UNSUPPORTED, "analyze: the frames of one launch exceed 2^31");
-    for (int f = 0; f < nf; ++f) {
-      const int64_t o = spg_frame_start(P, lengths[c], f), a = anl_ampl_start(A, lengths[c], nf, f);
-      if (o < 0 || o + wl > lengths[c] || a < 0 || a + wl + 1 > lengths[c])
-        throw SgError(SG_E_DEVICE, "analyze: a frame leaves its sound");
-      fr.push_back(AnlFrame{o, a, (int32_t)c, f});
-    }
-    cells += (int64_t)nf * B;
+      ps[c] = PathSound{out_off[c], f0 * pstride, nf, track_hw(track->smooth, P.sr, lengths[c], nf)};
+  });
+  std::vector<AnlSound> snds(n_calls);
+  std::vector<SumSound> ss(d_summary ? n_calls : 0);
+  for (int64_t c = 0; c < n_calls; ++c) {
+    snds[c] = AnlSound{offsets[c], L.lens[c], L.zoff[c], out_off[c], L.nfs[c], 0};
+    if (d_summary) ss[c] = SumSound{out_off[c], lengths[c], L.nfs[c], 0};
   }
   StageClock clk(s, kernel_ms, track ? kTrackStages : pitch ? kPitchStages : kAnlStages);
   clk.zero();
-  const int64_t F = (int64_t)fr.size();
+  const int64_t F = (int64_t)L.fr.size();
   if (d_summary && !track) throw SgError(SG_E_DEVICE, "analyze: the summary needs the tail's columns");
   if (F == 0) {  // nothing to analyse; the summary rows are still written (NaN)
     if (d_summary) summary_device(ss, A.cols, P.sr, d_out, d_summary, s, summary_ms);
@@ -887,72 +990,31 @@ void analyze_device(const AnlSetup& A, const T* d_x, const int64_t* offsets, con
   }
   check_setup(A, pitch);
   DevBuf db;
-  double* d_Z = db.get<double>((size_t)cells);
+  double* d_Z = db.get<double>((size_t)L.cells);
   SpgStat* d_stat = db.get<SpgStat>((size_t)n_calls);
-  std::vector<int32_t> b_o(n_calls), f_o(n_calls);
   clk.stamp();
-  spectrogram_device<T>(P, d_x, offsets, lens.data(), n_calls, d_Z, zoff.data(), b_o.data(), f_o.data(), s, nullptr,
-                        d_stat);
-  for (int64_t c = 0; c < n_calls; ++c)
-    if (f_o[c] != snds[c].nf) throw SgError(SG_E_DEVICE, "analyze: the spectrogram's frame count differs");
+  list_spectra<T>(P, d_x, offsets, L, d_Z, d_stat, s);
   const AnlSound* d_snd = upload(db, snds, s);
-  const AnlFrame* d_fr = upload(db, fr, s);
-  const double* d_freq = upload(db, A.freq, s);
-  const double* d_xc = upload(db, A.xc, s);
-  unsigned long long* d_min = upload(db, std::vector<unsigned long long>(n_calls, dkey(INFINITY)), s);
-  const AnlK K = launch_consts(A, A.cols, track ? A.cols - kPathCols : A.cols);
-  const dim3 gF((unsigned)F), bT(kT);
-  clk.stamp();  // 1: amplitudes
-  hipLaunchKernelGGL(sg_anl_ampl<T>, gF, bT, 0, s, d_x, d_fr, d_snd, d_stat, wl, A.cols, d_out, d_min);
-  HIPCHK(hipGetLastError());
-  clk.stamp();  // 2: descriptives and dom
-  hipLaunchKernelGGL(sg_anl_spec, gF, bT, 0, s, d_fr, d_snd, d_Z, d_freq, d_xc, d_min, K, d_out);
-  HIPCHK(hipGetLastError());
-  clk.stamp();  // 3: autocorrelation and its peaks
-  if (A.do_autocor) {
-    const double* d_win = upload(db, spg_window(wl, P.wn), s);
-    const double* d_filt = upload(db, anl_filter(A), s);
-    const double* d_lagf = upload(db, A.lagf, s);
-    const int lds = (wl + 4 + A.nlag) * (int)sizeof(double);
-    if (lds > 48 * 1024)
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&sg_anl_acf<T, false>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    hipLaunchKernelGGL((sg_anl_acf<T, false>), gF, bT, (size_t)lds, s, d_x, d_fr, d_snd, d_stat, d_win, d_filt, d_lagf, K, d_out,
-                       (double*)nullptr);
-    HIPCHK(hipGetLastError());
-  }
-  clk.stamp();  // 4: the cepstrum and its peaks
+  const AnlFrame* d_fr = upload(db, L.fr, s);
+  FrameGroup<T> G{d_x, d_fr, F, d_stat, d_Z, upload(db, A.freq, s), nullptr,
+                  upload(db, std::vector<unsigned long long>(n_calls, dkey(INFINITY)), s)};
+  // stages 1 to 5 (amplitudes; descriptives and dom; autocorrelation; cepstrum; BaNa): a stamp at every boundary, so a
+  // stage's figure carries the host work that prepares its launch
+  candidate_stages<T>(db, s, G, A, pitch, A.cols, track ? A.cols - kPathCols : A.cols, d_snd, d_out, kAcfPlain, nullptr,
+                      [&](int, bool launching) {
+                        if (!launching) clk.stamp();
+                      });
   if (pitch) {
-    const PitchSetup& Q = *pitch;
-    const PitchK X = launch_consts(Q, A.cols);
-    if (Q.do_cep) {
-      const int N = X.odd ? 2 * X.M : X.L;  // fft64 reads W_N^t, t < 2 M
-      double2* d_TN = db.get<double2>((size_t)N);
-      const double* d_cepf = upload(db, Q.cepf, s);
-      fill_roots64(d_TN, N, s);
-      const int lds = (2 * X.M + 32) * (int)sizeof(double2) + (X.l + 1) * (int)sizeof(double);
-      if (lds > 48 * 1024)
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&sg_anl_cep), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   lds));
-      hipLaunchKernelGGL(sg_anl_cep, gF, bT, (size_t)lds, s, d_fr, d_snd, d_Z, d_TN, d_cepf, X, d_out);
-      HIPCHK(hipGetLastError());
-    }
-    clk.stamp();  // 5: the spectral peaks and the BaNa candidates
-    if (Q.do_spec) {
-      hipLaunchKernelGGL(sg_anl_bana, gF, bT, 0, s, d_fr, d_snd, d_Z, d_freq, X, d_out);
-      HIPCHK(hipGetLastError());
-    }
     clk.stamp();
     if (track) {  // 6: voiced segments, pathfinder, smoother, final columns
-      if (track->path.cols != A.cols || A.cols != kAnlFixed + 6 * A.nCands + kPathCols || (int)track->lab.size() != B)
-        throw SgError(SG_E_DEVICE, "analyze: the tail's setup leaves the row");
+      check_tail_row(track->path, A.cols, A.nCands, (int)track->lab.size() == B);
       const PathSound* d_ps = upload(db, ps, s);
       double* d_scr = db.get<double>((size_t)F * pstride);
       const double* d_lab = upload(db, track->lab, s);
       hipLaunchKernelGGL(sg_anl_path, dim3((unsigned)n_calls), dim3(kPathT), 0, s, d_ps, track->path, d_out, d_scr);
       HIPCHK(hipGetLastError());
       clk.stamp();  // 7: harmonics
-      hipLaunchKernelGGL(sg_anl_harm, gF, bT, 0, s, d_fr, d_snd, d_Z, d_lab, B, A.cols, d_out);
+      hipLaunchKernelGGL(sg_anl_harm, dim3((unsigned)F), dim3(kT), 0, s, d_fr, d_snd, d_Z, d_lab, B, A.cols, d_out);
       HIPCHK(hipGetLastError());
       clk.stamp();
     }
@@ -976,8 +1038,7 @@ void path_device(const PathPars& P, int frames, int hw, double* d_rows, hipStrea
   StageClock clk(s, kernel_ms ? &ms : nullptr, 1);
   for (int k = 0; kernel_ms && k < kTrackStages; ++k) kernel_ms[k] = 0;
   if (frames <= 0) return;
-  if (P.cols != kAnlFixed + 6 * P.nCands + kPathCols || P.nCands < 1 || P.nCands > kAnlMaxCands || hw < 0)
-    throw SgError(SG_E_DEVICE, "analyze: the tail's setup leaves the row");
+  check_tail_row(P, P.cols, P.nCands, P.nCands >= 1 && P.nCands <= kAnlMaxCands && hw >= 0);
   DevBuf db;
   const PathSound* d_ps = upload(db, std::vector<PathSound>(1, PathSound{0, 0, frames, hw}), s);
   double* d_scr = db.get<double>((size_t)frames * path_stride(P.nCands));
@@ -1024,12 +1085,9 @@ int frames_batch(sg_ctx* ctx, const sg::AnlSetup& S, const sg::PitchSetup* pitch
 // the stages of sg_debug_analyze_sweep_kernel_ms
 enum SweepStage { kSwSpg = 0, kSwAmpl, kSwSpec, kSwAcf, kSwPeaks, kSwCep, kSwBana, kSwPath, kSwHarm, kSwSummary };
 static_assert(kSwSummary + 1 == sg::kSweepStages, "ten stages");
-
-template <class K>
-void allow_dyn_lds(K kernel, int lds) {
-  if (lds > 48 * 1024)
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-}
+static_assert(kSwSpec - kSwAmpl == kCsSpec && kSwAcf - kSwAmpl == kCsAcf && kSwPeaks - kSwAmpl == kCsPeaks &&
+                  kSwCep - kSwAmpl == kCsCep && kSwBana - kSwAmpl == kCsBana,
+              "stage kSwAmpl + k is candidate_stages' stage k");
 
 // sg_analyze_sweep: n_rows parameter rows over n_calls sounds (the header's text). Frame groups run one after
 // another; within one, the candidate groups in the order of their store groups, so that a store's users follow each
@@ -1045,12 +1103,11 @@ void analyze_sweep(sg_ctx* ctx, const float* d_x, const int64_t* offsets, const 
   for (int64_t r = 0; r < n_rows; ++r) {
     const TrackSetup& S = W.S[r];
     check_setup(S, &S);
-    if (S.path.cols != S.cols || S.cols != kAnlFixed + 6 * S.nCands + kPathCols || (int)S.lab.size() != S.spg.bins)
-      throw SgError(SG_E_DEVICE, "analyze: the tail's setup leaves the row");
+    check_tail_row(S.path, S.cols, S.nCands, (int)S.lab.size() == S.spg.bins);
     pars[r] = S.path;
   }
   const int64_t cap = workspace_cap > 0 ? workspace_cap : kSweepWorkspaceCap;
-  const bool use_store = g_sweep_mode & 1, copy_ampl = g_sweep_mode & 2, wave_peaks = g_sweep_mode & 4;
+  const bool use_store = g_sweep_store != 0;
   hipStream_t s = ctx->stream;
   HIPCHK(hipSetDevice(ctx->device));
   StageClock clk(s, ctx->profiling ? g_sweep_ms : nullptr, kSweepStages);
@@ -1081,29 +1138,11 @@ void analyze_sweep(sg_ctx* ctx, const float* d_x, const int64_t* offsets, const 
         if (W.cand_group[r] == cgs[i]) frows.push_back(r);
     const TrackSetup& A = W.S[frows[0]];
     const SpgSetup& P = A.spg;
-    const int B = P.bins, wl = P.wl;
-    // the frames, as analyze_device lists them
-    std::vector<AnlFrame> fr;
-    std::vector<int64_t> lens(n_calls), zoff(n_calls), foff(n_calls);
-    std::vector<int32_t> nfs(n_calls);
-    int64_t cells = 0;
-    for (int64_t c = 0; c < n_calls; ++c) {
-      const int nf = anl_frames(A, lengths[c]);
-      lens[c] = nf ? lengths[c] : 0;
-      zoff[c] = cells;
-      foff[c] = (int64_t)fr.size();
-      nfs[c] = nf;
-      if ((int64_t)fr.size() + nf > 2147483647LL) throw SgError(SG_E_UNSUPPORTED, "analyze: the frames of one launch exceed 2^31");
-      for (int f = 0; f < nf; ++f) {
-        const int64_t o = spg_frame_start(P, lengths[c], f), a = anl_ampl_start(A, lengths[c], nf, f);
-        if (o < 0 || o + wl > lengths[c] || a < 0 || a + wl + 1 > lengths[c])
-          throw SgError(SG_E_DEVICE, "analyze: a frame leaves its sound");
-        fr.push_back(AnlFrame{o, a, (int32_t)c, f});
-      }
-      cells += (int64_t)nf * B;
-    }
-    const int64_t F = (int64_t)fr.size();
-    const dim3 gF((unsigned)F), bT(kT);
+    const int B = P.bins;
+    const FrameList L = list_frames(A, lengths, n_calls, [](int64_t, int, int64_t) {});
+    const std::vector<int64_t>& foff = L.foff;
+    const std::vector<int32_t>& nfs = L.nfs;
+    const int64_t F = (int64_t)L.fr.size();
     DevBuf db;
     // where each candidate group's tables lie in the one buffer, and its view of the sounds
     std::vector<int64_t> cand0(cgs.size());
@@ -1133,23 +1172,18 @@ void analyze_sweep(sg_ctx* ctx, const float* d_x, const int64_t* offsets, const 
     double* d_work = d_cand + cand_cells;
     double* d_Z = nullptr;
     const AnlFrame* d_fr = nullptr;
-    const AnlSound* d_snd0 = nullptr;  // the first candidate group's
+    const AnlSound* d_zs = nullptr;  // the sounds' |X| frames (z0) for sg_anl_sweep_harm: any candidate group's view
     const double* d_lab = nullptr;
     if (F > 0) {
-      d_Z = db.get<double>((size_t)cells);
+      d_Z = db.get<double>((size_t)L.cells);
       SpgStat* d_stat = db.get<SpgStat>((size_t)n_calls);
-      std::vector<int32_t> b_o(n_calls), f_o(n_calls);
-      timed(kSwSpg, [&]() {
-        spectrogram_device<float>(P, d_x, offsets, lens.data(), n_calls, d_Z, zoff.data(), b_o.data(), f_o.data(), s, nullptr,
-                                  d_stat);
-      });
-      for (int64_t c = 0; c < n_calls; ++c)
-        if (f_o[c] != nfs[c]) throw SgError(SG_E_DEVICE, "analyze: the spectrogram's frame count differs");
-      d_fr = upload(db, fr, s);
+      timed(kSwSpg, [&]() { list_spectra<float>(P, d_x, offsets, L, d_Z, d_stat, s); });
+      d_fr = upload(db, L.fr, s);
       d_lab = upload(db, A.lab, s);
       const double* d_freq = upload(db, A.freq, s);
-      const double* d_win = upload(db, spg_window(wl, P.wn), s);
-      unsigned long long* d_min = upload(db, std::vector<unsigned long long>(n_calls, dkey(INFINITY)), s);
+      const double* d_win = upload(db, spg_window(P.wl, P.wn), s);
+      FrameGroup<float> G{d_x, d_fr, F, d_stat, d_Z, d_freq, d_win,
+                          upload(db, std::vector<unsigned long long>(n_calls, dkey(INFINITY)), s)};
       // one buffer for the stores that are built: shared by two candidate groups or more, and within the cap
       std::vector<int> users((size_t)std::max(W.n_store, 1), 0);
       int64_t store_cells = 0;
@@ -1163,79 +1197,22 @@ void analyze_sweep(sg_ctx* ctx, const float* d_x, const int64_t* offsets, const 
         if (built(rep[i])) store_cells = std::max(store_cells, F * W.S[rep[i]].nlag);
       double* d_store = store_cells ? db.get<double>((size_t)store_cells) : nullptr;
       int filled = -1;  // the store group whose values d_store holds
-      int first_cols = 0;
       for (size_t i : order) {
         const TrackSetup& S = W.S[rep[i]];
         const int cols = S.cols - kPathCols;
         std::vector<AnlSound> snds(n_calls);
         for (int64_t c = 0; c < n_calls; ++c)
-          snds[c] = AnlSound{offsets[c], lens[c], zoff[c], cand0[i] + foff[c] * cols, nfs[c], 0};
-        const AnlSound* d_snd = upload(db, snds, s);
-        const AnlK K = launch_consts(S, cols, cols);
-        if (!d_snd0 || !copy_ampl) {
-          timed(kSwAmpl, [&]() {
-            hipLaunchKernelGGL(sg_anl_ampl<float>, gF, bT, 0, s, d_x, d_fr, d_snd, d_stat, wl, cols, d_cand, d_min);
-          });
-        } else {
-          timed(kSwAmpl, [&]() {
-            hipLaunchKernelGGL(sg_anl_sweep_ampl, dim3((unsigned)((F + kT - 1) / kT)), bT, 0, s, d_fr, d_snd0, d_snd, F,
-                               first_cols, cols, d_cand, d_cand);
-          });
-        }
-        if (!d_snd0) {
-          d_snd0 = d_snd;
-          first_cols = cols;
-        }
-        const double* d_xc = upload(db, S.xc, s);
-        timed(kSwSpec, [&]() { hipLaunchKernelGGL(sg_anl_spec, gF, bT, 0, s, d_fr, d_snd, d_Z, d_freq, d_xc, d_min, K, d_cand); });
-        if (S.do_autocor) {
-          const double* d_lagf = upload(db, S.lagf, s);
-          const int sgp = W.store_group[rep[i]];
-          if (built(rep[i]) && filled == sgp) {
-            const int lds = S.nlag * (int)(sizeof(double) + sizeof(int));
-            timed(kSwPeaks, [&]() {
-              if (wave_peaks) {
-                allow_dyn_lds(&sg_anl_acf_peaks<64>, lds);
-                hipLaunchKernelGGL(sg_anl_acf_peaks<64>, gF, dim3(64), (size_t)lds, s, d_fr, d_snd, d_store, d_lagf, K, d_cand);
-              } else {
-                allow_dyn_lds(&sg_anl_acf_peaks<kT>, lds);
-                hipLaunchKernelGGL(sg_anl_acf_peaks<kT>, gF, bT, (size_t)lds, s, d_fr, d_snd, d_store, d_lagf, K, d_cand);
-              }
-            });
-          } else {
-            const double* d_filt = upload(db, anl_filter(S), s);
-            const int lds = (wl + 4 + S.nlag) * (int)sizeof(double);
-            timed(kSwAcf, [&]() {
-              if (built(rep[i])) {
-                allow_dyn_lds(&sg_anl_acf<float, true>, lds);
-                hipLaunchKernelGGL((sg_anl_acf<float, true>), gF, bT, (size_t)lds, s, d_x, d_fr, d_snd, d_stat, d_win, d_filt,
-                                   d_lagf, K, d_cand, d_store);
-                filled = sgp;
-              } else {
-                allow_dyn_lds(&sg_anl_acf<float, false>, lds);
-                hipLaunchKernelGGL((sg_anl_acf<float, false>), gF, bT, (size_t)lds, s, d_x, d_fr, d_snd, d_stat, d_win, d_filt,
-                                   d_lagf, K, d_cand, (double*)nullptr);
-              }
-            });
-          }
-        }
-        const PitchK X = launch_consts(S, cols);
-        if (S.do_cep) {
-          const int N = X.odd ? 2 * X.M : X.L;  // fft64 reads W_N^t, t < 2 M
-          double2* d_TN = db.get<double2>((size_t)N);
-          const double* d_cepf = upload(db, S.cepf, s);
-          fill_roots64(d_TN, N, s);
-          const int lds = (2 * X.M + 32) * (int)sizeof(double2) + (X.l + 1) * (int)sizeof(double);
-          allow_dyn_lds(&sg_anl_cep, lds);
-          timed(kSwCep,
-                [&]() { hipLaunchKernelGGL(sg_anl_cep, gF, bT, (size_t)lds, s, d_fr, d_snd, d_Z, d_TN, d_cepf, X, d_cand); });
-        }
-        if (S.do_spec)
-          timed(kSwBana, [&]() { hipLaunchKernelGGL(sg_anl_bana, gF, bT, 0, s, d_fr, d_snd, d_Z, d_freq, X, d_cand); });
+          snds[c] = AnlSound{offsets[c], L.lens[c], L.zoff[c], cand0[i] + foff[c] * cols, nfs[c], 0};
+        d_zs = upload(db, snds, s);
+        const int sgp = W.store_group[rep[i]];
+        const AcfRun acf = !built(rep[i]) ? kAcfPlain : filled == sgp ? kAcfFromStore : kAcfStore;
+        if (acf == kAcfStore) filled = sgp;
+        // a stamp only where a stage launches, under the stage's label
+        candidate_stages<float>(db, s, G, S, &S, cols, cols, d_zs, d_cand, acf, d_store, [&](int stage, bool launching) {
+          if (launching) clk.stamp(kSwAmpl + stage);
+        });
       }
     }
-    const AnlSound* d_zs = nullptr;  // the sounds' |X| frames (z0) for sg_anl_sweep_harm
-    if (F > 0) d_zs = d_snd0;
     size_t k0 = 0;
     for (size_t k1 : chunk_end) {
       std::vector<SweepPair> pairs;
@@ -1265,7 +1242,7 @@ void analyze_sweep(sg_ctx* ctx, const float* d_x, const int64_t* offsets, const 
       if (F > 0) {
         timed(kSwPath, [&]() { hipLaunchKernelGGL(sg_anl_sweep_path, gP, dim3(kPathT), 0, s, d_pairs, d_pars, d_cand, d_work); });
         timed(kSwHarm, [&]() {
-          hipLaunchKernelGGL(sg_anl_sweep_harm, dim3((unsigned)F, (unsigned)(k1 - k0)), bT, 0, s, d_fr, d_zs, d_pairs,
+          hipLaunchKernelGGL(sg_anl_sweep_harm, dim3((unsigned)F, (unsigned)(k1 - k0)), dim3(kT), 0, s, d_fr, d_zs, d_pairs,
                              (int)n_calls, d_Z, d_lab, B, d_work);
         });
       }
@@ -1459,8 +1436,8 @@ int sg_analyze_sweep(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, c
 }
 
 int sg_set_analyze_sweep_store(int32_t mode) {
-  if (mode < 0 || mode > 7) return SG_E_ARG;
-  g_sweep_mode = mode;
+  if (mode != 0 && mode != 1) return SG_E_ARG;
+  g_sweep_store = mode;
   return SG_OK;
 }
 

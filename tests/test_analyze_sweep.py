@@ -325,7 +325,7 @@ def _caps():
 @pytest.mark.gpu
 def test_sweep_does_not_depend_on_the_launch():
     """The same bits with the rows reversed, row by row, with the sounds reversed, with the store off, and under
-    the three caps."""
+    the three caps. sg_set_analyze_sweep_store refuses every mode but 0 and 1 and then leaves the mode as it was."""
     want = _bits(_swept())
     assert np.array_equal(_bits(_sweep(tuple(range(10, -1, -1)))[::-1]), want)
     for r in range(11):
@@ -333,9 +333,18 @@ def test_sweep_does_not_depend_on_the_launch():
     assert np.array_equal(_bits(_sweep(sounds=tuple(range(5, -1, -1)))[:, ::-1]), want)
     L = native.lib()
     try:
-        for mode in (0, 3, 5):  # the store off; the amplitudes copied; the peak picker as one wave
-            assert L.sg_set_analyze_sweep_store(mode) == 0
-            assert np.array_equal(_bits(_sweep()), want), mode
+        assert L.sg_set_analyze_sweep_store(0) == 0  # the store off
+        assert np.array_equal(_bits(_sweep()), want)
+        assert L.sg_set_analyze_sweep_store(1) == 0
+        for mode in (2, 3, 5, 8):  # SG_E_ARG, and mode 1 stays in force
+            assert L.sg_set_analyze_sweep_store(mode) == -1, mode
+        ctx = native.default_context(0)
+        L.sg_set_profiling(ctx.ptr, 1)
+        try:
+            _sweep()
+        finally:
+            L.sg_set_profiling(ctx.ptr, 0)
+        assert AN.sweep_kernel_ms()["autocorrelation (peaks only)"] > 0
     finally:
         L.sg_set_analyze_sweep_store(1)
     for name, cap in _caps().items():

@@ -11,9 +11,7 @@ C5 preset calls of tools/segment_sweep_bench.py already in HBM, and prints one J
 Arms, each followed by sweep_fitness on the device:
   * loop         one analyze_batch(summary=True) per row (what optimize_pars() ran before);
   * sweep        analyze_sweep with the autocorrelation store on (the default);
-  * sweep_off    the store off (sg_set_analyze_sweep_store(0));
-  * sweep_copy   the store on, the amplitudes copied between candidate tables (mode 3);
-  * sweep_wave   the store on, the peak picker as one wave per frame (mode 5).
+  * sweep_off    the store off (sg_set_analyze_sweep_store(0)).
 After --warmup runs of each arm, --steps runs of each in turn with profiling off, every run on record;
 then --steps profiled runs of each sweep arm record the device time of the ten stages
 (sg_debug_analyze_sweep_kernel_ms), so that the stage clock's events stay out of the wall times.
@@ -35,7 +33,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-MODES = {"sweep": 1, "sweep_off": 0, "sweep_copy": 3, "sweep_wave": 5}
+MODES = {"sweep": 1, "sweep_off": 0}
 
 
 def row_sets():
