@@ -981,6 +981,33 @@ int sg_debug_wave_fft(sg_ctx* ctx, int32_t wl, int32_t inverse, int32_t nframes,
  * NULL then, out is left alone), for M < 1, M > 2048 or M not 31-smooth. */
 int sg_debug_fft64(sg_ctx* ctx, int32_t M, int32_t inverse, int32_t nframes,
                    const double* in, double* out);
+/* Test hook, no reference counterpart: the six sine-bank kernels (sg_sine_bank,
+ * _pairs, _tall, _tall_pairs, _hp, _tab) on caller-built wave tasks, through the
+ * product's classifier and launchers. tasks: ntasks records of 128 bytes laid out as
+ * SgWTask (csrc/sg_dev.h); amps: namps floats, the columns the tasks' a_off / d_off
+ * index; wlen: elements of the epoch scratch the tasks' w_off + j index; jobs
+ * (NULL with njobs 0: none): njobs records of 32 bytes laid out as SgTabJob with
+ * flags 0, whose tasks run on the wavetable path; env: the flat amplitude
+ * envelope of every syllable with a task flagged SG_TASK_ENV (4).
+ * Every byte of the three outputs is first set to 0xFF on the device (a NaN in
+ * either precision), then each class is launched once and the table jobs once per
+ * logn: W (wlen floats) and W64 (wlen doubles) receive the fp32 and the fp64
+ * scratch, taskmax (ntasks floats) the per-task maxima, cls (ntasks) each task's
+ * class: 0 sg_sine_bank, 1 _pairs, 2 _tall, 3 _tall_pairs, 4 _hp, 5 _tab.
+ * SG_E_ARG, before anything touches the device, unless every task has
+ *   1 <= len <= 1024; R > 0 and a multiple of 16; 0 < Rn <= R, a multiple of 4;
+ *   j0 >= 0; 0 <= mbase <= 2^30; 0 <= w_off + j0 and w_off + j0 + len <= wlen;
+ *   0 <= a_off, d_off and a_off + R, d_off + R <= namps; 0 <= dj0 <= dj1; syl >= 0;
+ *   flags within 1 | 2 | 4 | 8, not 2 and 4 together; finite coefficients;
+ *   the tasks of one syl next to each other,
+ * and every job
+ *   flags 0; 1 <= n <= 64; 0 <= t0, t0 + n <= ntasks, past the job before it;
+ *   8 <= logn <= 11; 4 <= Rn <= 96; 0 <= a_off, a_off + Rn <= namps; every task of
+ *   it with flags 1 | 2 exactly, R <= 96 and the job's a_off and Rn,
+ * and 1 <= ntasks <= 2^20, 1 <= wlen <= 2^26, 1 <= namps <= 2^26, env finite. */
+int sg_debug_sine_bank(sg_ctx* ctx, const void* tasks, int64_t ntasks, const float* amps, int64_t namps,
+                       int64_t wlen, const void* jobs, int64_t njobs, double env,
+                       float* W, double* W64, float* taskmax, int32_t* cls);
 /* Test hook, no reference counterpart: the tile map of ssm()'s Gram kernel
  * (sg_ssm_gram, one wavefront per 16 x 16 tile on the fp64 matrix pipe). feat
  * holds n vectors of L doubles one after another (host); out (host, n * n

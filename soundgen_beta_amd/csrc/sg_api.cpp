@@ -17,6 +17,7 @@
 #include "sg_plan.h"
 #include "sg_exec.h"
 #include "sg_amp.h"
+#include "sg_sine_check.h"
 #include "sg_prof.h"
 #include "sg_mel.h"
 #include "sg_launch.h"
@@ -982,6 +983,23 @@ int sg_debug_wave_fft(sg_ctx* ctx, int32_t wl, int32_t inverse, int32_t nframes,
     (void)hipFree(dg);
     (void)hipFree(dfl);
     (void)hipFree(dd);
+    return SG_OK;
+  });
+}
+
+// Test hook (not part of the reference surface): the sine-bank kernels on caller-built
+// tasks (sg_exec.cpp: debug_sine_bank). Every refusal precedes the first HIP call.
+int sg_debug_sine_bank(sg_ctx* ctx, const void* tasks, int64_t ntasks, const float* amps, int64_t namps, int64_t wlen,
+                       const void* jobs, int64_t njobs, double env, float* W, double* W64, float* taskmax,
+                       int32_t* cls) {
+  return guarded(ctx, [&]() {
+    const SgWTask* t = static_cast<const SgWTask*>(tasks);
+    const SgTabJob* j = static_cast<const SgTabJob*>(jobs);
+    if (const char* why = sg::sine_bank_args_check(t, ntasks, namps, wlen, j, njobs, env))
+      throw sg::SgError(SG_E_ARG, std::string("sg_debug_sine_bank: ") + why);
+    if (!ctx || !amps || !W || !W64 || !taskmax || !cls) throw sg::SgError(SG_E_ARG, "sg_debug_sine_bank: null argument");
+    HIPCHK(hipSetDevice(ctx->device));
+    sg::debug_sine_bank(ctx->stream, t, ntasks, amps, namps, wlen, j, njobs, env, W, W64, taskmax, cls);
     return SG_OK;
   });
 }

@@ -1,6 +1,7 @@
 // sg_exec.cpp — HBM arena for a plan and the per-batch launch sequence.
 #include "sg_exec.h"
 #include "sg_amp.h"
+#include "sg_sine_check.h"
 #include "sg_prof.h"
 
 #include <algorithm>
@@ -15,6 +16,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
 
 namespace sg {
 
@@ -910,6 +912,109 @@ void device_execute_spec(const Batch& B, const DevicePlan& D, float* d_out, hipS
   phase(1);
   launch_mix(D, B.mixtile_split, (int64_t)B.mixtiles.size() - B.mixtile_split, d_out, s);
   HIPCHK(hipGetLastError());
+}
+
+// ------------------------------------------- test hook sg_debug_sine_bank
+namespace {
+struct DevMem {  // device buffers of the hook, freed on every way out
+  std::vector<void*> p;
+  template <class T>
+  T* get(size_t n) {
+    void* q = nullptr;
+    HIPCHK(hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)));
+    p.push_back(q);
+    return static_cast<T*>(q);
+  }
+  ~DevMem() {
+    for (void* q : p) (void)hipFree(q);
+  }
+};
+}  // namespace
+
+// The product's classifier and launchers on caller-built tasks (soundgen_hip.h). The
+// device copy of the tasks carries the syllables renumbered 0, 1, ... in order of
+// appearance (one SgSyllable each); nothing else of a record changes.
+void debug_sine_bank(hipStream_t s, const SgWTask* tasks, int64_t ntasks, const float* amps, int64_t namps, int64_t wlen,
+                     const SgTabJob* jobs, int64_t njobs, double env, float* W, double* W64, float* taskmax,
+                     int32_t* cls) {
+  if (const char* why = sine_bank_args_check(tasks, ntasks, namps, wlen, jobs, njobs, env))
+    throw SgError(SG_E_ARG, std::string("sg_debug_sine_bank: ") + why);
+  if (!amps || !W || !W64 || !taskmax || !cls) throw SgError(SG_E_ARG, "sg_debug_sine_bank: null buffer");
+  std::vector<SgWTask> T(tasks, tasks + ntasks);
+  std::vector<SgSyllable> syls;
+  for (int64_t i = 0; i < ntasks; ++i) {
+    if (i == 0 || tasks[i].syl != tasks[i - 1].syl) {
+      SgSyllable sy{};
+      sy.env.lo = -INFINITY;
+      sy.env.hi = INFINITY;
+      sy.env.a = env;
+      sy.task0 = i;
+      sy.max_slot = (int32_t)syls.size();
+      syls.push_back(sy);
+    }
+    SgSyllable& sy = syls.back();
+    ++sy.ntask;
+    if (tasks[i].flags & SG_TASK_ENV) sy.env.kind = 1;
+    T[(size_t)i].syl = (int32_t)syls.size() - 1;
+  }
+  // table jobs in launch order (one launch per logn), their tasks out of the classes
+  std::vector<SgTabJob> J(jobs, jobs + njobs);
+  std::stable_sort(J.begin(), J.end(), [](const SgTabJob& a, const SgTabJob& b) { return a.logn < b.logn; });
+  std::vector<uint8_t> in_tab((size_t)ntasks, 0);
+  for (const SgTabJob& j : J)
+    for (int32_t q = j.t0; q < j.t0 + j.n; ++q) in_tab[(size_t)q] = 1;
+  TaskClasses C;
+  classify_block(TaskBlock{0, T.data(), ntasks}, in_tab, C);
+  C.srun.push_back((int32_t)C.tshort.size());
+  C.trun.push_back((int32_t)C.tallp.size());
+  for (int64_t i = 0; i < ntasks; ++i) cls[i] = 5;
+  const std::vector<int32_t>* lists[5] = {&C.tlong, &C.tshort, &C.tall, &C.tallp, &C.thp};
+  for (int c = 0; c < 5; ++c)
+    for (int32_t i : *lists[c]) cls[i] = c;
+
+  DevMem M;
+  DevicePlan D;
+  auto put = [&](const auto& v) {
+    using V = typename std::decay_t<decltype(v)>::value_type;
+    V* d = M.get<V>(v.size());
+    if (!v.empty()) HIPCHK(hipMemcpyAsync(d, v.data(), v.size() * sizeof(V), hipMemcpyHostToDevice, s));
+    return d;
+  };
+  D.tasks = put(T);
+  D.syls = put(syls);
+  D.tlong = put(C.tlong);
+  D.tshort = put(C.tshort);
+  D.tall = put(C.tall);
+  D.tallp = put(C.tallp);
+  D.thp = put(C.thp);
+  D.srun = put(C.srun);
+  D.trun = put(C.trun);
+  D.tabjobs = put(J);
+  D.amps = M.get<float>((size_t)namps);
+  HIPCHK(hipMemcpyAsync(D.amps, amps, (size_t)namps * sizeof(float), hipMemcpyHostToDevice, s));
+  D.cknots = M.get<double>(1);  // no contour of the hook's syllables has knots
+  D.W = M.get<float>((size_t)wlen);
+  D.W64 = M.get<double>((size_t)wlen);
+  D.taskmax = M.get<float>((size_t)ntasks);
+  HIPCHK(hipMemsetAsync(D.cknots, 0, sizeof(double), s));
+  HIPCHK(hipMemsetAsync(D.W, 0xFF, (size_t)wlen * sizeof(float), s));
+  HIPCHK(hipMemsetAsync(D.W64, 0xFF, (size_t)wlen * sizeof(double), s));
+  HIPCHK(hipMemsetAsync(D.taskmax, 0xFF, (size_t)ntasks * sizeof(float), s));
+  launch_sine_bank_hp(D, (int64_t)C.thp.size(), s);
+  launch_sine_bank(D, 0, (int64_t)C.tlong.size(), s);
+  launch_sine_bank_pairs(D, 0, (int64_t)C.srun.size() - 1, s);
+  launch_sine_bank_tall(D, 0, (int64_t)C.tall.size(), s);
+  launch_sine_bank_tall_pairs(D, 0, (int64_t)C.trun.size() - 1, s);
+  for (size_t a = 0; a < J.size();) {  // W mode: no output buffer
+    size_t b = a;
+    while (b < J.size() && J[b].logn == J[a].logn) ++b;
+    launch_sine_bank_tab(D, J[a].logn, (int64_t)a, (int64_t)(b - a), nullptr, s);
+    a = b;
+  }
+  HIPCHK(hipStreamSynchronize(s));
+  HIPCHK(hipMemcpy(W, D.W, (size_t)wlen * sizeof(float), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(W64, D.W64, (size_t)wlen * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(taskmax, D.taskmax, (size_t)ntasks * sizeof(float), hipMemcpyDeviceToHost));
 }
 
 }  // namespace sg

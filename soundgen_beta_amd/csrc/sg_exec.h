@@ -120,6 +120,12 @@ void device_execute_many(const std::vector<PlanRun>& runs, hipStream_t s, hipStr
 void device_execute_spec(const Batch& B, const DevicePlan& D, float* d_out, hipStream_t s,
                          std::vector<SgProfEvent>* prof, bool join = false, hipEvent_t harm_done = nullptr);
 
+// Test hook sg_debug_sine_bank (soundgen_hip.h) on stream s, after sine_bank_args_check
+// (sg_sine_check.h); throws SgError
+void debug_sine_bank(hipStream_t s, const SgWTask* tasks, int64_t ntasks, const float* amps, int64_t namps, int64_t wlen,
+                     const SgTabJob* jobs, int64_t njobs, double env, float* W, double* W64, float* taskmax,
+                     int32_t* cls);
+
 // launchers (sg_harm.hip)
 void launch_amp_build(const DevicePlan& D, int64_t n_jobs, hipStream_t s);
 void launch_ugather(const SgUJob* jobs, int64_t n_jobs, const float* us, float* fl, hipStream_t s);

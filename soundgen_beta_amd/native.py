@@ -118,6 +118,9 @@ def lib():
         L.sg_debug_spectrogram_kernel_ms.argtypes = [dp]
     if hasattr(L, "sg_debug_fft64"):  # the fp64 transform alone (tests/test_fft64.py): likewise additive
         L.sg_debug_fft64.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, dp, dp]
+    if hasattr(L, "sg_debug_sine_bank"):  # the sine-bank kernels on caller-built tasks (tests/test_sine_bank.py)
+        L.sg_debug_sine_bank.argtypes = [vp, vp, i64, C.POINTER(C.c_float), i64, i64, vp, i64, C.c_double,
+                                         C.POINTER(C.c_float), dp, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
     if hasattr(L, "sg_analyze_frames_size"):  # analyze()'s per-frame stage: likewise additive
         i32p = C.POINTER(C.c_int32)
         app = C.POINTER(_abi.sg_analyze_params)

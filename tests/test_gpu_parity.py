@@ -158,6 +158,38 @@ def test_planner_cases_one_batch(oracle):
     print("worst rms", worst)
 
 
+def test_oracle_compared_cases_reach_every_sine_bank_kernel():
+    """What the oracle comparisons of this suite exercise, kernel by kernel: the planner
+    cases above, the tones of test_c2_tones_batch, the first C5 calls (tests/test_gpu_spectral.py
+    compares the first 128) and C5 calls with every filtered bout on the fp64 path
+    (test_c5_every_preset_vs_oracle, policy 2), planned and uploaded, must put tasks on each of
+    the five row-recurrence kernels and spans on the wavetable kernel. tests/test_sine_bank.py
+    holds each kernel alone to a per-sample bound; this keeps the end-to-end bar on all of them."""
+    import bench
+    from soundgen_beta_amd import batch, native
+    L = native.lib()
+    ctx = native.default_context(0)
+    c5 = bench.c5_calls(128)
+    batches = [(1, [{"kind": "harmonics", "pitch": p, "params": prm, "normals": NORMALS, "uniforms": UNIFORMS}
+                    for _, p, prm in CASES]
+                + [{"kind": "harmonics", "pitch": np.full(3500, f), "params": C2} for f in (110.0, 230.0)]),
+               (1, c5[:32]), (2, c5[:32])]
+    counts, tables = np.zeros(5, np.int64), 0
+    for policy, calls in batches:
+        assert L.sg_set_fp64_policy(policy, native.HP_RHO_DEFAULT) == 0
+        try:
+            plan = batch.Plan(calls, ctx)
+            assert (plan.status == 0).all()
+            plan.upload()
+        finally:
+            L.sg_set_fp64_policy(1, native.HP_RHO_DEFAULT)
+        print("policy", policy, len(calls), "calls: sine tasks", plan.sine_tasks(), "tables", plan.table_stats()[0])
+        counts += plan.sine_tasks()
+        tables += plan.table_stats()[0]
+    assert (counts > 0).all(), counts
+    assert tables > 0
+
+
 def test_ampl_anchors_and_contours(oracle):
     from soundgen_beta_amd import batch
     t = np.linspace(0, 1, 3500)
