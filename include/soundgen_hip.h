@@ -361,6 +361,35 @@ int sg_mel_spec(sg_ctx* ctx, const double* wave, int64_t len, const sg_mel_param
 int sg_compare_sounds_batch(sg_ctx* ctx, const double* target_spec, int32_t nb, int32_t nc_target,
                             const float* d_wave, const int64_t* offsets, const int64_t* lengths, int64_t n,
                             const sg_mel_params* p, int32_t methods, double* out, double* summary);
+/* A set of mel spectra resident in DEVICE memory (an additive extension of ABI 5):
+ * getMelSpec() of n sounds in device memory (fp32, or fp64 with is_f64 != 0; sound i at
+ * d_wave + offsets[i], lengths[i] samples, the layout of sg_compare_sounds_batch;
+ * lengths[i] <= 0: skipped), computed once under p and kept until sg_mel_set_destroy. The
+ * waveform is not referenced after sg_mel_set_create returns. penalizeLengthDif of p is not
+ * read here. */
+typedef struct sg_mel_set sg_mel_set;
+int sg_mel_set_create(sg_ctx* ctx, const void* d_wave, int32_t is_f64, const int64_t* offsets,
+                      const int64_t* lengths, int64_t n, const sg_mel_params* p, sg_mel_set** out);
+/* The set's sounds, mel bands and (ncols: n values, may be NULL) kept columns per sound, 0 for
+ * a skipped one. n and nb may be NULL. */
+int sg_mel_set_info(const sg_mel_set* set, int64_t* n, int32_t* nb, int32_t* ncols);
+/* getMelSpec of sound i of the set, as sg_mel_spec returns it: out (cap doubles; NULL to size)
+ * receives the nb x *nc matrix column-major. For an fp64 set the values are sg_mel_spec's of
+ * the same samples bit for bit. */
+int sg_mel_set_spec(sg_mel_set* set, int64_t i, double* out, int64_t cap, int32_t* nc);
+void sg_mel_set_destroy(sg_mel_set* set);
+/* compareSounds(target = sound pairs[2 k] of `targets`, cand = sound pairs[2 k + 1] of
+ * `cands`) for n_pairs pairs in one launch sequence: out[4 k + m] and summary[k] (may be NULL)
+ * as sg_compare_sounds_batch defines them, reduced on the device; NaN where either sound was
+ * skipped. The two sets may be one and the same; a pair's numbers do not depend on the other
+ * pairs or on the other sounds of the sets, and equal sg_compare_sounds_batch's for the same
+ * target spectrum and candidate samples bit for bit. SG_E_ARG, before any launch and with out
+ * untouched: a NULL set, sets of different contexts or of different geometry (window, step and
+ * FFT points, mel bands, maxFreq, throwaway), an index outside its set. More than 2^31 - 1
+ * column jobs in one call: SG_E_UNSUPPORTED. n_pairs == 0 returns SG_OK and launches nothing. */
+int sg_compare_sounds_pairs(sg_ctx* ctx, const sg_mel_set* targets, const sg_mel_set* cands, const int32_t* pairs,
+                            int64_t n_pairs, int32_t methods, int32_t penalizeLengthDif, double* out,
+                            double* summary);
 /* compareSounds' 'dtw' method (R/matchPars.R:372-376): dtw::dtw(x, y,
  * distance.only = TRUE)$normalizedDistance with the dtw package defaults
  * (|x_i - y_j|, symmetric2, / (n + m)). Host only (ABI 2). */
@@ -1066,6 +1095,9 @@ int sg_debug_sweep_kernel_ms(double* out);
  * only: sg_anl_acf_peaks from the store), cepstrum, BaNa, path, harmonics, summary. A stage runs
  * from its stamp to the next stage's: it carries the host's preparation of the next launch. */
 int sg_debug_analyze_sweep_kernel_ms(double* out);
+/* The device milliseconds of sg_mel_pair and sg_mel_pair_reduce in the last profiled
+ * sg_compare_sounds_pairs (2 doubles). */
+int sg_debug_mel_pair_kernel_ms(double* out);
 
 #ifdef __cplusplus
 }

@@ -856,6 +856,76 @@ int sg_compare_sounds_batch(sg_ctx* ctx, const double* target_spec, int32_t nb, 
   });
 }
 
+int sg_mel_set_create(sg_ctx* ctx, const void* d_wave, int32_t is_f64, const int64_t* offsets, const int64_t* lengths,
+                      int64_t n, const sg_mel_params* p, sg_mel_set** out) {
+  return guarded(ctx, [&]() {
+    if (!ctx || !p || !out || n < 0 || (n > 0 && (!offsets || !lengths || !d_wave)))
+      throw sg::SgError(SG_E_ARG, "sg_mel_set_create: bad arguments");
+    *out = nullptr;
+    HIPCHK(hipSetDevice(ctx->device));
+    std::unique_ptr<sg_mel_set> h(new sg_mel_set);
+    h->set.reset(new sg::MelSet(ctx, *p, d_wave, is_f64 != 0, offsets, lengths, n));
+    *out = h.release();
+    return SG_OK;
+  });
+}
+
+int sg_mel_set_info(const sg_mel_set* set, int64_t* n, int32_t* nb, int32_t* ncols) {
+  if (!set) return SG_E_ARG;
+  const sg::MelSet& S = *set->set;
+  if (n) *n = S.n;
+  if (nb) *nb = S.g.nb;
+  if (ncols && S.n > 0) std::memcpy(ncols, S.ncols.data(), (size_t)S.n * sizeof(int32_t));
+  return SG_OK;
+}
+
+int sg_mel_set_spec(sg_mel_set* set, int64_t i, double* out, int64_t cap, int32_t* nc) {
+  if (!set) return SG_E_ARG;
+  sg_ctx* ctx = set->set->ctx;
+  return guarded(ctx, [&]() {
+    const sg::MelSet& S = *set->set;
+    if (!nc || i < 0 || i >= S.n) throw sg::SgError(SG_E_ARG, "sg_mel_set_spec: bad arguments");
+    *nc = S.ncols[(size_t)i];
+    if (!out) return SG_OK;
+    if ((int64_t)*nc * S.g.nb > cap) throw sg::SgError(SG_E_CAPACITY, "sg_mel_set_spec: output capacity too small");
+    HIPCHK(hipSetDevice(ctx->device));
+    std::vector<double> spec;
+    int nk = 0;
+    S.spec(i, spec, &nk);
+    std::memcpy(out, spec.data(), spec.size() * sizeof(double));
+    return SG_OK;
+  });
+}
+
+void sg_mel_set_destroy(sg_mel_set* set) {
+  if (!set) return;
+  (void)hipSetDevice(set->set->ctx->device);
+  delete set;
+}
+
+int sg_compare_sounds_pairs(sg_ctx* ctx, const sg_mel_set* targets, const sg_mel_set* cands, const int32_t* pairs,
+                            int64_t n_pairs, int32_t methods, int32_t penalizeLengthDif, double* out,
+                            double* summary) {
+  return guarded(ctx, [&]() {
+    if (!ctx || !targets || !cands || n_pairs < 0 || (n_pairs > 0 && (!pairs || !out)) || (methods & ~15) ||
+        methods == 0)
+      throw sg::SgError(SG_E_ARG, "sg_compare_sounds_pairs: bad arguments");
+    const sg::MelSet &T = *targets->set, &Cs = *cands->set;
+    if (T.ctx != ctx || Cs.ctx != ctx)
+      throw sg::SgError(SG_E_ARG, "sg_compare_sounds_pairs: the sets belong to another context");
+    if (!T.same_geometry(Cs))
+      throw sg::SgError(SG_E_ARG, "sg_compare_sounds_pairs: the sets were computed under different geometries");
+    for (int64_t k = 0; k < n_pairs; ++k)
+      if (pairs[2 * k] < 0 || pairs[2 * k] >= T.n || pairs[2 * k + 1] < 0 || pairs[2 * k + 1] >= Cs.n)
+        throw sg::SgError(SG_E_ARG, "sg_compare_sounds_pairs: pair " + std::to_string(k) + " is out of range");
+    if (n_pairs == 0) return SG_OK;
+    HIPCHK(hipSetDevice(ctx->device));
+    sg::compare_sounds_pairs_device(T, Cs, pairs, n_pairs, methods, penalizeLengthDif != 0, out, summary, ctx->stream,
+                                    ctx->profiling);
+    return SG_OK;
+  });
+}
+
 int sg_dtw_symmetric2(const double* x, int64_t n, const double* y, int64_t m, double* out) {
   if (!x || !y || !out || n < 1 || m < 1) return SG_E_ARG;
   std::vector<double> prev((size_t)m), cur((size_t)m);

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <memory>
 #include <vector>
 
 #include "soundgen_hip.h"
@@ -32,4 +33,41 @@ void compare_sounds_device(const MelGeom& g, const double* tspec, int ncT, const
                            const int64_t* lengths, int64_t n, int methods, int penalize, double* out, double* summary,
                            hipStream_t s);
 
+// The mel spectra of a batch of sounds kept in HBM (sg_mel_set_*): what the frame and
+// kept-column kernels leave behind -- the raw band spectra, the kept-frame lists, nkept, min
+// and max per sound and the sound table -- with the geometry they were computed under. The
+// waveform itself is not kept. Sound c of d_x (float or double) is at offsets[c], lengths[c]
+// samples; lengths[c] <= 0: skipped (no frame, NaN in every comparison).
+struct MelRun;
+struct MelSet {
+  MelSet(sg_ctx* ctx, const sg_mel_params& p, const void* d_x, bool f64, const int64_t* offsets,
+         const int64_t* lengths, int64_t n);
+  ~MelSet();
+  MelSet(const MelSet&) = delete;
+  MelSet& operator=(const MelSet&) = delete;
+  // getMelSpec of sound i: nb x nk column-major, as mel_spec_device
+  void spec(int64_t i, std::vector<double>& out, int* nk) const;
+  // the sets were computed under one geometry (winpts, steppts, nfft, nb, maxFreq, throwaway)
+  bool same_geometry(const MelSet& o) const;
+
+  sg_ctx* ctx;
+  MelGeom g;
+  double maxFreq, throwaway;
+  int64_t n;
+  std::vector<int32_t> ncols;  // kept columns per sound (0 for a skipped one)
+  MelRun* r;
+};
+// compareSounds(target = sound pairs[2 p] of T, cand = sound pairs[2 p + 1] of C) for n_pairs
+// pairs in one launch sequence (sg_mel_pair, sg_mel_pair_reduce): out[4 p + m], summary[p]
+// (may be null). The indices are the caller's to check. More than 2^31 - 1 column jobs:
+// SG_E_UNSUPPORTED. profile: the device time of the two kernels is kept for
+// sg_debug_mel_pair_kernel_ms.
+void compare_sounds_pairs_device(const MelSet& T, const MelSet& C, const int32_t* pairs, int64_t n_pairs, int methods,
+                                 int penalize, double* out, double* summary, hipStream_t s, bool profile);
+
 }  // namespace sg
+
+// the C ABI's handle of a MelSet
+struct sg_mel_set {
+  std::unique_ptr<sg::MelSet> set;
+};

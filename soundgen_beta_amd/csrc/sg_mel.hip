@@ -17,6 +17,12 @@
 //                   cosine, pixel and the dtw package's symmetric2 distance
 //                   (anti-diagonal wavefront in LDS)
 //   sg_mel_out      the normalised kept columns of one spectrum (getMelSpec's value)
+// and, over spectra kept in HBM (sg::MelSet: what the first two kernels leave behind):
+//   sg_mel_pair     one wavefront per (pair, output column) of a list of (target,
+//                   candidate) pairs of two sets: both columns log01-normalised on the
+//                   fly, then the column code sg_mel_compare runs (mel_column_sims)
+//   sg_mel_pair_reduce  compareSounds' reduction of each pair's columns in index order
+//                   and the summary over the methods: 4 + 1 doubles per pair
 // Everything is fp64: R computes in doubles, and the log01 spectra of weak
 // bins amplify an fp32 FFT's absolute error past the 1e-6 parity bar.
 // HBM-light: each candidate sample is read ~2x (50 % overlap), the work is the
@@ -25,6 +31,8 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -151,44 +159,15 @@ __device__ __forceinline__ double log01(double v, double lo, double den) { retur
 // column j shows column j + off of the short matrix, NA outside [0, mcols)
 __device__ __forceinline__ int pad_off(int ncol, int mcols) { return (ncol + mcols + 2) / 2 - 1 - ncol; }
 
-// One wavefront per (candidate, output column): methods cor, cosine, pixel, dtw
-__global__ __launch_bounds__(64) void sg_mel_compare(const int32_t* __restrict__ job_cand,
-                                                     const int32_t* __restrict__ job_col,
-                                                     const double* __restrict__ tspec, int ncT, int nb,
-                                                     const double* __restrict__ spec, const int32_t* __restrict__ kept,
-                                                     const MelCand* __restrict__ cands,
-                                                     const int32_t* __restrict__ nkept, const double* __restrict__ mn,
-                                                     const double* __restrict__ mx, int do_dtw,
-                                                     double* __restrict__ sims) {
-  extern __shared__ double sh[];
-  double* t = sh;
-  double* d = sh + nb;
-  double* D0 = sh + 2 * nb;
+// cor, cosine, pixel and the dtw package's symmetric2 similarity of one pair of columns in
+// LDS, by one wavefront: t and d hold the nb values of the two columns, lane l having written
+// (and read back here) entries l, l + 64, ...; st and sd are the lane's partial sums of them;
+// D0 is 3 nb doubles of scratch. Lane 0 writes out[0..3]. sg_mel_compare and sg_mel_pair both
+// run this code, so a column pair has one value whichever kernel scores it.
+__device__ __forceinline__ void mel_column_sims(const double* t, const double* d, double* D0, int nb, double st,
+                                                double sd, int do_dtw, double* __restrict__ out) {
   double* D1 = D0 + nb;
   double* D2 = D1 + nb;
-  const int c = job_cand[blockIdx.x], j = job_col[blockIdx.x];
-  const int nk = nkept[c];
-  const int ncol = nk > ncT ? nk : ncT;
-  if (j >= ncol) return;
-  double* out = sims + (int64_t)blockIdx.x * 4;
-  int tj = j, cj = j;
-  if (ncT < ncol) tj = j + pad_off(ncol, ncT);
-  if (nk < ncol) cj = j + pad_off(ncol, nk);
-  const double lo = mn[c], den = log(mx[c] - lo + 1.0);
-  if (tj < 0 || tj >= ncT || cj < 0 || cj >= nk || !(den > 0)) {
-    if (threadIdx.x < 4) out[threadIdx.x] = NAN;
-    return;
-  }
-  const double* tc = tspec + (int64_t)tj * nb;
-  const double* sc = spec + (int64_t)kept[cands[c].f0 + cj] * nb;
-  double st = 0, sd = 0;
-  for (int b = threadIdx.x; b < nb; b += 64) {
-    const double tv = tc[b], dv = log01(sc[b], lo, den);
-    t[b] = tv;
-    d[b] = dv;
-    st += tv;
-    sd += dv;
-  }
   st = wsum(st);
   sd = wsum(sd);
   const double mt = st / nb, md = sd / nb;
@@ -246,6 +225,148 @@ __global__ __launch_bounds__(64) void sg_mel_compare(const int32_t* __restrict__
     out[1] = td / sqrt(tt * dd);
     out[2] = 1.0 - ad / nb;
     out[3] = dtw;
+  }
+}
+
+// One wavefront per (candidate, output column): methods cor, cosine, pixel, dtw
+__global__ __launch_bounds__(64) void sg_mel_compare(const int32_t* __restrict__ job_cand,
+                                                     const int32_t* __restrict__ job_col,
+                                                     const double* __restrict__ tspec, int ncT, int nb,
+                                                     const double* __restrict__ spec, const int32_t* __restrict__ kept,
+                                                     const MelCand* __restrict__ cands,
+                                                     const int32_t* __restrict__ nkept, const double* __restrict__ mn,
+                                                     const double* __restrict__ mx, int do_dtw,
+                                                     double* __restrict__ sims) {
+  extern __shared__ double sh[];
+  double* t = sh;
+  double* d = sh + nb;
+  const int c = job_cand[blockIdx.x], j = job_col[blockIdx.x];
+  const int nk = nkept[c];
+  const int ncol = nk > ncT ? nk : ncT;
+  if (j >= ncol) return;
+  double* out = sims + (int64_t)blockIdx.x * 4;
+  int tj = j, cj = j;
+  if (ncT < ncol) tj = j + pad_off(ncol, ncT);
+  if (nk < ncol) cj = j + pad_off(ncol, nk);
+  const double lo = mn[c], den = log(mx[c] - lo + 1.0);
+  if (tj < 0 || tj >= ncT || cj < 0 || cj >= nk || !(den > 0)) {
+    if (threadIdx.x < 4) out[threadIdx.x] = NAN;
+    return;
+  }
+  const double* tc = tspec + (int64_t)tj * nb;
+  const double* sc = spec + (int64_t)kept[cands[c].f0 + cj] * nb;
+  double st = 0, sd = 0;
+  for (int b = threadIdx.x; b < nb; b += 64) {
+    const double tv = tc[b], dv = log01(sc[b], lo, den);
+    t[b] = tv;
+    d[b] = dv;
+    st += tv;
+    sd += dv;
+  }
+  mel_column_sims(t, d, sh + 2 * nb, nb, st, sd, do_dtw, out);
+}
+
+// One job of sg_mel_pair: jobs [job0[p], job0[p + 1]) are the output columns of pair p
+// (a bound from the frame counts before dropping; the columns past the pair's own count leave at once)
+__device__ __forceinline__ int64_t mel_pair_of_job(const int64_t* __restrict__ job0, int64_t n_pairs, int64_t job) {
+  int64_t lo = 0, hi = n_pairs;  // job0[lo] <= job < job0[hi]
+  while (hi - lo > 1) {
+    const int64_t mid = lo + (hi - lo) / 2;
+    if (job0[mid] <= job) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// One wavefront per (pair, output column): column j of compareSounds(target = sound pairs[2 p]
+// of the set T, cand = sound pairs[2 p + 1] of the set C), both read from the sets' raw band
+// spectra and log01-normalised here with the sound's own min and max; the shorter side gets
+// matchColumns' central NA padding. sims[4 job + m], m = cor, cosine, pixel, dtw.
+__global__ __launch_bounds__(64) void sg_mel_pair(
+    const int32_t* __restrict__ pairs, const int64_t* __restrict__ job0, int64_t n_pairs, int nb,
+    const double* __restrict__ specT, const int32_t* __restrict__ keptT, const MelCand* __restrict__ sndT,
+    const int32_t* __restrict__ nkeptT, const double* __restrict__ mnT, const double* __restrict__ mxT,
+    const double* __restrict__ specC, const int32_t* __restrict__ keptC, const MelCand* __restrict__ sndC,
+    const int32_t* __restrict__ nkeptC, const double* __restrict__ mnC, const double* __restrict__ mxC, int do_dtw,
+    double* __restrict__ sims) {
+  extern __shared__ double sh[];
+  double* t = sh;
+  double* d = sh + nb;
+  const int64_t p = mel_pair_of_job(job0, n_pairs, (int64_t)blockIdx.x);
+  const int j = (int)((int64_t)blockIdx.x - job0[p]);
+  const int ti = pairs[2 * p], ci = pairs[2 * p + 1];
+  const int ncT = nkeptT[ti], nk = nkeptC[ci];
+  const int ncol = nk > ncT ? nk : ncT;
+  if (j >= ncol) return;
+  double* out = sims + (int64_t)blockIdx.x * 4;
+  int tj = j, cj = j;
+  if (ncT < ncol) tj = j + pad_off(ncol, ncT);
+  if (nk < ncol) cj = j + pad_off(ncol, nk);
+  const double lo = mnC[ci], den = log(mxC[ci] - lo + 1.0);
+  if (tj < 0 || tj >= ncT || cj < 0 || cj >= nk || !(den > 0)) {
+    if (threadIdx.x < 4) out[threadIdx.x] = NAN;
+    return;
+  }
+  const double loT = mnT[ti], denT = log(mxT[ti] - loT + 1.0);
+  const double* tc = specT + (int64_t)keptT[sndT[ti].f0 + tj] * nb;
+  const double* sc = specC + (int64_t)keptC[sndC[ci].f0 + cj] * nb;
+  double st = 0, sd = 0;
+  for (int b = threadIdx.x; b < nb; b += 64) {
+    const double tv = log01(tc[b], loT, denT), dv = log01(sc[b], lo, den);
+    t[b] = tv;
+    d[b] = dv;
+    st += tv;
+    sd += dv;
+  }
+  mel_column_sims(t, d, sh + 2 * nb, nb, st, sd, do_dtw, out);
+}
+
+// compareSounds' reduction (R/matchPars.R:378-416) of each pair's columns: thread (pair, m)
+// adds the pair's values of method m in column order with the NAs dropped and divides by the
+// column count (penalize) or by the number added; then the pair's first thread takes the mean
+// of the computed methods that are not NA. The operations and their order are those of the host
+// loop at the end of compare_sounds_device. out[4 p + m], summary[p].
+__global__ __launch_bounds__(256) void sg_mel_pair_reduce(
+    const int32_t* __restrict__ pairs, const int64_t* __restrict__ job0, int64_t n_pairs,
+    const MelCand* __restrict__ sndT, const int32_t* __restrict__ nkeptT, const MelCand* __restrict__ sndC,
+    const int32_t* __restrict__ nkeptC, const double* __restrict__ sims, int methods, int penalize,
+    double* __restrict__ out, double* __restrict__ summary) {
+  __shared__ double so[256];
+  const int64_t p = (int64_t)blockIdx.x * 64 + threadIdx.x / 4;
+  const int m = threadIdx.x & 3;
+  double o = NAN;
+  if (p < n_pairs) {
+    const int ti = pairs[2 * p], ci = pairs[2 * p + 1];
+    if (sndT[ti].nf > 0 && sndC[ci].nf > 0 && (methods & (1 << m))) {
+      const int ncT = nkeptT[ti], nk = nkeptC[ci];
+      const int ncol = nk > ncT ? nk : ncT;
+      const double* v = sims + job0[p] * 4 + m;
+      double sm = 0;
+      int cnt = 0;
+      for (int j = 0; j < ncol; ++j) {
+        const double x = v[(int64_t)j * 4];
+        if (!isnan(x)) {
+          sm += x;
+          ++cnt;
+        }
+      }
+      o = penalize ? sm / ncol : (cnt ? sm / cnt : NAN);
+    }
+    out[4 * p + m] = o;
+  }
+  so[threadIdx.x] = o;
+  __syncthreads();
+  if (p < n_pairs && m == 0) {
+    double sm = 0;
+    int cnt = 0;
+    for (int k = 0; k < 4; ++k) {
+      const double x = so[threadIdx.x + k];
+      if (!isnan(x)) {
+        sm += x;
+        ++cnt;
+      }
+    }
+    summary[p] = cnt ? sm / cnt : NAN;
   }
 }
 
@@ -348,8 +469,7 @@ int mel_frames(const MelGeom& g, int64_t len) {
   return 1;
 }
 
-namespace {
-
+// what sg_mel_frames and sg_mel_cand leave on the device for a batch of sounds
 struct MelRun {
   int F = 0;
   DevBuf db;
@@ -360,6 +480,8 @@ struct MelRun {
   MelCand* cands = nullptr;
   std::vector<MelCand> hc;
 };
+
+namespace {
 
 template <typename T>
 void mel_run(MelRun& r, const MelGeom& g, const T* d_x, const int64_t* offsets, const int64_t* lengths, int64_t n,
@@ -499,4 +621,95 @@ void compare_sounds_device(const MelGeom& g, const double* tspec, int ncT, const
   }
 }
 
+MelSet::MelSet(sg_ctx* c, const sg_mel_params& p, const void* d_x, bool f64, const int64_t* offsets,
+               const int64_t* lengths, int64_t n_)
+    : ctx(c), g(mel_geom(p)), maxFreq(std::isnan(p.maxFreq) ? p.samplingRate / 2 : p.maxFreq),
+      throwaway(p.throwaway), n(n_), ncols((size_t)n_, 0), r(nullptr) {
+  if (n == 0) return;
+  std::unique_ptr<MelRun> run(new MelRun);
+  hipStream_t s = ctx->stream;
+  if (f64) mel_run<double>(*run, g, static_cast<const double*>(d_x), offsets, lengths, n, s);
+  else mel_run<float>(*run, g, static_cast<const float*>(d_x), offsets, lengths, n, s);
+  HIPCHK(hipMemcpyAsync(ncols.data(), run->nkept, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  // the caller's waveform is free to go once this returns, and so are the staged uploads
+  HIPCHK(hipStreamSynchronize(s));
+  run->db.host.clear();
+  r = run.release();
+}
+
+MelSet::~MelSet() { delete r; }
+
+void MelSet::spec(int64_t i, std::vector<double>& out, int* nk_out) const {
+  const int nk = ncols[(size_t)i];
+  *nk_out = nk;
+  out.assign((size_t)nk * g.nb, 0.0);
+  if (nk == 0) return;
+  hipStream_t s = ctx->stream;
+  DevBuf db;
+  const int64_t tot = (int64_t)nk * g.nb;
+  double* d_out = db.get<double>((size_t)tot);
+  hipLaunchKernelGGL(sg_mel_out, dim3((unsigned)std::min<int64_t>((tot + 255) / 256, 4096)), dim3(256), 0, s, r->spec,
+                     r->kept + r->hc[(size_t)i].f0, nk, g.nb, r->mn + i, r->mx + i, d_out);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out.data(), d_out, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+}
+
+bool MelSet::same_geometry(const MelSet& o) const {
+  return g.winpts == o.g.winpts && g.steppts == o.g.steppts && g.nfft == o.g.nfft && g.nb == o.g.nb &&
+         maxFreq == o.maxFreq && throwaway == o.throwaway;
+}
+
+namespace {
+double g_mel_pair_ms[2];  // of the last profiled compare_sounds_pairs_device (sg_debug_mel_pair_kernel_ms)
+}
+
+void compare_sounds_pairs_device(const MelSet& T, const MelSet& C, const int32_t* pairs, int64_t n_pairs, int methods,
+                                 int penalize, double* out, double* summary, hipStream_t s, bool profile) {
+  // column jobs: a pair may need up to max(frames of its two sounds) output columns, known
+  // here without asking the device for the kept counts
+  if (n_pairs > INT32_MAX) throw SgError(SG_E_UNSUPPORTED, "compareSounds: more than 2^31 - 1 pairs");
+  std::vector<int64_t> job0((size_t)n_pairs + 1);
+  int64_t J = 0;
+  for (int64_t p = 0; p < n_pairs; ++p) {
+    job0[(size_t)p] = J;
+    const int nfT = T.r->hc[(size_t)pairs[2 * p]].nf, nfC = C.r->hc[(size_t)pairs[2 * p + 1]].nf;
+    if (nfT > 0 && nfC > 0) J += std::max(nfT, nfC);
+    if (J > INT32_MAX) throw SgError(SG_E_UNSUPPORTED, "compareSounds: more than 2^31 - 1 column jobs");
+  }
+  job0[(size_t)n_pairs] = J;
+  DevBuf db;
+  const int32_t* d_pairs = upload(db, std::vector<int32_t>(pairs, pairs + 2 * n_pairs), s);
+  const int64_t* d_job0 = upload(db, job0, s);
+  double* d_sims = db.get<double>((size_t)std::max<int64_t>(J, 1) * 4);
+  double* d_out = db.get<double>((size_t)n_pairs * 4);
+  double* d_sum = db.get<double>((size_t)n_pairs);
+  const int nb = T.g.nb;
+  StageClock clk(s, profile ? g_mel_pair_ms : nullptr, 2);
+  clk.stamp();
+  if (J > 0) {
+    hipLaunchKernelGGL(sg_mel_pair, dim3((unsigned)J), dim3(64), (size_t)5 * nb * sizeof(double), s, d_pairs, d_job0,
+                       n_pairs, nb, T.r->spec, T.r->kept, T.r->cands, T.r->nkept, T.r->mn, T.r->mx, C.r->spec,
+                       C.r->kept, C.r->cands, C.r->nkept, C.r->mn, C.r->mx, (methods & 8) ? 1 : 0, d_sims);
+    HIPCHK(hipGetLastError());
+  }
+  clk.stamp();
+  hipLaunchKernelGGL(sg_mel_pair_reduce, dim3((unsigned)((n_pairs + 63) / 64)), dim3(256), 0, s, d_pairs, d_job0,
+                     n_pairs, T.r->cands, T.r->nkept, C.r->cands, C.r->nkept, d_sims, methods, penalize ? 1 : 0, d_out,
+                     d_sum);
+  HIPCHK(hipGetLastError());
+  clk.stamp();
+  HIPCHK(hipMemcpyAsync(out, d_out, (size_t)n_pairs * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (summary) HIPCHK(hipMemcpyAsync(summary, d_sum, (size_t)n_pairs * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  clk.finish();
+}
+
 }  // namespace sg
+
+extern "C" int sg_debug_mel_pair_kernel_ms(double* out) {
+  if (!out) return SG_E_ARG;
+  out[0] = sg::g_mel_pair_ms[0];
+  out[1] = sg::g_mel_pair_ms[1];
+  return SG_OK;
+}

@@ -37,6 +37,13 @@ after morph().
   most 8 of its rows are returned; a target without a syllable raises 'Invalid
   initial pars' and a single syllable leaves pauseLen at its default (see
   match_pars_init_numpy).
+- Many targets at once: MelSet keeps the mel spectra of a batch of sounds in HBM,
+  compare_sounds_pairs() scores any list of (target, candidate) pairs of two such sets in one
+  launch sequence (sg_mel_pair, sg_mel_pair_reduce; five numbers per pair come back), bit-equal
+  to compare_sounds_batch(); compare_sounds_matrix() is the pairwise matrix of a folder of
+  sounds from one such call, and match_pars_batch() climbs every target of a list with one
+  synthesis batch and one pair call per generation. match_pars() and match_pars_batch() step
+  the same per-target state machine (_Climb), each target on its own R stream.
 Parity: restated from the sources; no R here, so the similarity values are
 checked against hand-derived cases (tests/test_matchpars.py).
 """
@@ -618,65 +625,324 @@ def match_pars(target, samplingRate, pars, init=None, method=("cor", "cosine", "
     (formants then holds only the found ones), and `pars` may be empty when maxIter <= 1
     ("match pars based on acoustic analysis alone"). The default False takes the starting
     point from defaults[pars] and `init` alone, as before."""
-    from . import batch
     from .rrng import RRng
     rng = rng if rng is not None else RRng(1)
-    D = _Draws(rng)
+    targetSpec = get_mel_spec_gpu(target, samplingRate, windowLength, overlap, step, throwaway, maxFreq, device)
+    _check_pars(pars, maxIter, analyzeTarget)
+    upd = match_pars_init(target, samplingRate, windowLength, overlap, step, device) if analyzeTarget else None
+    parDefault = _start_pars(pars, upd, init, samplingRate)
     kw = dict(windowLength=windowLength, overlap=overlap, step=step, penalizeLengthDif=penalizeLengthDif,
               throwaway=throwaway, maxFreq=maxFreq)
-    targetSpec = get_mel_spec_gpu(target, samplingRate, windowLength, overlap, step, throwaway, maxFreq, device)
+
+    def score(plist):
+        """One generation on the GPU: the candidates synthesized as one batch into
+        HBM, their spectra and similarities in one launch sequence; -inf for a
+        call the planner refused."""
+        from . import batch
+        calls = [{"kind": "soundgen", "args": _soundgen_args(p), "rng": rng} for p in plist]
+        data, offs, lens = batch.synthesize_packed(calls, device)
+        _, summ = compare_sounds_batch(targetSpec, data, offs, lens, samplingRate, method, device=device, **kw)
+        return _sims(summ, lens), lens
+
+    st = _Climb(pars, parDefault, rng, probMutation, stepVariance, maxIter, minExpectedDelta, pop, verbose)
+    return _climb_single(st, score)
+
+
+def _check_pars(pars, maxIter, analyzeTarget):
+    if analyzeTarget and maxIter > 1 and len(pars) < 1:
+        raise ValueError("No parameters for optimization are specified! Either list them in 'pars' or set "
+                         "'maxIter = 0'")
+
+
+def _start_pars(pars, updates, init, samplingRate):
+    """matchPars' starting point: defaults[pars], then the updates from the target's analysis
+    (match_pars_init(); None without analyzeTarget), then `init`."""
     defaults = MATCHPARS_DEFAULTS
     parDefault = {p: copy.deepcopy(defaults[p]) for p in pars}
-    if analyzeTarget:
-        if maxIter > 1 and len(pars) < 1:
-            raise ValueError("No parameters for optimization are specified! Either list them in 'pars' or set "
-                             "'maxIter = 0'")
-        for k, v in match_pars_init(target, samplingRate, windowLength, overlap, step, device).items():
-            if k == "formants" and isinstance(parDefault.get("formants"), dict):
-                parDefault["formants"].update(v)  # parDefault$formants[[f]] = ...: the others stay
-            else:
-                parDefault[k] = v
+    for k, v in (updates or {}).items():
+        if k == "formants" and isinstance(parDefault.get("formants"), dict):
+            parDefault["formants"].update(v)  # parDefault$formants[[f]] = ...: the others stay
+        else:
+            parDefault[k] = v
     for k, v in (init or {}).items():
         if k not in defaults:
             raise ValueError("init parameter not recognized: %s" % k)
         parDefault[k] = copy.deepcopy(v)
     parDefault["samplingRate"] = samplingRate
+    return parDefault
 
-    def call(p):
-        return {"kind": "soundgen", "args": _soundgen_args(p), "rng": rng}
 
-    def score(calls):
-        """One generation on the GPU: the candidates synthesized as one batch into
-        HBM, their spectra and similarities in one launch sequence; -inf for a
-        call the planner refused."""
-        data, offs, lens = batch.synthesize_packed(calls, device)
-        _, summ = compare_sounds_batch(targetSpec, data, offs, lens, samplingRate, method, device=device, **kw)
-        return [(-math.inf if n < 0 or math.isnan(v) else float(v)) for v, n in zip(summ, lens)], lens
+def _sims(summ, lens):
+    return [(-math.inf if n < 0 or math.isnan(v) else float(v)) for v, n in zip(summ, lens)]
 
-    sims, lens = score([call(parDefault)])
-    if lens[0] < 0:
-        raise ValueError("Invalid initial pars")
-    sim0 = sims[0]
-    history = [{"pars": parDefault, "sim": sim0}]
-    parLoop, i, evaluated = parDefault, 1, 1
-    while i < maxIter:
-        muts = [wiggle_pars(D, parLoop, list(pars), probMutation, stepVariance) for _ in range(pop)]
-        sims, _ = score([call(m) for m in muts])
+
+class _Climb:
+    """One target's hill climb (R/matchPars.R:176-250), the state machine both match_pars()
+    and match_pars_batch() step: the counter i of non-improving candidates in a row, the
+    minExpectedDelta test, i += pop - 1 for a generation without a winner, the history and
+    the number of candidates evaluated. The driver scores; the climb draws (from its own
+    stream, pop mutants per generation in order) and decides."""
+
+    def __init__(self, pars, parDefault, rng, probMutation, stepVariance, maxIter, minExpectedDelta, pop,
+                 verbose=False):
+        self.pars, self.start_pars, self.D = list(pars), parDefault, _Draws(rng)
+        self.probMutation, self.stepVariance = probMutation, stepVariance
+        self.maxIter, self.minExpectedDelta, self.pop, self.verbose = maxIter, minExpectedDelta, pop, verbose
+        self.history, self.muts = None, None
+
+    def start(self, sim0):
+        """The starting point's similarity: the first entry of the history."""
+        self.history = [{"pars": self.start_pars, "sim": sim0}]
+        self.parLoop, self.i, self.evaluated = self.start_pars, 1, 1
+
+    @property
+    def active(self):
+        return self.history is not None and self.i < self.maxIter
+
+    def mutants(self):
+        """The next generation: pop draws of wigglePars from the current best."""
+        self.muts = [wiggle_pars(self.D, self.parLoop, self.pars, self.probMutation, self.stepVariance)
+                     for _ in range(self.pop)]
+        return self.muts
+
+    def update(self, sims):
+        """The generation's similarities, in the mutants' order."""
         best, best_m = -math.inf, None
-        for m, s in zip(muts, sims):
-            evaluated += 1
+        for m, s in zip(self.muts, sims):
+            self.evaluated += 1
             if s > best:
                 best, best_m = s, m
-        if best - history[-1]["sim"] > minExpectedDelta:
-            history.append({"pars": best_m, "sim": best})
-            parLoop = best_m
-            i = 1
-            if verbose:
+        if best - self.history[-1]["sim"] > self.minExpectedDelta:
+            self.history.append({"pars": best_m, "sim": best})
+            self.parLoop = best_m
+            self.i = 1
+            if self.verbose:
                 print("Best similarity: ", round(best, 4))
         else:
-            i += pop - 1
-        i += 1
-    return {"history": history, "pars": history[-1]["pars"], "evaluated": evaluated}
+            self.i += self.pop - 1
+        self.i += 1
+
+    def result(self):
+        return {"history": self.history, "pars": self.history[-1]["pars"], "evaluated": self.evaluated}
+
+
+def _climb_single(st, score):
+    """match_pars()' loop over one _Climb. score(list of pars) -> (sims, lens): a generation's
+    similarities (-inf for a refused call) and lengths (< 0 for a refused call)."""
+    sims, lens = score([st.start_pars])
+    if lens[0] < 0:
+        raise ValueError("Invalid initial pars")
+    st.start(sims[0])
+    while st.active:
+        sims, _ = score(st.mutants())
+        st.update(sims)
+    return st.result()
+
+
+def _climb_batch(states, score):
+    """match_pars_batch()'s loop over one _Climb per target (None: a target already given up).
+    score(list of (target index, pars)) -> (sims, lens) as in _climb_single, for the candidates
+    of every active target in one go, a target's mutants in their order. A target leaves when
+    its own counter reaches maxIter; the loop ends when none is left. Returns one result per
+    target, None where the initial call was refused."""
+    live = [k for k, st in enumerate(states) if st is not None]
+    if live:
+        sims, lens = score([(k, states[k].start_pars) for k in live])
+        for j, k in enumerate(live):
+            if lens[j] >= 0:
+                states[k].start(sims[j])
+    while True:
+        active = [k for k in live if states[k].active]
+        if not active:
+            break
+        items = [(k, m) for k in active for m in states[k].mutants()]
+        sims, _ = score(items)
+        at = 0
+        for k in active:
+            states[k].update(sims[at:at + states[k].pop])
+            at += states[k].pop
+    return [st.result() if st is not None and st.history is not None else None for st in states]
+
+
+# ------------------------------------- resident mel spectra, pairs, many targets at once
+class MelSet:
+    """The mel spectra of a batch of sounds kept in HBM (sg_mel_set_*): getMelSpec() of every
+    sound of `data` (a float32 or float64 CUDA tensor, sound i at offsets[i], lengths[i]
+    samples, <= 0 for a sound to skip -- the layout of batch.synthesize_packed), computed once
+    and scored as often as needed by compare_sounds_pairs(). The waveform is not kept. A
+    context manager; .n sounds, .nb mel bands, .ncols kept columns per sound, .spec(i) the
+    spectrum of sound i as get_mel_spec_gpu() returns it."""
+
+    def __init__(self, data, offsets, lengths, samplingRate, windowLength=40, overlap=50, step=None, throwaway=-120,
+                 maxFreq=None, device=0):
+        import torch
+        if not (isinstance(data, torch.Tensor) and data.is_cuda and data.dtype in (torch.float32, torch.float64)):
+            raise TypeError("MelSet: data must be a float32 or float64 CUDA tensor")
+        if data.device.index != device:
+            raise ValueError("MelSet: data is on cuda:%s, not on cuda:%d" % (data.device.index, device))
+        L = native.lib()
+        self.ctx = native.default_context(device)
+        self.device = device
+        offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64))
+        lens = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64))
+        if len(offs) != len(lens):
+            raise ValueError("MelSet: offsets and lengths differ in length")
+        live = lens > 0
+        if live.any() and (offs[live].min() < 0 or (offs[live] + lens[live]).max() > data.numel()):
+            raise ValueError("MelSet: a sound lies outside data")
+        P = _mel_params(samplingRate, windowLength, overlap, step, throwaway, maxFreq)
+        i64p = C.POINTER(C.c_int64)
+        self.ptr = C.c_void_p()
+        torch.cuda.synchronize(device)  # data may come from another stream
+        native.check(L.sg_mel_set_create(self.ctx.ptr, C.c_void_p(data.contiguous().data_ptr()),
+                                         int(data.dtype == torch.float64), offs.ctypes.data_as(i64p),
+                                         lens.ctypes.data_as(i64p), len(offs), C.byref(P), C.byref(self.ptr)),
+                     self.ctx.ptr)
+        n, nb = C.c_int64(), C.c_int32()
+        self.ncols = np.zeros(len(offs), dtype=np.int32)
+        native.check(L.sg_mel_set_info(self.ptr, C.byref(n), C.byref(nb),
+                                       self.ncols.ctypes.data_as(C.POINTER(C.c_int32))))
+        self.n, self.nb = int(n.value), int(nb.value)
+
+    def spec(self, i):
+        L = native.lib()
+        nc = C.c_int32()
+        native.check(L.sg_mel_set_spec(self.ptr, int(i), None, 0, C.byref(nc)), self.ctx.ptr)
+        out = np.zeros(self.nb * nc.value)
+        native.check(L.sg_mel_set_spec(self.ptr, int(i), out.ctypes.data_as(C.POINTER(C.c_double)), len(out),
+                                       C.byref(nc)), self.ctx.ptr)
+        return out.reshape(nc.value, self.nb).T
+
+    def close(self):
+        if self.ptr:
+            native.lib().sg_mel_set_destroy(self.ptr)
+            self.ptr = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def compare_sounds_pairs(targets, cands, pairs, method=_METHOD_ORDER, penalizeLengthDif=True, out=None):
+    """compareSounds(target = sound t of the MelSet `targets`, cand = sound c of the MelSet
+    `cands`) for every (t, c) of `pairs` in one launch sequence (sg_compare_sounds_pairs: one
+    wavefront per pair and column, then the reduction on the device; five numbers per pair
+    come back). The sets may be one and the same. Returns what compare_sounds_batch() returns,
+    over the pairs: ({method: array}, summary). A pair's numbers do not depend on the other
+    pairs or sounds in the call. `out`: an optional (n_pairs, 4) float64 array the per-method
+    values are written into (left untouched by a refused call)."""
+    L = native.lib()
+    mask = 0
+    for m in method:
+        mask |= _METHOD_BITS[m]
+    pr = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+    n = len(pr)
+    if out is None:
+        out = np.full((n, 4), np.nan)
+    if out.shape != (n, 4) or out.dtype != np.float64 or not out.flags.c_contiguous:
+        raise ValueError("compare_sounds_pairs: out must be a C-contiguous (n_pairs, 4) float64 array")
+    summ = np.full(n, np.nan)
+    dp = C.POINTER(C.c_double)
+    native.check(L.sg_compare_sounds_pairs(targets.ctx.ptr, targets.ptr, cands.ptr,
+                                           pr.ctypes.data_as(C.POINTER(C.c_int32)), n, mask,
+                                           int(bool(penalizeLengthDif)), out.ctypes.data_as(dp),
+                                           summ.ctypes.data_as(dp)), targets.ctx.ptr)
+    return {m: out[:, k] for k, m in enumerate(_METHOD_ORDER) if m in method}, summ
+
+
+def compare_sounds_matrix(sounds, method=_METHOD_ORDER, penalizeLengthDif=True):
+    """The pairwise similarity of n sounds: `sounds` is a MelSet, or the arguments of one as a
+    tuple (data, offsets, lengths, samplingRate, ...). Every sound's spectrum is computed once
+    and the n (n + 1) / 2 pairs with i <= j are scored in one compare_sounds_pairs() call and
+    mirrored: every operation of the comparison is commutative in (target, candidate), which
+    tests/test_compare_pairs.py checks on explicit pairs. Returns (the n x n summary matrix,
+    {method: n x n matrix}); entry [i, j] is compareSounds(target = i, cand = j)."""
+    own = not isinstance(sounds, MelSet)
+    S = MelSet(*sounds) if own else sounds
+    try:
+        n = S.n
+        iu, ju = np.triu_indices(n)
+        per, summ = compare_sounds_pairs(S, S, np.stack([iu, ju], axis=1), method, penalizeLengthDif)
+    finally:
+        if own:
+            S.close()
+
+    def square(v):
+        M = np.full((n, n), np.nan)
+        M[iu, ju] = v
+        M[ju, iu] = v
+        return M
+    return square(summ), {m: square(v) for m, v in per.items()}
+
+
+def match_pars_batch(targets, samplingRate, pars, init=None, method=_METHOD_ORDER, probMutation=.25,
+                     stepVariance=.1, maxIter=50, minExpectedDelta=.001, windowLength=40, overlap=50, step=None,
+                     penalizeLengthDif=True, throwaway=-120, maxFreq=None, rngs=None, pop=1, device=0,
+                     analyzeTarget=False):
+    """match_pars() for many targets of one sampling rate at once: `targets` is a list of host
+    arrays, `init` one dict for all or a list of one per target, `rngs` one rrng.RRng per target
+    (default: a fresh RRng(1) each, match_pars()' default). Returns a list with match_pars()'
+    dict per target, None for a target whose starting point the planner refuses (or, with
+    analyzeTarget, whose analysis match_pars_init_batch() gives up on); the others are unaffected.
+
+    The targets go to HBM once as float64 and their mel spectra are computed once (a MelSet).
+    Per generation every active target draws its pop mutants from its own stream, all of those
+    calls are synthesized by ONE batch.synthesize_packed (each call carries its target's rng, a
+    target's mutants in their order), one MelSet is built over the candidates and one
+    compare_sounds_pairs() scores each against its own target. A target leaves when its own
+    counter reaches maxIter. Result k equals match_pars(targets[k], ..., rng=rngs[k]): the
+    streams are separate, a call's samples do not depend on the batch around it, and a pair's
+    similarity does not depend on the other pairs. With analyzeTarget the analysis runs on the
+    float32-rounded samples (match_pars_init_batch())."""
+    import torch
+    from . import batch
+    from .rrng import RRng
+    nT = len(targets)
+    _check_pars(pars, maxIter, analyzeTarget)
+    inits = list(init) if isinstance(init, (list, tuple)) else [init] * nT
+    if len(inits) != nT:
+        raise ValueError("match_pars_batch: init must be one dict or one per target")
+    rngs = list(rngs) if rngs is not None else [RRng(1) for _ in range(nT)]
+    if len(rngs) != nT:
+        raise ValueError("match_pars_batch: rngs must hold one generator per target")
+    if nT == 0:
+        return []
+    host = [np.ascontiguousarray(np.asarray(t, dtype=np.float64).ravel()) for t in targets]
+    lens = np.array([len(t) for t in host], dtype=np.int64)
+    offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64)
+    data = torch.from_numpy(np.concatenate(host)).to("cuda:%d" % device)
+    mel = dict(windowLength=windowLength, overlap=overlap, step=step, throwaway=throwaway, maxFreq=maxFreq)
+    updates = [None] * nT
+    if analyzeTarget:
+        updates = match_pars_init_batch(data.to(torch.float32), offs, lens, samplingRate, windowLength, overlap, step,
+                                        device)
+    states = []
+    for k in range(nT):
+        if analyzeTarget and updates[k] is None:
+            states.append(None)
+            continue
+        states.append(_Climb(pars, _start_pars(pars, updates[k], inits[k], samplingRate), rngs[k], probMutation,
+                             stepVariance, maxIter, minExpectedDelta, pop))
+    with MelSet(data, offs, lens, samplingRate, device=device, **mel) as tset:
+        del data
+
+        def score(items):
+            calls = [{"kind": "soundgen", "args": _soundgen_args(p), "rng": rngs[k]} for k, p in items]
+            cand, coffs, clens = batch.synthesize_packed(calls, device)
+            with MelSet(cand, coffs, clens, samplingRate, device=device, **mel) as cset:
+                _, summ = compare_sounds_pairs(tset, cset, [(k, j) for j, (k, _) in enumerate(items)], method,
+                                               penalizeLengthDif)
+            return _sims(summ, clens), clens
+
+        return _climb_batch(states, score)
 
 
 def _soundgen_args(p):

@@ -99,6 +99,16 @@ def lib():
                               C.POINTER(C.c_int32)]
     L.sg_compare_sounds_batch.argtypes = [vp, dp, C.c_int32, C.c_int32, vp, i64p, i64p, i64,
                                           C.POINTER(_abi.sg_mel_params), C.c_int32, dp, dp]
+    if hasattr(L, "sg_mel_set_create"):  # resident mel spectra and pair scoring: additive to ABI 5
+        i32p = C.POINTER(C.c_int32)
+        L.sg_mel_set_create.argtypes = [vp, vp, C.c_int32, i64p, i64p, i64, C.POINTER(_abi.sg_mel_params),
+                                        C.POINTER(vp)]
+        L.sg_mel_set_info.argtypes = [vp, i64p, i32p, i32p]
+        L.sg_mel_set_spec.argtypes = [vp, i64, dp, i64, i32p]
+        L.sg_mel_set_destroy.argtypes = [vp]
+        L.sg_mel_set_destroy.restype = None
+        L.sg_compare_sounds_pairs.argtypes = [vp, vp, vp, i32p, i64, C.c_int32, C.c_int32, dp, dp]
+        L.sg_debug_mel_pair_kernel_ms.argtypes = [dp]
     if hasattr(L, "sg_ssm_size"):  # ssm(): an additive extension of ABI 5 (a host-only build lacks it)
         i32p = C.POINTER(C.c_int32)
         L.sg_ssm_size.argtypes = [i64, C.POINTER(_abi.sg_ssm_params), i32p, i32p, i32p, i32p]
