@@ -357,7 +357,11 @@ int sg_mel_spec(sg_ctx* ctx, const double* wave, int64_t len, const sg_mel_param
  * the dtw package's symmetric2 normalizedDistance), summary[c] the mean of the
  * computed non-NA methods (compareSounds(summary = TRUE); may be NULL). One
  * launch sequence for the whole batch (R/matchPars.R:313-416, called per
- * candidate at :168, :202). */
+ * candidate at :168, :202): the pairs (target, c) go through the kernels of
+ * sg_compare_sounds_pairs with the target's columns read as they stand, are
+ * reduced on the device, and five numbers per candidate come back. A target of
+ * nc_target = 0 columns is a sound without a kept frame, not a skipped one:
+ * 0 per method under penalizeLengthDif, NaN without it. */
 int sg_compare_sounds_batch(sg_ctx* ctx, const double* target_spec, int32_t nb, int32_t nc_target,
                             const float* d_wave, const int64_t* offsets, const int64_t* lengths, int64_t n,
                             const sg_mel_params* p, int32_t methods, double* out, double* summary);
@@ -383,7 +387,8 @@ void sg_mel_set_destroy(sg_mel_set* set);
  * as sg_compare_sounds_batch defines them, reduced on the device; NaN where either sound was
  * skipped. The two sets may be one and the same; a pair's numbers do not depend on the other
  * pairs or on the other sounds of the sets, and equal sg_compare_sounds_batch's for the same
- * target spectrum and candidate samples bit for bit. SG_E_ARG, before any launch and with out
+ * target spectrum and candidate samples bit for bit (one set of kernels serves both entries;
+ * they differ in where the target's columns come from). SG_E_ARG, before any launch and with out
  * untouched: a NULL set, sets of different contexts or of different geometry (window, step and
  * FFT points, mel bands, maxFreq, throwaway), an index outside its set. More than 2^31 - 1
  * column jobs in one call: SG_E_UNSUPPORTED. n_pairs == 0 returns SG_OK and launches nothing. */

@@ -27,8 +27,10 @@ int mel_frames(const MelGeom& g, int64_t len);
 // getMelSpec of one waveform already on the device: nb x nk column-major into out
 void mel_spec_device(const MelGeom& g, const double* d_x, int64_t len, std::vector<double>& out, int* nk,
                      hipStream_t s);
-// compareSounds(targetSpec = tspec (host, nb x ncT), cand = each candidate of
-// d_x): out[4 c + m] per method (cor, cosine, pixel, dtw), summary[c]
+// compareSounds(targetSpec = tspec (host, nb x ncT, getMelSpec's value: already normalised),
+// cand = each candidate of d_x): out[4 c + m] per method (cor, cosine, pixel, dtw), summary[c]
+// (may be null). The pairs (target, c) through the kernels of compare_sounds_pairs_device, the
+// target read as it stands; ncT = 0 is a target without a column, not an absent one.
 void compare_sounds_device(const MelGeom& g, const double* tspec, int ncT, const float* d_x, const int64_t* offsets,
                            const int64_t* lengths, int64_t n, int methods, int penalize, double* out, double* summary,
                            hipStream_t s);
@@ -58,7 +60,8 @@ struct MelSet {
   MelRun* r;
 };
 // compareSounds(target = sound pairs[2 p] of T, cand = sound pairs[2 p + 1] of C) for n_pairs
-// pairs in one launch sequence (sg_mel_pair, sg_mel_pair_reduce): out[4 p + m], summary[p]
+// pairs in one launch sequence (sg_mel_pair, sg_mel_pair_reduce; the only comparison path, which
+// compare_sounds_device shares): out[4 p + m], summary[p]
 // (may be null). The indices are the caller's to check. More than 2^31 - 1 column jobs:
 // SG_E_UNSUPPORTED. profile: the device time of the two kernels is kept for
 // sg_debug_mel_pair_kernel_ms.

@@ -2,8 +2,8 @@
 // similarity metric of matchPars(): getMelSpec()
 // (R/matchPars.R:510-560 = tuneR 1.3.2 melfcc(spec_out = TRUE)$aspectrum:
 // tuneR/R/melfcc.R, powspec.R, audspec.R, fft2melmx.R, hz2mel.R, mel2hz.R;
-// signal 0.7-6 specgram.R, hamming.R) of a batch of candidates and the
-// per-column cor / cosine / pixel / dtw against one target spectrum.
+// signal 0.7-6 specgram.R, hamming.R) of a batch of sounds and the per-column
+// cor / cosine / pixel / dtw of (target, candidate) pairs of them.
 //
 //   sg_mel_frames   one workgroup per frame: pre-emphasis 0.97 on the fly,
 //                   hamming(winpts), zero-padded real nfft-point FFT (complex
@@ -12,15 +12,16 @@
 //                   and the column's mean (soundgen's frame stripping)
 //   sg_mel_cand     one workgroup per candidate: kept columns (colMeans >
 //                   2^(throwaway/10)) compacted in order, their min and max (log01)
-//   sg_mel_compare  one wavefront per (candidate, output column): matchColumns'
-//                   central NA padding of the shorter spectrum, then cor,
-//                   cosine, pixel and the dtw package's symmetric2 distance
-//                   (anti-diagonal wavefront in LDS)
 //   sg_mel_out      the normalised kept columns of one spectrum (getMelSpec's value)
-// and, over spectra kept in HBM (sg::MelSet: what the first two kernels leave behind):
+// and, over what the first two kernels leave in HBM (a MelRun; sg::MelSet keeps one), the one
+// comparison path of sg_compare_sounds_pairs and sg_compare_sounds_batch (whose target is a
+// run made from getMelSpec's value: one sound, already normalised):
 //   sg_mel_pair     one wavefront per (pair, output column) of a list of (target,
-//                   candidate) pairs of two sets: both columns log01-normalised on the
-//                   fly, then the column code sg_mel_compare runs (mel_column_sims)
+//                   candidate) pairs of two runs: matchColumns' central NA padding of
+//                   the shorter spectrum, both columns log01-normalised on the fly (a
+//                   ready-made target's is read as it stands), then cor, cosine, pixel
+//                   and the dtw package's symmetric2 distance (anti-diagonal wavefront
+//                   in LDS; mel_column_sims)
 //   sg_mel_pair_reduce  compareSounds' reduction of each pair's columns in index order
 //                   and the summary over the methods: 4 + 1 doubles per pair
 // Everything is fp64: R computes in doubles, and the log01 spectra of weak
@@ -32,6 +33,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <memory>
 #include <string>
 #include <vector>
@@ -162,8 +164,8 @@ __device__ __forceinline__ int pad_off(int ncol, int mcols) { return (ncol + mco
 // cor, cosine, pixel and the dtw package's symmetric2 similarity of one pair of columns in
 // LDS, by one wavefront: t and d hold the nb values of the two columns, lane l having written
 // (and read back here) entries l, l + 64, ...; st and sd are the lane's partial sums of them;
-// D0 is 3 nb doubles of scratch. Lane 0 writes out[0..3]. sg_mel_compare and sg_mel_pair both
-// run this code, so a column pair has one value whichever kernel scores it.
+// D0 is 3 nb doubles of scratch. Lane 0 writes out[0..3]. sg_mel_pair is its only caller, so
+// a column pair has one value whichever entry scores it.
 __device__ __forceinline__ void mel_column_sims(const double* t, const double* d, double* D0, int nb, double st,
                                                 double sd, int do_dtw, double* __restrict__ out) {
   double* D1 = D0 + nb;
@@ -228,44 +230,6 @@ __device__ __forceinline__ void mel_column_sims(const double* t, const double* d
   }
 }
 
-// One wavefront per (candidate, output column): methods cor, cosine, pixel, dtw
-__global__ __launch_bounds__(64) void sg_mel_compare(const int32_t* __restrict__ job_cand,
-                                                     const int32_t* __restrict__ job_col,
-                                                     const double* __restrict__ tspec, int ncT, int nb,
-                                                     const double* __restrict__ spec, const int32_t* __restrict__ kept,
-                                                     const MelCand* __restrict__ cands,
-                                                     const int32_t* __restrict__ nkept, const double* __restrict__ mn,
-                                                     const double* __restrict__ mx, int do_dtw,
-                                                     double* __restrict__ sims) {
-  extern __shared__ double sh[];
-  double* t = sh;
-  double* d = sh + nb;
-  const int c = job_cand[blockIdx.x], j = job_col[blockIdx.x];
-  const int nk = nkept[c];
-  const int ncol = nk > ncT ? nk : ncT;
-  if (j >= ncol) return;
-  double* out = sims + (int64_t)blockIdx.x * 4;
-  int tj = j, cj = j;
-  if (ncT < ncol) tj = j + pad_off(ncol, ncT);
-  if (nk < ncol) cj = j + pad_off(ncol, nk);
-  const double lo = mn[c], den = log(mx[c] - lo + 1.0);
-  if (tj < 0 || tj >= ncT || cj < 0 || cj >= nk || !(den > 0)) {
-    if (threadIdx.x < 4) out[threadIdx.x] = NAN;
-    return;
-  }
-  const double* tc = tspec + (int64_t)tj * nb;
-  const double* sc = spec + (int64_t)kept[cands[c].f0 + cj] * nb;
-  double st = 0, sd = 0;
-  for (int b = threadIdx.x; b < nb; b += 64) {
-    const double tv = tc[b], dv = log01(sc[b], lo, den);
-    t[b] = tv;
-    d[b] = dv;
-    st += tv;
-    sd += dv;
-  }
-  mel_column_sims(t, d, sh + 2 * nb, nb, st, sd, do_dtw, out);
-}
-
 // One job of sg_mel_pair: jobs [job0[p], job0[p + 1]) are the output columns of pair p
 // (a bound from the frame counts before dropping; the columns past the pair's own count leave at once)
 __device__ __forceinline__ int64_t mel_pair_of_job(const int64_t* __restrict__ job0, int64_t n_pairs, int64_t job) {
@@ -279,13 +243,14 @@ __device__ __forceinline__ int64_t mel_pair_of_job(const int64_t* __restrict__ j
 }
 
 // One wavefront per (pair, output column): column j of compareSounds(target = sound pairs[2 p]
-// of the set T, cand = sound pairs[2 p + 1] of the set C), both read from the sets' raw band
-// spectra and log01-normalised here with the sound's own min and max; the shorter side gets
-// matchColumns' central NA padding. sims[4 job + m], m = cor, cosine, pixel, dtw.
+// of the run T, cand = sound pairs[2 p + 1] of the run C), both read from the runs' raw band
+// spectra and log01-normalised here with the sound's own min and max (readyT: specT holds
+// normalised values already, read as they stand; mnT and mxT are not read); the shorter side
+// gets matchColumns' central NA padding. sims[4 job + m], m = cor, cosine, pixel, dtw.
 __global__ __launch_bounds__(64) void sg_mel_pair(
     const int32_t* __restrict__ pairs, const int64_t* __restrict__ job0, int64_t n_pairs, int nb,
     const double* __restrict__ specT, const int32_t* __restrict__ keptT, const MelCand* __restrict__ sndT,
-    const int32_t* __restrict__ nkeptT, const double* __restrict__ mnT, const double* __restrict__ mxT,
+    const int32_t* __restrict__ nkeptT, const double* __restrict__ mnT, const double* __restrict__ mxT, int readyT,
     const double* __restrict__ specC, const int32_t* __restrict__ keptC, const MelCand* __restrict__ sndC,
     const int32_t* __restrict__ nkeptC, const double* __restrict__ mnC, const double* __restrict__ mxC, int do_dtw,
     double* __restrict__ sims) {
@@ -307,12 +272,16 @@ __global__ __launch_bounds__(64) void sg_mel_pair(
     if (threadIdx.x < 4) out[threadIdx.x] = NAN;
     return;
   }
-  const double loT = mnT[ti], denT = log(mxT[ti] - loT + 1.0);
+  double loT = 0, denT = 1;
+  if (!readyT) {
+    loT = mnT[ti];
+    denT = log(mxT[ti] - loT + 1.0);
+  }
   const double* tc = specT + (int64_t)keptT[sndT[ti].f0 + tj] * nb;
   const double* sc = specC + (int64_t)keptC[sndC[ci].f0 + cj] * nb;
   double st = 0, sd = 0;
   for (int b = threadIdx.x; b < nb; b += 64) {
-    const double tv = log01(tc[b], loT, denT), dv = log01(sc[b], lo, den);
+    const double tv = readyT ? tc[b] : log01(tc[b], loT, denT), dv = log01(sc[b], lo, den);
     t[b] = tv;
     d[b] = dv;
     st += tv;
@@ -324,11 +293,12 @@ __global__ __launch_bounds__(64) void sg_mel_pair(
 // compareSounds' reduction (R/matchPars.R:378-416) of each pair's columns: thread (pair, m)
 // adds the pair's values of method m in column order with the NAs dropped and divides by the
 // column count (penalize) or by the number added; then the pair's first thread takes the mean
-// of the computed methods that are not NA. The operations and their order are those of the host
-// loop at the end of compare_sounds_device. out[4 p + m], summary[p].
+// of the computed methods that are not NA. A sound without a frame is absent (a failed slot):
+// NaN throughout; a ready-made target (readyT) is present even with no column, and then every
+// column value is NA: 0 / ncol (penalize) or NaN, as R gives. out[4 p + m], summary[p].
 __global__ __launch_bounds__(256) void sg_mel_pair_reduce(
     const int32_t* __restrict__ pairs, const int64_t* __restrict__ job0, int64_t n_pairs,
-    const MelCand* __restrict__ sndT, const int32_t* __restrict__ nkeptT, const MelCand* __restrict__ sndC,
+    const MelCand* __restrict__ sndT, const int32_t* __restrict__ nkeptT, int readyT, const MelCand* __restrict__ sndC,
     const int32_t* __restrict__ nkeptC, const double* __restrict__ sims, int methods, int penalize,
     double* __restrict__ out, double* __restrict__ summary) {
   __shared__ double so[256];
@@ -337,7 +307,7 @@ __global__ __launch_bounds__(256) void sg_mel_pair_reduce(
   double o = NAN;
   if (p < n_pairs) {
     const int ti = pairs[2 * p], ci = pairs[2 * p + 1];
-    if (sndT[ti].nf > 0 && sndC[ci].nf > 0 && (methods & (1 << m))) {
+    if ((readyT || sndT[ti].nf > 0) && sndC[ci].nf > 0 && (methods & (1 << m))) {
       const int ncT = nkeptT[ti], nk = nkeptC[ci];
       const int ncol = nk > ncT ? nk : ncT;
       const double* v = sims + job0[p] * 4 + m;
@@ -469,8 +439,11 @@ int mel_frames(const MelGeom& g, int64_t len) {
   return 1;
 }
 
-// what sg_mel_frames and sg_mel_cand leave on the device for a batch of sounds
+// what sg_mel_frames and sg_mel_cand leave on the device for a batch of sounds (mel_run), or
+// one sound given as getMelSpec's value (mel_run_ready): ready, spec holds the normalised
+// columns as they stand, every one kept, and mn and mx stay unset
 struct MelRun {
+  bool ready = false;
   int F = 0;
   DevBuf db;
   double* spec = nullptr;
@@ -529,6 +502,88 @@ void mel_run(MelRun& r, const MelGeom& g, const T* d_x, const int64_t* offsets, 
   HIPCHK(hipGetLastError());
 }
 
+// One sound given as getMelSpec's value (host, nb x nc, already through log01). nf = nc, so
+// a pair's column-job bound max(nfT, nfC) covers its columns as it does for frames.
+void mel_run_ready(MelRun& r, const double* tspec, int nc, int nb, hipStream_t s) {
+  r.ready = true;
+  r.F = nc;
+  r.hc.assign(1, MelCand{0, nc, 0, 0});
+  // one upload (this runs once per scoring call): the columns, then as int32 the sound table (a
+  // MelCand is four), nkept and the identity kept list
+  std::vector<int32_t> t{0, nc, 0, 0, nc};
+  for (int j = 0; j < nc; ++j) t.push_back(j);
+  const size_t ns = (size_t)nc * nb;
+  std::vector<double> h(ns + (t.size() + 1) / 2);
+  std::copy(tspec, tspec + ns, h.begin());
+  std::memcpy(h.data() + ns, t.data(), t.size() * sizeof(int32_t));
+  r.spec = upload(r.db, h, s);
+  int32_t* d = reinterpret_cast<int32_t*>(r.spec + ns);
+  r.cands = reinterpret_cast<MelCand*>(d);
+  r.nkept = d + 4;
+  r.kept = d + 5;
+}
+
+// getMelSpec's value of sound i of a run, which kept nk columns: nb x nk column-major
+void mel_run_spec(const MelRun& r, int64_t i, int nk, int nb, std::vector<double>& out, hipStream_t s) {
+  out.assign((size_t)nk * nb, 0.0);
+  if (nk == 0) return;
+  DevBuf db;
+  const int64_t tot = (int64_t)nk * nb;
+  double* d_out = db.get<double>((size_t)tot);
+  hipLaunchKernelGGL(sg_mel_out, dim3((unsigned)std::min<int64_t>((tot + 255) / 256, 4096)), dim3(256), 0, s, r.spec,
+                     r.kept + r.hc[(size_t)i].f0, nk, nb, r.mn + i, r.mx + i, d_out);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out.data(), d_out, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+}
+
+double g_mel_pair_ms[2];  // of the last profiled compare_pairs (sg_debug_mel_pair_kernel_ms)
+
+// compareSounds(target = sound pairs[2 p] of T, cand = sound pairs[2 p + 1] of C), two runs of
+// nb bands: sg_mel_pair, sg_mel_pair_reduce, then out[4 p + m] and summary[p] (may be null)
+void compare_pairs(const MelRun& T, const MelRun& C, int nb, const int32_t* pairs, int64_t n_pairs, int methods,
+                   int penalize, double* out, double* summary, hipStream_t s, bool profile) {
+  // column jobs: a pair may need up to max(frames of its two sounds) output columns, known
+  // here without asking the device for the kept counts
+  if (n_pairs > INT32_MAX) throw SgError(SG_E_UNSUPPORTED, "compareSounds: more than 2^31 - 1 pairs");
+  // job0 and, behind it in the same upload, the pairs (two int32 per entry)
+  std::vector<int64_t> job0((size_t)n_pairs + 1 + (size_t)n_pairs);
+  int64_t J = 0;
+  for (int64_t p = 0; p < n_pairs; ++p) {
+    job0[(size_t)p] = J;
+    const int nfT = T.hc[(size_t)pairs[2 * p]].nf, nfC = C.hc[(size_t)pairs[2 * p + 1]].nf;
+    if ((T.ready || nfT > 0) && nfC > 0) J += std::max(nfT, nfC);
+    if (J > INT32_MAX) throw SgError(SG_E_UNSUPPORTED, "compareSounds: more than 2^31 - 1 column jobs");
+  }
+  job0[(size_t)n_pairs] = J;
+  std::memcpy(job0.data() + n_pairs + 1, pairs, (size_t)n_pairs * 2 * sizeof(int32_t));
+  DevBuf db;
+  const int64_t* d_job0 = upload(db, job0, s);
+  const int32_t* d_pairs = reinterpret_cast<const int32_t*>(d_job0 + n_pairs + 1);
+  // one allocation: the column values, then the pairs' 4 + 1 results
+  double* d_sims = db.get<double>((size_t)J * 4 + (size_t)n_pairs * 5);
+  double* d_out = d_sims + J * 4;
+  double* d_sum = d_out + n_pairs * 4;
+  StageClock clk(s, profile ? g_mel_pair_ms : nullptr, 2);
+  clk.stamp();
+  if (J > 0) {
+    hipLaunchKernelGGL(sg_mel_pair, dim3((unsigned)J), dim3(64), (size_t)5 * nb * sizeof(double), s, d_pairs, d_job0,
+                       n_pairs, nb, T.spec, T.kept, T.cands, T.nkept, T.mn, T.mx, T.ready ? 1 : 0, C.spec, C.kept,
+                       C.cands, C.nkept, C.mn, C.mx, (methods & 8) ? 1 : 0, d_sims);
+    HIPCHK(hipGetLastError());
+  }
+  clk.stamp();
+  hipLaunchKernelGGL(sg_mel_pair_reduce, dim3((unsigned)((n_pairs + 63) / 64)), dim3(256), 0, s, d_pairs, d_job0,
+                     n_pairs, T.cands, T.nkept, T.ready ? 1 : 0, C.cands, C.nkept, d_sims, methods, penalize ? 1 : 0,
+                     d_out, d_sum);
+  HIPCHK(hipGetLastError());
+  clk.stamp();
+  HIPCHK(hipMemcpyAsync(out, d_out, (size_t)n_pairs * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (summary) HIPCHK(hipMemcpyAsync(summary, d_sum, (size_t)n_pairs * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  clk.finish();
+}
+
 }  // namespace
 
 void mel_spec_device(const MelGeom& g, const double* d_x, int64_t len, std::vector<double>& out, int* nk_out,
@@ -540,85 +595,18 @@ void mel_spec_device(const MelGeom& g, const double* d_x, int64_t len, std::vect
   HIPCHK(hipMemcpyAsync(&nk, r.nkept, sizeof nk, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   *nk_out = nk;
-  out.assign((size_t)nk * g.nb, 0.0);
-  if (nk == 0) return;
-  double* d_out = r.db.get<double>((size_t)nk * g.nb);
-  const int64_t tot = (int64_t)nk * g.nb;
-  hipLaunchKernelGGL(sg_mel_out, dim3((unsigned)std::min<int64_t>((tot + 255) / 256, 4096)), dim3(256), 0, s, r.spec,
-                     r.kept, nk, g.nb, r.mn, r.mx, d_out);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out.data(), d_out, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
+  mel_run_spec(r, 0, nk, g.nb, out, s);
 }
 
 void compare_sounds_device(const MelGeom& g, const double* tspec, int ncT, const float* d_x, const int64_t* offsets,
                            const int64_t* lengths, int64_t n, int methods, int penalize, double* out, double* summary,
                            hipStream_t s) {
-  MelRun r;
-  mel_run<float>(r, g, d_x, offsets, lengths, n, s);
-  // column jobs: candidate c may need up to max(ncT, its frames) output columns
-  std::vector<int32_t> jc, jj;
-  for (int64_t c = 0; c < n; ++c) {
-    r.hc[c].job0 = (int32_t)jc.size();
-    const int ub = lengths[c] > 0 ? std::max(ncT, r.hc[c].nf) : 0;
-    for (int j = 0; j < ub; ++j) {
-      jc.push_back((int32_t)c);
-      jj.push_back(j);
-    }
-  }
-  const int32_t* d_jc = upload(r.db, jc, s);
-  const int32_t* d_jj = upload(r.db, jj, s);
-  const double* d_t = upload(r.db, std::vector<double>(tspec, tspec + (size_t)ncT * g.nb), s);
-  const int64_t J = (int64_t)jc.size();
-  double* d_sims = r.db.get<double>((size_t)std::max<int64_t>(J, 1) * 4);
-  if (J > 0) {
-    hipLaunchKernelGGL(sg_mel_compare, dim3((unsigned)J), dim3(64), (size_t)5 * g.nb * sizeof(double), s, d_jc, d_jj,
-                       d_t, ncT, g.nb, r.spec, r.kept, r.cands, r.nkept, r.mn, r.mx, (methods & 8) ? 1 : 0, d_sims);
-    HIPCHK(hipGetLastError());
-  }
-  std::vector<double> sims((size_t)J * 4);
-  std::vector<int32_t> nk(n);
-  if (J) HIPCHK(hipMemcpyAsync(sims.data(), d_sims, sims.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(nk.data(), r.nkept, nk.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  // compareSounds' reduction (R/matchPars.R:378-416): per method the column
-  // values' sum with NAs dropped over the column count (penalizeLengthDif), else
-  // their mean; the summary is the mean over the methods that are not NA
-  for (int64_t c = 0; c < n; ++c) {
-    double* o = out + 4 * c;
-    if (lengths[c] <= 0) {
-      for (int m = 0; m < 4; ++m) o[m] = NAN;
-      if (summary) summary[c] = NAN;
-      continue;
-    }
-    const int ncol = std::max(ncT, (int)nk[c]);
-    for (int m = 0; m < 4; ++m) {
-      if (!(methods & (1 << m))) {
-        o[m] = NAN;
-        continue;
-      }
-      double sm = 0;
-      int cnt = 0;
-      for (int j = 0; j < ncol; ++j) {
-        const double v = sims[((size_t)r.hc[c].job0 + j) * 4 + m];
-        if (!std::isnan(v)) {
-          sm += v;
-          ++cnt;
-        }
-      }
-      o[m] = penalize ? sm / ncol : (cnt ? sm / cnt : NAN);
-    }
-    if (summary) {
-      double sm = 0;
-      int cnt = 0;
-      for (int m = 0; m < 4; ++m)
-        if ((methods & (1 << m)) && !std::isnan(o[m])) {
-          sm += o[m];
-          ++cnt;
-        }
-      summary[c] = cnt ? sm / cnt : NAN;
-    }
-  }
+  MelRun T, C;
+  mel_run<float>(C, g, d_x, offsets, lengths, n, s);
+  mel_run_ready(T, tspec, ncT, g.nb, s);
+  std::vector<int32_t> pairs((size_t)2 * n, 0);  // (0, c)
+  for (int64_t c = 0; c < n; ++c) pairs[(size_t)2 * c + 1] = (int32_t)c;
+  compare_pairs(T, C, g.nb, pairs.data(), n, methods, penalize, out, summary, s, false);
 }
 
 MelSet::MelSet(sg_ctx* c, const sg_mel_params& p, const void* d_x, bool f64, const int64_t* offsets,
@@ -640,19 +628,8 @@ MelSet::MelSet(sg_ctx* c, const sg_mel_params& p, const void* d_x, bool f64, con
 MelSet::~MelSet() { delete r; }
 
 void MelSet::spec(int64_t i, std::vector<double>& out, int* nk_out) const {
-  const int nk = ncols[(size_t)i];
-  *nk_out = nk;
-  out.assign((size_t)nk * g.nb, 0.0);
-  if (nk == 0) return;
-  hipStream_t s = ctx->stream;
-  DevBuf db;
-  const int64_t tot = (int64_t)nk * g.nb;
-  double* d_out = db.get<double>((size_t)tot);
-  hipLaunchKernelGGL(sg_mel_out, dim3((unsigned)std::min<int64_t>((tot + 255) / 256, 4096)), dim3(256), 0, s, r->spec,
-                     r->kept + r->hc[(size_t)i].f0, nk, g.nb, r->mn + i, r->mx + i, d_out);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(out.data(), d_out, (size_t)tot * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
+  *nk_out = ncols[(size_t)i];
+  mel_run_spec(*r, i, *nk_out, g.nb, out, ctx->stream);
 }
 
 bool MelSet::same_geometry(const MelSet& o) const {
@@ -660,49 +637,9 @@ bool MelSet::same_geometry(const MelSet& o) const {
          maxFreq == o.maxFreq && throwaway == o.throwaway;
 }
 
-namespace {
-double g_mel_pair_ms[2];  // of the last profiled compare_sounds_pairs_device (sg_debug_mel_pair_kernel_ms)
-}
-
 void compare_sounds_pairs_device(const MelSet& T, const MelSet& C, const int32_t* pairs, int64_t n_pairs, int methods,
                                  int penalize, double* out, double* summary, hipStream_t s, bool profile) {
-  // column jobs: a pair may need up to max(frames of its two sounds) output columns, known
-  // here without asking the device for the kept counts
-  if (n_pairs > INT32_MAX) throw SgError(SG_E_UNSUPPORTED, "compareSounds: more than 2^31 - 1 pairs");
-  std::vector<int64_t> job0((size_t)n_pairs + 1);
-  int64_t J = 0;
-  for (int64_t p = 0; p < n_pairs; ++p) {
-    job0[(size_t)p] = J;
-    const int nfT = T.r->hc[(size_t)pairs[2 * p]].nf, nfC = C.r->hc[(size_t)pairs[2 * p + 1]].nf;
-    if (nfT > 0 && nfC > 0) J += std::max(nfT, nfC);
-    if (J > INT32_MAX) throw SgError(SG_E_UNSUPPORTED, "compareSounds: more than 2^31 - 1 column jobs");
-  }
-  job0[(size_t)n_pairs] = J;
-  DevBuf db;
-  const int32_t* d_pairs = upload(db, std::vector<int32_t>(pairs, pairs + 2 * n_pairs), s);
-  const int64_t* d_job0 = upload(db, job0, s);
-  double* d_sims = db.get<double>((size_t)std::max<int64_t>(J, 1) * 4);
-  double* d_out = db.get<double>((size_t)n_pairs * 4);
-  double* d_sum = db.get<double>((size_t)n_pairs);
-  const int nb = T.g.nb;
-  StageClock clk(s, profile ? g_mel_pair_ms : nullptr, 2);
-  clk.stamp();
-  if (J > 0) {
-    hipLaunchKernelGGL(sg_mel_pair, dim3((unsigned)J), dim3(64), (size_t)5 * nb * sizeof(double), s, d_pairs, d_job0,
-                       n_pairs, nb, T.r->spec, T.r->kept, T.r->cands, T.r->nkept, T.r->mn, T.r->mx, C.r->spec,
-                       C.r->kept, C.r->cands, C.r->nkept, C.r->mn, C.r->mx, (methods & 8) ? 1 : 0, d_sims);
-    HIPCHK(hipGetLastError());
-  }
-  clk.stamp();
-  hipLaunchKernelGGL(sg_mel_pair_reduce, dim3((unsigned)((n_pairs + 63) / 64)), dim3(256), 0, s, d_pairs, d_job0,
-                     n_pairs, T.r->cands, T.r->nkept, C.r->cands, C.r->nkept, d_sims, methods, penalize ? 1 : 0, d_out,
-                     d_sum);
-  HIPCHK(hipGetLastError());
-  clk.stamp();
-  HIPCHK(hipMemcpyAsync(out, d_out, (size_t)n_pairs * 4 * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (summary) HIPCHK(hipMemcpyAsync(summary, d_sum, (size_t)n_pairs * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  clk.finish();
+  compare_pairs(*T.r, *C.r, T.g.nb, pairs, n_pairs, methods, penalize, out, summary, s, profile);
 }
 
 }  // namespace sg

@@ -14,7 +14,9 @@ after morph().
 - On the GPU (sg_mel.hip, the product path of match_pars): get_mel_spec_gpu and
   compare_sounds_batch run both for a whole generation of candidates in HBM in
   one launch sequence (fp64 FFT frames, mel bands, kept columns, then one
-  wavefront per column for cor / cosine / pixel / dtw). The numpy functions
+  wavefront per column for cor / cosine / pixel / dtw and the reduction on
+  the device: the pair kernels below, with the target spectrum read as it
+  stands; five numbers per candidate come back). The numpy functions
   below (get_mel_spec, compare_sounds) are the host restatement the GPU tests
   compare against.
   dtw: the dtw package's default (symmetric2 steps, Euclidean local distance,
@@ -40,7 +42,7 @@ after morph().
 - Many targets at once: MelSet keeps the mel spectra of a batch of sounds in HBM,
   compare_sounds_pairs() scores any list of (target, candidate) pairs of two such sets in one
   launch sequence (sg_mel_pair, sg_mel_pair_reduce; five numbers per pair come back), bit-equal
-  to compare_sounds_batch(); compare_sounds_matrix() is the pairwise matrix of a folder of
+  to compare_sounds_batch(), which runs the same kernels; compare_sounds_matrix() is the pairwise matrix of a folder of
   sounds from one such call, and match_pars_batch() climbs every target of a list with one
   synthesis batch and one pair call per generation. match_pars() and match_pars_batch() step
   the same per-target state machine (_Climb), each target on its own R stream.

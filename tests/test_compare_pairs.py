@@ -1,8 +1,10 @@
 """Mel spectra resident in HBM (matchpars.MelSet, sg_mel_set_*) and compareSounds() over a list
 of (target, candidate) pairs of them (compare_sounds_pairs, compare_sounds_matrix: sg_mel_pair,
-sg_mel_pair_reduce), against the one-target entry sg_compare_sounds_batch bit for bit and against
-the numpy restatement at its own bars."""
+sg_mel_pair_reduce), against the one-target entry sg_compare_sounds_batch bit for bit, both
+entries against the values recorded before they came to share those kernels, and against the
+numpy restatement at its own bars."""
 import math
+import os
 
 import numpy as np
 import pytest
@@ -159,6 +161,65 @@ def test_pairs_equal_one_target_entry(world, wl, penalize):
         rper, rsumm = MP.compare_sounds_batch(world.spec("c", t, wl), world.cdata, world.coffs, world.clens, SR,
                                               windowLength=wl, penalizeLengthDif=penalize)
         assert all(_same(per[m][k], rper[m][c]) for m in M) and _same(summ[k], rsumm[c]), (t, c)
+
+
+def test_both_entries_reproduce_the_recorded_one_target_values(world):
+    """sg_compare_sounds_batch and sg_compare_sounds_pairs share their kernels, so the bit-for-bit
+    assertions between them above compare one path with itself. This one anchors both to
+    tests/golden/compare_sounds_one_target.npz: what compare_sounds_batch() returned for this
+    world (every windowLength, both penalizeLengthDif, 3 targets x 7 slots, the silent target and
+    the failed slot among them) at the commit before the fold, when the one-target entry had a
+    kernel of its own and reduced on the host (make_golden.py compare_sounds_one_target; two
+    recordings in separate processes gave identical files). Every value, bit for bit."""
+    with np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
+                              "compare_sounds_one_target.npz")) as z:
+        gout, gsumm, raised, wls = z["out"], z["summary"], z["raised"], z["wls"]
+    assert tuple(wls) == WLS and gout.shape == (3, 2, 3, 7, 4) and gsumm.shape == (3, 2, 3, 7)
+    assert not raised.any()  # the entry refused no target then, the nb x 0 one included
+    pairs = [(t, c) for t in range(3) for c in range(7)]
+    for a, wl in enumerate(WLS):
+        tset, cset = world.sets(wl)
+        for b, penalize in enumerate((False, True)):
+            for t in range(3):
+                per, summ = MP.compare_sounds_batch(world.spec("t", t, wl), world.cdata, world.coffs, world.clens, SR,
+                                                    windowLength=wl, penalizeLengthDif=penalize)
+                got = np.stack([per[m] for m in M], axis=1)
+                assert _same(got, gout[a, b, t]), (wl, penalize, t, got, gout[a, b, t])
+                assert _same(summ, gsumm[a, b, t]), (wl, penalize, t, summ, gsumm[a, b, t])
+            per, summ = MP.compare_sounds_pairs(tset, cset, pairs, penalizeLengthDif=penalize)
+            got = np.stack([per[m] for m in M], axis=1).reshape(3, 7, 4)
+            assert _same(got, gout[a, b]), (wl, penalize)
+            assert _same(summ.reshape(3, 7), gsumm[a, b]), (wl, penalize)
+    # what the fixture holds: numbers for every live pair of a voiced target, the silent target's
+    # 0 / ncol = 0 (penalizeLengthDif) or NaN, and NaN for the failed slot
+    live = [c for c in range(7) if c != FAILED]
+    assert np.isfinite(gout[:, :, :2][:, :, :, live]).all() and np.isfinite(gsumm[:, :, :2][:, :, :, live]).all()
+    assert (gout[:, 1, 2][:, live] == 0).all() and (gsumm[:, 1, 2][:, live] == 0).all()
+    assert np.isnan(gout[:, 0, 2]).all() and np.isnan(gsumm[:, 0, 2]).all()
+    assert np.isnan(gout[:, :, :, FAILED]).all() and np.isnan(gsumm[:, :, :, FAILED]).all()
+
+
+def test_mel_spec_of_a_sound_within_one_window(world):
+    """get_mel_spec_gpu() (mel_spec_device) and MelSet.spec() copy a spectrum out through one
+    helper: the two voiced targets at windowLength 13 agree bit for bit, and a sound of exactly
+    one window (208 samples) and a shorter one (150), one frame each, are within 1e-9 of the
+    numpy get_mel_spec through either."""
+    import torch
+    wl = 13
+    tset, _ = world.sets(wl)
+    for i in (0, 1):
+        assert np.array_equal(tset.spec(i), world.spec("t", i, wl)), i
+    winpts = 208  # round(0.013 * 16000)
+    shorts = [world.targets[1][2000:2000 + winpts], world.targets[1][2000:2150]]
+    lens = np.array([len(y) for y in shorts], dtype=np.int64)
+    offs = np.array([0, winpts], dtype=np.int64)
+    with MP.MelSet(torch.from_numpy(np.concatenate(shorts)).to("cuda:0"), offs, lens, SR, windowLength=wl) as S:
+        for i, y in enumerate(shorts):
+            want = MP.get_mel_spec(y, SR, windowLength=wl)
+            got = MP.get_mel_spec_gpu(y, SR, windowLength=wl)
+            assert want.shape == (65, 1) and got.shape == want.shape, (i, got.shape, want.shape)
+            np.testing.assert_allclose(got, want, rtol=0, atol=1e-9)
+            assert np.array_equal(S.spec(i), got), i
 
 
 def test_pair_is_independent_of_the_call(world):
