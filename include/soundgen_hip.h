@@ -248,9 +248,11 @@ int64_t sg_plan_device_bytes(const sg_plan* plan);
 /* Upload descriptors/inputs to HBM (outside any timed region). */
 int sg_plan_upload(sg_ctx* ctx, sg_plan* plan);
 /* After upload: free the plan's host copies of descriptors and inputs (a
- * 65,536-call preset batch holds ~0.7 MB per call on the host). Execution,
- * lengths, offsets, statuses and messages keep working; re-upload does not.
- * The bulk arrays are returned to the OS on a detached host thread, so the
+ * 65,536-call preset batch holds ~0.7 MB per call on the host). Execution needs
+ * nothing of the host plan: sg_execute and sg_execute_plans read the uploaded
+ * device plan alone. Lengths, offsets, statuses, messages and the sg_plan_*
+ * statistics keep working; re-upload does not.
+ * The arrays are returned to the OS on a detached host thread, so the
  * call returns before their pages are unmapped.
  * No reference counterpart (R holds nothing between calls). */
 int sg_plan_release_host(sg_plan* plan);

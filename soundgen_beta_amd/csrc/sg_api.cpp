@@ -28,7 +28,7 @@
 struct sg_plan {
   sg::Batch B;
   sg::DevicePlan D;
-  bool host_released = false;  // sg_plan_release_host: bulk host arrays freed, re-upload impossible
+  bool host_released = false;  // sg_plan_release_host: B keeps its PlanReport only, re-upload impossible
 };
 
 namespace sg {
@@ -610,39 +610,19 @@ int64_t sg_plan_device_bytes(const sg_plan* plan) {
 int sg_plan_release_host(sg_plan* plan) {
   if (!plan) return SG_E_ARG;
   if (!plan->D.uploaded) return SG_E_ARG;
-  sg::Batch& B = plan->B;
-  auto drop = [](auto& v) { std::remove_reference_t<decltype(v)>().swap(v); };
-  // The bulk arrays (~12 GB for a 16,384-call C5 plan) are returned to the OS on a
-  // detached thread: unmapping them took ~1.2 s on the caller, which then plans
-  // or uploads the next chunk meanwhile.
-  struct Bulk {
-    decltype(B.fl) fl;
-    decltype(B.tasks) tasks;
-    decltype(B.segs) segs;
-    decltype(B.eterms) eterms;
-    decltype(B.cknots) cknots;
-    decltype(B.knots) knots;
-    decltype(B.fl_x) fl_x;
-    decltype(B.tasks_x) tasks_x;
-    decltype(B.segs_x) segs_x;
-    decltype(B.eterms_x) eterms_x;
-  };
-  auto* bulk = new Bulk{std::move(B.fl),     std::move(B.tasks),   std::move(B.segs), std::move(B.eterms),
-                        std::move(B.cknots), std::move(B.knots),   std::move(B.fl_x), std::move(B.tasks_x),
-                        std::move(B.segs_x), std::move(B.eterms_x)};
-  B.fl_x = {}; B.tasks_x = {}; B.segs_x = {}; B.eterms_x = {};
+  // Execution reads the device plan alone (sg_exec.h: ExecInfo, the section counts), so
+  // everything of the Batch but its report goes. The bulk arrays (~12 GB for a
+  // 16,384-call C5 plan) are returned to the OS on a detached thread: unmapping them
+  // took ~1.2 s on the caller, which then plans or uploads the next chunk meanwhile.
+  sg::PlanReport report = std::move(static_cast<sg::PlanReport&>(plan->B));
+  auto* old = new sg::Batch(std::move(plan->B));
+  plan->B = sg::Batch{};
+  static_cast<sg::PlanReport&>(plan->B) = std::move(report);
   try {
-    std::thread([bulk]() { delete bulk; }).detach();
+    std::thread([old]() { delete old; }).detach();
   } catch (...) {
-    delete bulk;  // no thread: free here
+    delete old;  // no thread: free here
   }
-  // what sg_execute reads from the host plan stays: slices, ranges and splits,
-  // the table sizes it launches over, the copy list, the envelope area base
-  drop(B.segs); drop(B.epochs); drop(B.knots); drop(B.ampsrc); drop(B.ampcols); drop(B.ampjobs); drop(B.tasks); drop(B.pieces); drop(B.syls);
-  drop(B.syl_tiles); drop(B.fin_tiles); drop(B.copy_tiles); drop(B.ptiles); drop(B.cknots); drop(B.fl);
-  drop(B.fgroups); drop(B.olasegs); drop(B.items); drop(B.mixes_dev); drop(B.eterms); drop(B.ecols); drop(B.envjobs);
-  for (int ph = 0; ph < 2; ++ph) { drop(B.frames[ph]); drop(B.frame_geom[ph]); drop(B.olas[ph]); drop(B.mixes[ph]); }
-  drop(B.ustream); drop(B.ujobs);
   plan->host_released = true;
   return SG_OK;
 }
@@ -663,7 +643,7 @@ int sg_execute(sg_ctx* ctx, sg_plan* plan, float* d_out, void* stream) {
     // NULL is the null (default) stream, as for every HIP API: the kernels are
     // ordered after earlier null-stream work (e.g. torch's default stream)
     hipStream_t s = (hipStream_t)stream;
-    sg::device_execute(plan->B, plan->D, d_out, s, ctx->aux, ctx->profiling ? &ctx->prof_events : nullptr);
+    sg::device_execute(plan->D, d_out, s, ctx->aux, ctx->profiling ? &ctx->prof_events : nullptr);
     return SG_OK;
   });
 }
@@ -677,7 +657,7 @@ int sg_execute_plans(sg_ctx* ctx, sg_plan* const* plans, float* const* d_outs, i
       if (!plans[i] || !plans[i]->D.uploaded) throw sg::SgError(SG_E_ARG, "sg_execute_plans: plan not uploaded");
       for (int j = 0; j < i; ++j)
         if (plans[j] == plans[i]) throw sg::SgError(SG_E_ARG, "sg_execute_plans: a plan listed twice");
-      runs.push_back(sg::PlanRun{&plans[i]->B, &plans[i]->D, d_outs[i]});
+      runs.push_back(sg::PlanRun{&plans[i]->D, d_outs[i]});
     }
     if (runs.empty()) return SG_OK;
     sg::device_execute_many(runs, (hipStream_t)stream, ctx->aux, ctx->profiling ? &ctx->prof_events : nullptr);
@@ -800,7 +780,7 @@ int sg_plan_precision(const sg_plan* plan, int32_t* call_fp64, int64_t* fp64_fra
   if (!plan) return SG_E_ARG;
   const sg::Batch& B = plan->B;
   if (call_fp64) std::memcpy(call_fp64, B.call_fp64.data(), B.call_fp64.size() * sizeof(int32_t));
-  if (fp64_frames) *fp64_frames = (int64_t)B.frames64.size();
+  if (fp64_frames) *fp64_frames = plan->host_released ? plan->D.n.frames64 : (int64_t)B.frames64.size();
   if (fp64_tasks) {
     int64_t n = 0;
     sg::bulk_each(B.tasks_x, B.tasks, [&](int64_t, const SgWTask* p, int64_t k) {
@@ -973,7 +953,7 @@ int sg_execute_to_host(sg_ctx* ctx, sg_plan* plan, double* out_host) {
     float* d_out = nullptr;
     HIPCHK(hipMalloc(&d_out, (size_t)std::max<int64_t>(T, 1) * sizeof(float)));
     std::unique_ptr<void, hipError_t (*)(void*)> hold_out(d_out, hipFree);
-    sg::device_execute(plan->B, plan->D, d_out, ctx->stream, ctx->aux, nullptr);
+    sg::device_execute(plan->D, d_out, ctx->stream, ctx->aux, nullptr);
     std::vector<float> h((size_t)T);
     if (T) HIPCHK(hipMemcpyAsync(h.data(), d_out, (size_t)T * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -1142,7 +1122,7 @@ int sg_spectral_envelope(sg_ctx* ctx, int32_t nr, int32_t nc, const sg_formants*
     sg::finalize_spec(B);
     HIPCHK(hipSetDevice(ctx->device));
     sg::device_upload(B, P->D, ctx->stream);
-    sg::launch_spec_env(P->D, B, ctx->stream);
+    sg::launch_spec_env(P->D, ctx->stream);
     const size_t n = (size_t)nr * (size_t)nc;
     std::vector<float> h(n);
     if (n) HIPCHK(hipMemcpyAsync(h.data(), P->D.fl + B.fe_base + B.envjobs[0].out, n * sizeof(float),

@@ -189,14 +189,14 @@ extern "C" __global__ __launch_bounds__(256) void sg_spec_env(const SgEnvTask* _
 }
 
 #include "sg_exec.h"
+#include "sg_launch.h"
 
 namespace sg {
-void launch_spec_env(const DevicePlan& D, const Batch& B, hipStream_t s) {
-  const int64_t n = (int64_t)B.envtasks.size();
+void launch_spec_env(const DevicePlan& D, hipStream_t s) {
+  const int64_t n = D.n.envtasks;
   if (n <= 0) return;
   hipLaunchKernelGGL(sg_spec_env, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, D.envtasks, n, D.envjobs, D.eterms,
-                     D.ecols, D.elog2, (int64_t)B.elog2.size(), D.fl + B.fe_base);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) throw SgError(SG_E_DEVICE, std::string("launch sg_spec_env: ") + hipGetErrorString(e));
+                     D.ecols, D.elog2, D.n.elog2, D.fl + D.x.fe_base);
+  SG_LAUNCHED("sg_spec_env");
 }
 }  // namespace sg

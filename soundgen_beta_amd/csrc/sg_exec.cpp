@@ -1,6 +1,7 @@
 // sg_exec.cpp — HBM arena for a plan and the per-batch launch sequence.
 #include "sg_exec.h"
 #include "sg_amp.h"
+#include "sg_launch.h"
 #include "sg_sine_check.h"
 #include "sg_prof.h"
 
@@ -19,86 +20,6 @@
 #include <type_traits>
 
 namespace sg {
-
-namespace {
-#define HIPCHK(x)                                                                         \
-  do {                                                                                    \
-    hipError_t _e = (x);                                                                  \
-    if (_e != hipSuccess)                                                                 \
-      throw SgError(SG_E_DEVICE, std::string(#x) + ": " + hipGetErrorString(_e));     \
-  } while (0)
-
-constexpr size_t ALIGN = 256;
-size_t up(size_t x) { return (x + ALIGN - 1) / ALIGN * ALIGN; }
-
-struct Layout {
-  size_t tall, tlong, tshort, tallp, srun, trun, thp, fin_tiles_hp, W64, fh, frames64, frames64_tab, roots64, roots64_wl,
-      roots64_off;
-  size_t segs, epochs, knots, amps, ampcols, ampjobs, ampsrc, tasks, pieces, syls, syl_tiles, copy_tiles, ptiles, cknots, W, taskmax, ptilemax, maxes, total;
-  size_t geoms, frames, fgroups, olas, olatiles, olasegs, olatilemax, olamax, items, mixes, mixtiles, fl, fs;
-  size_t eterms, ecols, envjobs, envtasks, elog2;
-  explicit Layout(const Batch& B) {
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t r = o; o += up(bytes > 0 ? bytes : 1); return r; };
-    const size_t ntask = (size_t)bulk_size(B.tasks_x, B.tasks);
-    segs = take((size_t)bulk_size(B.segs_x, B.segs) * sizeof(SgSeg));
-    epochs = take(B.epochs.size() * sizeof(SgEpoch));
-    knots = take(B.knots.size() * sizeof(double));
-    amps = take((size_t)B.amp_total * sizeof(float) + 64 * sizeof(float));
-    ampcols = take(B.ampcols.size() * sizeof(SgAmpCol));
-    ampjobs = take(B.ampjobs.size() * sizeof(SgAmpJob));
-    ampsrc = take(B.ampsrc.size() * sizeof(float));
-    tasks = take(ntask * sizeof(SgWTask));
-    tall = take(ntask * sizeof(int32_t));
-    tlong = take(ntask * sizeof(int32_t));
-    tshort = take(ntask * sizeof(int32_t));
-    tallp = take(ntask * sizeof(int32_t));
-    srun = take((ntask + 1) * sizeof(int32_t));
-    trun = take((ntask + 1) * sizeof(int32_t));
-    thp = take(ntask * sizeof(int32_t));
-    fin_tiles_hp = take(B.fin_tiles_hp.size() * sizeof(SgSylTile));
-    W64 = take((size_t)B.w64_total * sizeof(double));
-    fh = take((size_t)B.fh_total * sizeof(double));
-    frames64 = take(B.frames64.size() * sizeof(SgFrame64));
-    frames64_tab = take(B.frames64_tab.size() * sizeof(int64_t));
-    roots64 = take((size_t)B.roots64_total * 2 * sizeof(double));
-    roots64_wl = take(B.roots64_wl.size() * sizeof(int32_t));
-    roots64_off = take(B.roots64_off.size() * sizeof(int64_t));
-    pieces = take(B.pieces.size() * sizeof(SgPiece));
-    syls = take(B.syls.size() * sizeof(SgSyllable));
-    syl_tiles = take(B.fin_tiles.size() * sizeof(SgSylTile));
-    copy_tiles = take(B.copy_tiles.size() * sizeof(SgCopyTile));
-    ptiles = take(B.ptiles.size() * sizeof(SgSylTile));
-    cknots = take(B.cknots.size() * sizeof(double));
-    W = take((size_t)B.w_total * sizeof(float));
-    taskmax = take(ntask * sizeof(float));
-    ptilemax = take(B.ptiles.size() * sizeof(float));
-    maxes = take(B.syls.size() * sizeof(float));
-    geoms = take(B.geoms.size() * sizeof(SgFftGeom));
-    frames = take((B.frames[0].size() + B.frames[1].size()) * sizeof(SgFrame));
-    fgroups = take(B.fgroups.size() * sizeof(SgFrameGroup));
-    olas = take(B.olas_dev.size() * sizeof(SgOla));
-    olatiles = take(B.olatiles.size() * sizeof(SgOlaTile));
-    olasegs = take(B.olasegs.size() * sizeof(SgSegment));
-    olatilemax = take((B.olatiles.size() + (size_t)B.n_segslots) * sizeof(float));  // tile slots, then segment slots
-    olamax = take(B.olas_dev.size() * sizeof(float));
-    items = take(B.items.size() * sizeof(SgNoiseItem));
-    mixes = take(B.mixes_dev.size() * sizeof(SgMix));
-    mixtiles = take(B.mixtiles.size() * sizeof(SgMixTile));
-    eterms = take((size_t)bulk_size(B.eterms_x, B.eterms) * sizeof(SgEnvTerm));
-    ecols = take(B.ecols.size() * sizeof(SgEnvCol));
-    envjobs = take(B.envjobs.size() * sizeof(SgEnvJob));
-    envtasks = take(B.envtasks.size() * sizeof(SgEnvTask));
-    elog2 = take(B.elog2.size() * sizeof(double));
-    // uploaded floats, then the device-computed envelopes from fe_base on, then the
-    // noise uniforms expanded at upload from fu_base on
-    fl = take((size_t)std::max<int64_t>(std::max<int64_t>(bulk_size(B.fl_x, B.fl), B.fe_base + B.fe_total),
-                                        B.fu_base + B.fu_total) * sizeof(float));
-    fs = take((size_t)B.fs_total * sizeof(float) + 256);
-    total = o;
-  }
-};
-}  // namespace
 
 // Split the 1024-sample finalize tiles of syllables without envelope or
 // drift: the parts of a tile lying in direct or zero pieces go to the fast
@@ -392,121 +313,124 @@ static TabSpans group_tables(const Batch& B, bool tables, TaskClasses* classes) 
   return S;
 }
 
+// SG_DEBUG_PLAN: what the plan holds, on stderr
+static void debug_plan_stats(const Batch& B) {
+  std::fprintf(stderr, "sg plan: %zu sine tasks, %zu syllables, %zu copy tiles, %zu general finalize tiles\n",
+               (size_t)bulk_size(B.tasks_x, B.tasks), B.syls.size(), B.copy_tiles.size(), B.fin_tiles.size());
+  {  // amplitude blocks of subharmonic (vocal-fry) epochs vs plain ones
+    double fry = 0, plain = 0;
+    int64_t nfry = 0;
+    for (const SgEpoch& e : B.epochs) {
+      const double b = (double)(2 * e.G - 1) * e.R * 4;
+      if (e.invD < 1) { fry += b; ++nfry; } else plain += b;
+    }
+    std::fprintf(stderr, "sg plan: amplitude bytes: plain epochs %.3g, subharmonic epochs %.3g (%lld of %zu)\n", plain,
+                 fry, (long long)nfry, B.epochs.size());
+  }
+  {
+    const TabSpans T = group_tables(B, true, nullptr);
+    int64_t cl = 0, cl_samples = 0;
+    bulk_each(B.tasks_x, B.tasks, [&](int64_t, const SgWTask* p, int64_t n) {
+      for (int64_t k = 0; k < n; ++k)
+        if (p[k].flags == (SG_TASK_CONST | SG_TASK_LIN)) { ++cl; cl_samples += p[k].len; }
+    });
+    int64_t hist[13] = {0};
+    for (const SgTabJob& j : T.jobs) ++hist[j.logn];
+    std::fprintf(stderr, "sg plan: wavetable jobs %zu, %lld direct syllables (N = 256/512/1024/2048: %lld %lld %lld %lld; %zu tasks, %lld samples, %.3g terms); CONST|LIN tasks %lld (%lld samples)\n",
+                 T.jobs.size(), (long long)T.direct, (long long)hist[8], (long long)hist[9], (long long)hist[10], (long long)hist[11],
+                 (size_t)T.tasks, (long long)T.samples, (double)T.terms, (long long)cl,
+                 (long long)cl_samples);
+  }
+  {  // pre-filter mixes that only place voiced syllables (raw items, no envelope, no noise)
+    int64_t all = 0, ident = 0, ni = 0, ident_items = 0, noisy = 0, noisy_cov = 0, other = 0, env_only = 0, env_kind[4] = {0, 0, 0, 0};
+    for (const SgMix& m : B.mixes[0]) {
+      all += m.len;
+      bool id = m.mult.kind == 0 && m.am_lo == 0 && m.to_fs == 1 && m.base_kind == SG_BASE_NONE;
+      for (int32_t i = m.item0; i < m.item0 + m.nitems && id; ++i) {
+        const SgNoiseItem& it = B.items[(size_t)i];
+        id = it.ola < 0 && it.fade < 2 && it.strength.kind == 0 && !(it.flags & SG_ITEM_F64);
+      }
+      if (id) { ident += m.len; ident_items += m.nitems; }
+      ni += m.nitems;
+      if (!id && m.mult.kind == 0 && m.to_fs == 1) {  // noise-carrying mixes: samples under a noise item
+        std::vector<std::pair<int64_t, int64_t>> iv;
+        for (int32_t i = m.item0; i < m.item0 + m.nitems; ++i) {
+          const SgNoiseItem& it = B.items[(size_t)i];
+          if (it.ola >= 0) iv.push_back({std::max<int64_t>(0, it.off), std::min(m.len, it.off + it.len)});
+        }
+        std::sort(iv.begin(), iv.end());
+        int64_t cov = 0, e = 0;
+        for (auto& q : iv) { const int64_t a0 = std::max(q.first, e); if (q.second > a0) cov += q.second - a0; e = std::max(e, q.second); }
+        noisy += m.len;
+        noisy_cov += cov;
+      } else if (!id) {
+        other += m.len;
+        bool vo = m.to_fs == 1;
+        for (int32_t i = m.item0; i < m.item0 + m.nitems && vo; ++i) vo = B.items[(size_t)i].ola < 0;
+        if (vo && m.mult.kind != 0) { env_only += m.len; env_kind[m.mult.kind & 3]++; }
+      }
+    }
+    std::fprintf(stderr, "sg plan: pre-filter mixes %zu, %lld samples; voiced-only %lld samples (%lld of %lld items)\n",
+                 B.mixes[0].size(), (long long)all, (long long)ident, (long long)ident_items, (long long)ni);
+    std::fprintf(stderr, "sg plan: pre-filter mixes with noise %lld samples (%lld under noise), enveloped or fp64 %lld "
+                 "(voiced-only with the global envelope %lld; contour kinds 1/2/3: %lld %lld %lld)\n",
+                 (long long)noisy, (long long)noisy_cov, (long long)other, (long long)env_only, (long long)env_kind[1],
+                 (long long)env_kind[2], (long long)env_kind[3]);
+  }
+  {  // spectral envelopes: jobs by column count, wave tasks, bins
+    int64_t j1 = 0, jm = 0, cols = 0, bins = 0;
+    for (const SgEnvJob& j : B.envjobs) {
+      (j.nc == 1 ? j1 : jm)++;
+      cols += j.nc;
+      bins += (int64_t)j.nc * j.nr;
+    }
+    std::fprintf(stderr, "sg plan: envelope jobs %zu (%lld one-column), %lld columns, %lld bins, %zu wave tasks\n",
+                 B.envjobs.size(), (long long)j1, (long long)cols, (long long)bins, B.envtasks.size());
+  }
+  std::vector<SgWTask> tasks;  // the merged task list (debug statistics only)
+  bulk_each(B.tasks_x, B.tasks, [&](int64_t, const SgWTask* p, int64_t n) { tasks.insert(tasks.end(), p, p + n); });
+  // sine-bank work: (sample, row) terms of the fp32 and the tall tasks, rows histogram of the tall ones
+  double terms[2] = {0, 0};
+  int64_t ntask[2] = {0, 0}, rmax = 0, samples[2] = {0, 0};
+  std::map<int, int64_t> rh;
+  int64_t nshort[2] = {0, 0}, lh[2][5] = {{0}};
+  double sterms[2] = {0, 0};
+  {  // fp64 (SG_TASK_HP) tasks
+    int64_t nh = 0, sh = 0, lh64 = 0;
+    double th = 0, rn = 0;
+    for (const SgWTask& t : tasks)
+      if (t.flags & SG_TASK_HP) {
+        ++nh; sh += t.len; lh64 += t.len <= 64;
+        th += (double)t.Rn * t.len * ((t.flags & SG_TASK_CONST) ? 1 : 2);
+        rn += t.Rn;
+      }
+    std::fprintf(stderr, "sg plan: fp64 tasks %lld (%lld samples, %lld of <= 64 samples, %.3g chain terms, mean Rn %.1f)\n",
+                 (long long)nh, (long long)sh, (long long)lh64, th, nh ? rn / nh : 0.0);
+  }
+  for (const SgWTask& t : tasks) {
+    const int k = t.R > SG_ROWS_F32 ? 1 : 0;
+    terms[k] += (double)t.R * t.len * ((t.flags & SG_TASK_CONST) ? 1 : 2);
+    ++ntask[k];
+    samples[k] += t.len;
+    if (t.len <= 64) { ++nshort[k]; sterms[k] += (double)t.R * t.len * ((t.flags & SG_TASK_CONST) ? 1 : 2); }
+    lh[k][t.len <= 64 ? 0 : t.len <= 128 ? 1 : t.len <= 256 ? 2 : t.len <= 512 ? 3 : 4]++;
+    if (k) {
+      rmax = std::max<int64_t>(rmax, t.R);
+      rh[t.R < 256 ? 0 : t.R < 512 ? 1 : t.R < 1024 ? 2 : t.R < 2048 ? 3 : 4]++;
+    }
+  }
+  std::fprintf(stderr, "sg plan: sine tasks fp32 %lld (%lld samples, %.3g chain terms), tall %lld (%lld samples, %.3g chain terms, max R %lld; R<256 %lld, <512 %lld, <1024 %lld, <2048 %lld, more %lld)\n",
+               (long long)ntask[0], (long long)samples[0], terms[0], (long long)ntask[1], (long long)samples[1], terms[1],
+               (long long)rmax, (long long)rh[0], (long long)rh[1], (long long)rh[2], (long long)rh[3], (long long)rh[4]);
+  for (int k = 0; k < 2; ++k)
+    std::fprintf(stderr, "sg plan: %s tasks <= 64 samples: %lld (%.3g chain terms); len <=64/128/256/512/more: %lld %lld %lld %lld %lld\n",
+                 k ? "tall" : "fp32", (long long)nshort[k], sterms[k], (long long)lh[k][0], (long long)lh[k][1],
+                 (long long)lh[k][2], (long long)lh[k][3], (long long)lh[k][4]);
+}
+
 void finalize_plan(Batch& B) {
   split_finalize_tiles(B);
-  if (std::getenv("SG_DEBUG_PLAN")) {
-    std::fprintf(stderr, "sg plan: %zu sine tasks, %zu syllables, %zu copy tiles, %zu general finalize tiles\n",
-                 (size_t)bulk_size(B.tasks_x, B.tasks), B.syls.size(), B.copy_tiles.size(), B.fin_tiles.size());
-    {  // amplitude blocks of subharmonic (vocal-fry) epochs vs plain ones
-      double fry = 0, plain = 0;
-      int64_t nfry = 0;
-      for (const SgEpoch& e : B.epochs) {
-        const double b = (double)(2 * e.G - 1) * e.R * 4;
-        if (e.invD < 1) { fry += b; ++nfry; } else plain += b;
-      }
-      std::fprintf(stderr, "sg plan: amplitude bytes: plain epochs %.3g, subharmonic epochs %.3g (%lld of %zu)\n", plain,
-                   fry, (long long)nfry, B.epochs.size());
-    }
-    {
-      const TabSpans T = group_tables(B, true, nullptr);
-      int64_t cl = 0, cl_samples = 0;
-      bulk_each(B.tasks_x, B.tasks, [&](int64_t, const SgWTask* p, int64_t n) {
-        for (int64_t k = 0; k < n; ++k)
-          if (p[k].flags == (SG_TASK_CONST | SG_TASK_LIN)) { ++cl; cl_samples += p[k].len; }
-      });
-      int64_t hist[13] = {0};
-      for (const SgTabJob& j : T.jobs) ++hist[j.logn];
-      std::fprintf(stderr, "sg plan: wavetable jobs %zu, %lld direct syllables (N = 256/512/1024/2048: %lld %lld %lld %lld; %zu tasks, %lld samples, %.3g terms); CONST|LIN tasks %lld (%lld samples)\n",
-                   T.jobs.size(), (long long)T.direct, (long long)hist[8], (long long)hist[9], (long long)hist[10], (long long)hist[11],
-                   (size_t)T.tasks, (long long)T.samples, (double)T.terms, (long long)cl,
-                   (long long)cl_samples);
-    }
-    {  // pre-filter mixes that only place voiced syllables (raw items, no envelope, no noise)
-      int64_t all = 0, ident = 0, ni = 0, ident_items = 0, noisy = 0, noisy_cov = 0, other = 0, env_only = 0, env_kind[4] = {0, 0, 0, 0};
-      for (const SgMix& m : B.mixes[0]) {
-        all += m.len;
-        bool id = m.mult.kind == 0 && m.am_lo == 0 && m.to_fs == 1 && m.base_kind == SG_BASE_NONE;
-        for (int32_t i = m.item0; i < m.item0 + m.nitems && id; ++i) {
-          const SgNoiseItem& it = B.items[(size_t)i];
-          id = it.ola < 0 && it.fade < 2 && it.strength.kind == 0 && !(it.flags & SG_ITEM_F64);
-        }
-        if (id) { ident += m.len; ident_items += m.nitems; }
-        ni += m.nitems;
-        if (!id && m.mult.kind == 0 && m.to_fs == 1) {  // noise-carrying mixes: samples under a noise item
-          std::vector<std::pair<int64_t, int64_t>> iv;
-          for (int32_t i = m.item0; i < m.item0 + m.nitems; ++i) {
-            const SgNoiseItem& it = B.items[(size_t)i];
-            if (it.ola >= 0) iv.push_back({std::max<int64_t>(0, it.off), std::min(m.len, it.off + it.len)});
-          }
-          std::sort(iv.begin(), iv.end());
-          int64_t cov = 0, e = 0;
-          for (auto& q : iv) { const int64_t a0 = std::max(q.first, e); if (q.second > a0) cov += q.second - a0; e = std::max(e, q.second); }
-          noisy += m.len;
-          noisy_cov += cov;
-        } else if (!id) {
-          other += m.len;
-          bool vo = m.to_fs == 1;
-          for (int32_t i = m.item0; i < m.item0 + m.nitems && vo; ++i) vo = B.items[(size_t)i].ola < 0;
-          if (vo && m.mult.kind != 0) { env_only += m.len; env_kind[m.mult.kind & 3]++; }
-        }
-      }
-      std::fprintf(stderr, "sg plan: pre-filter mixes %zu, %lld samples; voiced-only %lld samples (%lld of %lld items)\n",
-                   B.mixes[0].size(), (long long)all, (long long)ident, (long long)ident_items, (long long)ni);
-      std::fprintf(stderr, "sg plan: pre-filter mixes with noise %lld samples (%lld under noise), enveloped or fp64 %lld "
-                   "(voiced-only with the global envelope %lld; contour kinds 1/2/3: %lld %lld %lld)\n",
-                   (long long)noisy, (long long)noisy_cov, (long long)other, (long long)env_only, (long long)env_kind[1],
-                   (long long)env_kind[2], (long long)env_kind[3]);
-    }
-    {  // spectral envelopes: jobs by column count, wave tasks, bins
-      int64_t j1 = 0, jm = 0, cols = 0, bins = 0;
-      for (const SgEnvJob& j : B.envjobs) {
-        (j.nc == 1 ? j1 : jm)++;
-        cols += j.nc;
-        bins += (int64_t)j.nc * j.nr;
-      }
-      std::fprintf(stderr, "sg plan: envelope jobs %zu (%lld one-column), %lld columns, %lld bins, %zu wave tasks\n",
-                   B.envjobs.size(), (long long)j1, (long long)cols, (long long)bins, B.envtasks.size());
-    }
-    std::vector<SgWTask> tasks;  // the merged task list (debug statistics only)
-    bulk_each(B.tasks_x, B.tasks, [&](int64_t, const SgWTask* p, int64_t n) { tasks.insert(tasks.end(), p, p + n); });
-    // sine-bank work: (sample, row) terms of the fp32 and the tall tasks, rows histogram of the tall ones
-    double terms[2] = {0, 0};
-    int64_t ntask[2] = {0, 0}, rmax = 0, samples[2] = {0, 0};
-    std::map<int, int64_t> rh;
-    int64_t nshort[2] = {0, 0}, lh[2][5] = {{0}};
-    double sterms[2] = {0, 0};
-    {  // fp64 (SG_TASK_HP) tasks
-      int64_t nh = 0, sh = 0, lh64 = 0;
-      double th = 0, rn = 0;
-      for (const SgWTask& t : tasks)
-        if (t.flags & SG_TASK_HP) {
-          ++nh; sh += t.len; lh64 += t.len <= 64;
-          th += (double)t.Rn * t.len * ((t.flags & SG_TASK_CONST) ? 1 : 2);
-          rn += t.Rn;
-        }
-      std::fprintf(stderr, "sg plan: fp64 tasks %lld (%lld samples, %lld of <= 64 samples, %.3g chain terms, mean Rn %.1f)\n",
-                   (long long)nh, (long long)sh, (long long)lh64, th, nh ? rn / nh : 0.0);
-    }
-    for (const SgWTask& t : tasks) {
-      const int k = t.R > SG_ROWS_F32 ? 1 : 0;
-      terms[k] += (double)t.R * t.len * ((t.flags & SG_TASK_CONST) ? 1 : 2);
-      ++ntask[k];
-      samples[k] += t.len;
-      if (t.len <= 64) { ++nshort[k]; sterms[k] += (double)t.R * t.len * ((t.flags & SG_TASK_CONST) ? 1 : 2); }
-      lh[k][t.len <= 64 ? 0 : t.len <= 128 ? 1 : t.len <= 256 ? 2 : t.len <= 512 ? 3 : 4]++;
-      if (k) {
-        rmax = std::max<int64_t>(rmax, t.R);
-        rh[t.R < 256 ? 0 : t.R < 512 ? 1 : t.R < 1024 ? 2 : t.R < 2048 ? 3 : 4]++;
-      }
-    }
-    std::fprintf(stderr, "sg plan: sine tasks fp32 %lld (%lld samples, %.3g chain terms), tall %lld (%lld samples, %.3g chain terms, max R %lld; R<256 %lld, <512 %lld, <1024 %lld, <2048 %lld, more %lld)\n",
-                 (long long)ntask[0], (long long)samples[0], terms[0], (long long)ntask[1], (long long)samples[1], terms[1],
-                 (long long)rmax, (long long)rh[0], (long long)rh[1], (long long)rh[2], (long long)rh[3], (long long)rh[4]);
-    for (int k = 0; k < 2; ++k)
-      std::fprintf(stderr, "sg plan: %s tasks <= 64 samples: %lld (%.3g chain terms); len <=64/128/256/512/more: %lld %lld %lld %lld %lld\n",
-                   k ? "tall" : "fp32", (long long)nshort[k], sterms[k], (long long)lh[k][0], (long long)lh[k][1],
-                   (long long)lh[k][2], (long long)lh[k][3], (long long)lh[k][4]);
-  }
+  if (std::getenv("SG_DEBUG_PLAN")) debug_plan_stats(B);
   // crossfade-piece tiles: fp32 syllables first, then the fp64 ones (sg_piece_max_hp)
   B.ptiles.clear();
   bool any_hp = false;
@@ -555,13 +479,12 @@ void finalize_plan(Batch& B) {
   }
 }
 
-int64_t device_bytes(const Batch& B) { return (int64_t)Layout(B).total; }
+int64_t device_bytes(const Batch& B) { return (int64_t)arena_bytes(arena_counts(B)); }
 
 void device_free(DevicePlan& D) {
   if (D.arena) (void)hipFree(D.arena);
   if (D.tabbuf) (void)hipFree(D.tabbuf);
   D.pcm.free();
-  for (hipEvent_t e : D.ev_slice) (void)hipEventDestroy(e);
   if (D.ev_fork) (void)hipEventDestroy(D.ev_fork);
   if (D.ev_join) (void)hipEventDestroy(D.ev_join);
   D = DevicePlan{};
@@ -588,6 +511,42 @@ extern "C" int sg_set_sine_table(int32_t on) {
 }
 namespace sg {
 
+// A copy into an arena section (sg_arena.h: arena_copy_bytes refuses what does not fit)
+template <class T, class S>
+static void put(hipStream_t s, const char* name, T* sec, int64_t count, const S* src, int64_t n, int64_t at) {
+  static_assert(std::is_same<std::remove_const_t<T>, S>::value, "a section takes elements of its own type");
+  const size_t bytes = arena_copy_bytes(name, sizeof(T), count, at, n);
+  if (bytes) HIPCHK(hipMemcpyAsync(const_cast<S*>(sec) + at, src, bytes, hipMemcpyHostToDevice, s));
+}
+template <class T, class V>
+static void put(hipStream_t s, const char* name, T* sec, int64_t count, const V& v) {
+  put(s, name, sec, count, v.data(), (int64_t)v.size(), 0);
+}
+
+// what the launch sequence reads of the plan (sg_exec.h)
+static ExecInfo exec_info(const Batch& B) {
+  ExecInfo x;
+  x.slices = B.slices;
+  x.copies = B.copies;
+  x.ptile_hp = B.ptile_hp;
+  for (int ph = 0; ph < 2; ++ph) {
+    for (int k = 0; k < 3; ++k) x.fgroup_range[ph][k] = B.fgroup_range[ph][k];
+    for (int k = 0; k < 2; ++k) {
+      x.fgroup_lds[ph][k] = B.fgroup_lds[ph][k];
+      x.seg_range[ph][k] = B.seg_range[ph][k];
+    }
+    x.frames64_w[ph] = B.frames64_w[ph];
+  }
+  x.olatile_split = B.olatile_split;
+  x.ola_split = B.ola_split;
+  x.mixtile_hp = B.mixtile_hp;
+  x.mixtile_split = B.mixtile_split;
+  x.frames64_noise = B.frames64_noise;
+  x.frames64_maxwl = B.frames64_maxwl;
+  x.fe_base = B.fe_base;
+  return x;
+}
+
 void device_upload(const Batch& B, DevicePlan& D, hipStream_t s) {
   // SG_PLAN_PROF=1: seconds of each upload stage on stderr
   auto tprev = std::chrono::steady_clock::now();
@@ -597,75 +556,25 @@ void device_upload(const Batch& B, DevicePlan& D, hipStream_t s) {
     std::fprintf(stderr, "sg_upload_prof %-10s %.3f s\n", what, std::chrono::duration<double>(t - tprev).count());
     tprev = t;
   };
-  Layout L(B);
-  if (D.arena && D.arena_bytes < L.total) device_free(D);
+  const ArenaCounts n = arena_counts(B);
+  const size_t total = arena_bytes(n);
+  if (D.arena && D.arena_bytes < total) device_free(D);
   if (!D.arena) {
-    HIPCHK(hipMalloc(&D.arena, L.total));
-    D.arena_bytes = L.total;
+    HIPCHK(hipMalloc(&D.arena, total));
+    D.arena_bytes = total;
   }
   stage("malloc");
-  char* a = D.arena;
-  D.segs = (SgSeg*)(a + L.segs);
-  D.epochs = (SgEpoch*)(a + L.epochs);
-  D.knots = (double*)(a + L.knots);
-  D.amps = (float*)(a + L.amps);
-  D.ampcols = (const SgAmpCol*)(a + L.ampcols);
-  D.ampjobs = (const SgAmpJob*)(a + L.ampjobs);
-  D.ampsrc = (const float*)(a + L.ampsrc);
-  D.tasks = (SgWTask*)(a + L.tasks);
-  D.tall = (int32_t*)(a + L.tall);
-  D.tlong = (int32_t*)(a + L.tlong);
-  D.tshort = (int32_t*)(a + L.tshort);
-  D.tallp = (int32_t*)(a + L.tallp);
-  D.srun = (int32_t*)(a + L.srun);
-  D.trun = (int32_t*)(a + L.trun);
-  D.thp = (int32_t*)(a + L.thp);
-  D.fin_tiles_hp = (SgSylTile*)(a + L.fin_tiles_hp);
-  D.W64 = (double*)(a + L.W64);
-  D.fh = (double*)(a + L.fh);
-  D.frames64 = (SgFrame64*)(a + L.frames64);
-  D.frames64_tab = (int64_t*)(a + L.frames64_tab);
-  D.roots64 = (double*)(a + L.roots64);
-  D.roots64_wl = (int32_t*)(a + L.roots64_wl);
-  D.roots64_off = (int64_t*)(a + L.roots64_off);
-  D.pieces = (SgPiece*)(a + L.pieces);
-  D.syls = (SgSyllable*)(a + L.syls);
-  D.syl_tiles = (SgSylTile*)(a + L.syl_tiles);
-  D.copy_tiles = (SgCopyTile*)(a + L.copy_tiles);
-  D.ptiles = (SgSylTile*)(a + L.ptiles);
-  D.cknots = (double*)(a + L.cknots);
-  D.W = (float*)(a + L.W);
-  D.taskmax = (float*)(a + L.taskmax);
-  D.ptilemax = (float*)(a + L.ptilemax);
-  D.maxes = (float*)(a + L.maxes);
-  D.geoms = (SgFftGeom*)(a + L.geoms);
-  D.frames = (SgFrame*)(a + L.frames);
-  D.fgroups = (SgFrameGroup*)(a + L.fgroups);
-  D.olas = (SgOla*)(a + L.olas);
-  D.olatiles = (SgOlaTile*)(a + L.olatiles);
-  D.olasegs = (SgSegment*)(a + L.olasegs);
-  D.olatilemax = (float*)(a + L.olatilemax);
-  D.olamax = (float*)(a + L.olamax);
-  D.items = (SgNoiseItem*)(a + L.items);
-  D.mixes = (SgMix*)(a + L.mixes);
-  D.mixtiles = (SgMixTile*)(a + L.mixtiles);
-  D.fl = (float*)(a + L.fl);
-  D.fs = (float*)(a + L.fs);
-  D.eterms = (SgEnvTerm*)(a + L.eterms);
-  D.ecols = (SgEnvCol*)(a + L.ecols);
-  D.envjobs = (SgEnvJob*)(a + L.envjobs);
-  D.envtasks = (SgEnvTask*)(a + L.envtasks);
-  D.elog2 = (double*)(a + L.elog2);
-  auto cp = [&](void* dst, const void* src, size_t bytes) {
-    if (bytes) HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
-  };
-  bulk_each(B.segs_x, B.segs, [&](int64_t o, const SgSeg* p, int64_t n) { cp(D.segs + o, p, n * sizeof(SgSeg)); });
-  cp(D.epochs, B.epochs.data(), B.epochs.size() * sizeof(SgEpoch));
-  cp(D.knots, B.knots.data(), B.knots.size() * sizeof(double));
-  cp((void*)D.ampcols, B.ampcols.data(), B.ampcols.size() * sizeof(SgAmpCol));
-  cp((void*)D.ampjobs, B.ampjobs.data(), B.ampjobs.size() * sizeof(SgAmpJob));
-  cp((void*)D.ampsrc, B.ampsrc.data(), B.ampsrc.size() * sizeof(float));
-  bulk_each(B.tasks_x, B.tasks, [&](int64_t o, const SgWTask* p, int64_t n) { cp(D.tasks + o, p, n * sizeof(SgWTask)); });
+  D.n = n;
+  arena_point(n, D.arena, D);
+  // every copy into the arena: n elements to element `at` of a section, or a whole vector to its start
+#define PUT(sec, ...) put(s, #sec, D.sec, D.n.sec, __VA_ARGS__)
+  bulk_each(B.segs_x, B.segs, [&](int64_t o, const SgSeg* p, int64_t k) { PUT(segs, p, k, o); });
+  PUT(epochs, B.epochs);
+  PUT(knots, B.knots);
+  PUT(ampcols, B.ampcols);
+  PUT(ampjobs, B.ampjobs);
+  PUT(ampsrc, B.ampsrc);
+  bulk_each(B.tasks_x, B.tasks, [&](int64_t o, const SgWTask* p, int64_t k) { PUT(tasks, p, k, o); });
   stage("copy_tasks");
   // wavetable spans (SgTabJob, sg_dev.h) and the task classes, block by block
   TaskClasses C;
@@ -693,85 +602,81 @@ void device_upload(const Batch& B, DevicePlan& D, hipStream_t s) {
     D.tabjobs = (SgTabJob*)D.tabbuf;
   }
   stage("classify");
-  cp(D.tall, D.tall_host.data(), D.tall_host.size() * sizeof(int32_t));
-  cp(D.tlong, D.tlong_host.data(), D.tlong_host.size() * sizeof(int32_t));
-  cp(D.tshort, D.tshort_host.data(), D.tshort_host.size() * sizeof(int32_t));
-  cp(D.tallp, D.tallp_host.data(), D.tallp_host.size() * sizeof(int32_t));
-  cp(D.srun, D.srun_host.data(), D.srun_host.size() * sizeof(int32_t));
-  cp(D.trun, D.trun_host.data(), D.trun_host.size() * sizeof(int32_t));
-  cp(D.thp, D.thp_host.data(), D.thp_host.size() * sizeof(int32_t));
-  if (!D.tabjobs_host.empty()) cp(D.tabjobs, D.tabjobs_host.data(), D.tabjobs_host.size() * sizeof(SgTabJob));
-  cp(D.fin_tiles_hp, B.fin_tiles_hp.data(), B.fin_tiles_hp.size() * sizeof(SgSylTile));
-  cp(D.frames64, B.frames64.data(), B.frames64.size() * sizeof(SgFrame64));
-  cp(D.frames64_tab, B.frames64_tab.data(), B.frames64_tab.size() * sizeof(int64_t));
-  cp(D.roots64_wl, B.roots64_wl.data(), B.roots64_wl.size() * sizeof(int32_t));
-  cp(D.roots64_off, B.roots64_off.data(), B.roots64_off.size() * sizeof(int64_t));
-  cp(D.pieces, B.pieces.data(), B.pieces.size() * sizeof(SgPiece));
-  cp(D.syls, B.syls.data(), B.syls.size() * sizeof(SgSyllable));
-  cp(D.syl_tiles, B.fin_tiles.data(), B.fin_tiles.size() * sizeof(SgSylTile));
+  PUT(tall, D.tall_host);
+  PUT(tlong, D.tlong_host);
+  PUT(tshort, D.tshort_host);
+  PUT(tallp, D.tallp_host);
+  PUT(srun, D.srun_host);
+  PUT(trun, D.trun_host);
+  PUT(thp, D.thp_host);
+  if (!D.tabjobs_host.empty())  // not an arena section: the allocation above, sized for these jobs
+    HIPCHK(hipMemcpyAsync(D.tabjobs, D.tabjobs_host.data(), D.tabjobs_host.size() * sizeof(SgTabJob),
+                          hipMemcpyHostToDevice, s));
+  PUT(fin_tiles_hp, B.fin_tiles_hp);
+  PUT(frames64, B.frames64);
+  PUT(frames64_tab, B.frames64_tab);
+  PUT(roots64_wl, B.roots64_wl);
+  PUT(roots64_off, B.roots64_off);
+  PUT(pieces, B.pieces);
+  PUT(syls, B.syls);
+  PUT(syl_tiles, B.fin_tiles);
   if (T.direct) {  // direct syllables: their W-reading copy tiles become empty (zero pieces stay)
     std::vector<SgCopyTile> ct(B.copy_tiles);
     for (SgCopyTile& c : ct)
       if (T.direct_syl[(size_t)c.syl] && !(c.flags & SG_COPY_ZERO)) c.n = 0;
-    cp(D.copy_tiles, ct.data(), ct.size() * sizeof(SgCopyTile));
+    PUT(copy_tiles, ct);
     HIPCHK(hipStreamSynchronize(s));  // ct is a temporary
   } else {
-    cp(D.copy_tiles, B.copy_tiles.data(), B.copy_tiles.size() * sizeof(SgCopyTile));
+    PUT(copy_tiles, B.copy_tiles);
   }
-  cp(D.ptiles, B.ptiles.data(), B.ptiles.size() * sizeof(SgSylTile));
-  cp(D.cknots, B.cknots.data(), B.cknots.size() * sizeof(double));
-  cp(D.geoms, B.geoms.data(), B.geoms.size() * sizeof(SgFftGeom));
-  cp(D.frames, B.frames[0].data(), B.frames[0].size() * sizeof(SgFrame));
-  cp(D.frames + B.frames[0].size(), B.frames[1].data(), B.frames[1].size() * sizeof(SgFrame));
-  cp(D.fgroups, B.fgroups.data(), B.fgroups.size() * sizeof(SgFrameGroup));
-  cp(D.olas, B.olas_dev.data(), B.olas_dev.size() * sizeof(SgOla));
-  cp(D.olatiles, B.olatiles.data(), B.olatiles.size() * sizeof(SgOlaTile));
-  cp(D.olasegs, B.olasegs.data(), B.olasegs.size() * sizeof(SgSegment));
-  cp(D.items, B.items.data(), B.items.size() * sizeof(SgNoiseItem));
-  cp(D.mixes, B.mixes_dev.data(), B.mixes_dev.size() * sizeof(SgMix));
-  cp(D.mixtiles, B.mixtiles.data(), B.mixtiles.size() * sizeof(SgMixTile));
-  bulk_each(B.fl_x, B.fl, [&](int64_t o, const float* p, int64_t n) { cp(D.fl + o, p, n * sizeof(float)); });
-  bulk_each(B.eterms_x, B.eterms,
-            [&](int64_t o, const SgEnvTerm* p, int64_t n) { cp(D.eterms + o, p, n * sizeof(SgEnvTerm)); });
-  cp(D.ecols, B.ecols.data(), B.ecols.size() * sizeof(SgEnvCol));
-  cp(D.envjobs, B.envjobs.data(), B.envjobs.size() * sizeof(SgEnvJob));
-  cp(D.envtasks, B.envtasks.data(), B.envtasks.size() * sizeof(SgEnvTask));
-  cp(D.elog2, B.elog2.data(), B.elog2.size() * sizeof(double));
+  PUT(ptiles, B.ptiles);
+  PUT(cknots, B.cknots);
+  PUT(geoms, B.geoms);
+  PUT(frames, B.frames[0]);
+  PUT(frames, B.frames[1].data(), (int64_t)B.frames[1].size(), (int64_t)B.frames[0].size());
+  PUT(fgroups, B.fgroups);
+  PUT(olas, B.olas_dev);
+  PUT(olatiles, B.olatiles);
+  PUT(olasegs, B.olasegs);
+  PUT(items, B.items);
+  PUT(mixes, B.mixes_dev);
+  PUT(mixtiles, B.mixtiles);
+  bulk_each(B.fl_x, B.fl, [&](int64_t o, const float* p, int64_t k) { PUT(fl, p, k, o); });
+  bulk_each(B.eterms_x, B.eterms, [&](int64_t o, const SgEnvTerm* p, int64_t k) { PUT(eterms, p, k, o); });
+  PUT(ecols, B.ecols);
+  PUT(envjobs, B.envjobs);
+  PUT(envtasks, B.envtasks);
+  PUT(elog2, B.elog2);
+#undef PUT
   stage("copy_rest");
-  launch_amp_build(D, (int64_t)B.ampjobs.size(), s);  // the amplitude blocks, from the jobs just copied
+  launch_amp_build(D, D.n.ampjobs, s);  // the amplitude blocks, from the jobs just copied
   // gathered noise uniforms: the union of the draw ranges and the item jobs in a
   // temporary buffer, expanded into the uniform area
   void* ug = nullptr;
   if (!B.ujobs.empty()) {
-    const size_t ub = up(B.ustream.size() * sizeof(float)), jb = B.ujobs.size() * sizeof(SgUJob);
+    const size_t ub = arena_up(B.ustream.size() * sizeof(float)), jb = B.ujobs.size() * sizeof(SgUJob);
     HIPCHK(hipMalloc(&ug, ub + jb));
-    cp(ug, B.ustream.data(), B.ustream.size() * sizeof(float));
-    cp((char*)ug + ub, B.ujobs.data(), jb);
+    if (ub) HIPCHK(hipMemcpyAsync(ug, B.ustream.data(), B.ustream.size() * sizeof(float), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync((char*)ug + ub, B.ujobs.data(), jb, hipMemcpyHostToDevice, s));
     launch_ugather((const SgUJob*)((char*)ug + ub), (int64_t)B.ujobs.size(), (const float*)ug, D.fl, s);
   }
   HIPCHK(hipStreamSynchronize(s));
   stage("amps_sync");
   if (ug) (void)hipFree(ug);
-  while (D.ev_slice.size() < B.slices.size()) {
-    hipEvent_t e;
-    HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    D.ev_slice.push_back(e);
-  }
   if (!D.ev_fork) HIPCHK(hipEventCreateWithFlags(&D.ev_fork, hipEventDisableTiming));
   if (!D.ev_join) HIPCHK(hipEventCreateWithFlags(&D.ev_join, hipEventDisableTiming));
+  D.x = exec_info(B);
   D.uploaded = true;
 }
 
 // the harmonic chain of one plan on stream h: sine banks (four task classes),
 // maxima, finalize
-static void device_execute_harm(const Batch& B, DevicePlan& D, float* d_out, hipStream_t h,
-                                std::vector<SgProfEvent>* prof) {
+static void device_execute_harm(DevicePlan& D, float* d_out, hipStream_t h, std::vector<SgProfEvent>* prof) {
   // fp64 syllables: their sine-bank tasks and crossfade maxima first, so the
   // slices' per-syllable maxima include them; their finalize after the slices
   launch_sine_bank_hp(D, (int64_t)D.thp_host.size(), h);
-  launch_piece_max_hp(D, B.ptile_hp, (int64_t)B.ptiles.size() - B.ptile_hp, h);
-  for (size_t c = 0; c < B.slices.size(); ++c) {
-    const Slice& sl = B.slices[c];
+  launch_piece_max_hp(D, D.x.ptile_hp, D.n.ptiles - D.x.ptile_hp, h);
+  for (const Slice& sl : D.x.slices) {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (prof) {
       HIPCHK(hipEventCreate(&e0));
@@ -826,7 +731,7 @@ static void device_execute_harm(const Batch& B, DevicePlan& D, float* d_out, hip
     launch_harm_copy(D, sl.c0, sl.c1 - sl.c0, d_out, h);
     launch_harm_finalize(D, sl.f0, sl.f1 - sl.f0, d_out, h);
   }
-  launch_harm_finalize_hp(D, (int64_t)B.fin_tiles_hp.size(), h);
+  launch_harm_finalize_hp(D, D.n.fin_tiles_hp, h);
 }
 
 // The harmonic source (sine banks -> maxima -> finalize) and the noise phase
@@ -841,9 +746,8 @@ static bool overlap_on() {
   return on;
 }
 
-void device_execute(const Batch& B, DevicePlan& D, float* d_out, hipStream_t s, hipStream_t s2,
-                    std::vector<SgProfEvent>* prof) {
-  std::vector<PlanRun> one{PlanRun{&B, &D, d_out}};
+void device_execute(DevicePlan& D, float* d_out, hipStream_t s, hipStream_t s2, std::vector<SgProfEvent>* prof) {
+  std::vector<PlanRun> one{PlanRun{&D, d_out}};
   device_execute_many(one, s, s2, prof);
 }
 
@@ -858,8 +762,8 @@ void device_execute_many(const std::vector<PlanRun>& runs, hipStream_t s, hipStr
   const bool ovl = overlap_on() && prof == nullptr && s2 != nullptr && s2 != s;
   if (!ovl) {
     for (const PlanRun& r : runs) {
-      device_execute_harm(*r.B, *r.D, r.out, s, prof);
-      device_execute_spec(*r.B, *r.D, r.out, s, prof, false);
+      device_execute_harm(*r.D, r.out, s, prof);
+      device_execute_spec(*r.D, r.out, s, prof, false);
     }
     HIPCHK(hipGetLastError());
     return;
@@ -869,68 +773,53 @@ void device_execute_many(const std::vector<PlanRun>& runs, hipStream_t s, hipStr
   HIPCHK(hipEventRecord(D0.ev_fork, s));
   HIPCHK(hipStreamWaitEvent(s2, D0.ev_fork, 0));
   for (const PlanRun& r : runs) {
-    device_execute_harm(*r.B, *r.D, r.out, s2, nullptr);
+    device_execute_harm(*r.D, r.out, s2, nullptr);
     HIPCHK(hipEventRecord(r.D->ev_join, s2));
   }
-  for (const PlanRun& r : runs) device_execute_spec(*r.B, *r.D, r.out, s, nullptr, true, r.D->ev_join);
+  for (const PlanRun& r : runs) device_execute_spec(*r.D, r.out, s, nullptr, true, r.D->ev_join);
   HIPCHK(hipGetLastError());
 }
 
 // Spectral phases after the harmonic syllables: noise frames -> noise OLA,
 // pre-filter mixes (sounds), filter frames -> filter OLA, final mixes.
-void device_execute_spec(const Batch& B, const DevicePlan& D, float* d_out, hipStream_t s,
-                         std::vector<SgProfEvent>* prof, bool join, hipEvent_t harm_done) {
-  launch_spec_env(D, B, s);  // envelopes and noise filters read by both phases
+void device_execute_spec(const DevicePlan& D, float* d_out, hipStream_t s, std::vector<SgProfEvent>* prof, bool join,
+                         hipEvent_t harm_done) {
+  const ExecInfo& X = D.x;
+  launch_spec_env(D, s);  // envelopes and noise filters read by both phases
   // phase: fused STFT/ISTFT/OLA segments, unfused frame groups + OLA tiles, per-OLA maxima
   auto phase = [&](int ph) {
-    const int64_t* r = B.fgroup_range[ph];
-    const int64_t nseg = B.seg_range[ph][1] - B.seg_range[ph][0];
+    const int64_t* r = X.fgroup_range[ph];
+    const int64_t nseg = X.seg_range[ph][1] - X.seg_range[ph][0];
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (prof && nseg > 0) {
       HIPCHK(hipEventCreate(&e0));
       HIPCHK(hipEventCreate(&e1));
       HIPCHK(hipEventRecord(e0, s));
     }
-    launch_stft_ola(D, ph, B.seg_range[ph][0], nseg, B.fgroup_lds[ph][0], s);
+    launch_stft_ola(D, ph, X.seg_range[ph][0], nseg, X.fgroup_lds[ph][0], s);
     if (prof && nseg > 0) {
       HIPCHK(hipEventRecord(e1, s));
       prof->push_back({SG_PROF_STFT_OLA, e0, e1});
     }
-    launch_fft_frames(D, r[1], r[2] - r[1], B.fgroup_lds[ph][1], s);
-    launch_fft_frames64(D, B, ph, s);  // fp64 noise frames (phase 0), fp64 filter frames (phase 1)
-    const int64_t t0 = ph == 0 ? 0 : B.olatile_split, t1 = ph == 0 ? B.olatile_split : (int64_t)B.olatiles.size();
-    const int64_t o0 = ph == 0 ? 0 : B.ola_split, o1 = ph == 0 ? B.ola_split : (int64_t)B.olas_dev.size();
+    launch_fft_frames(D, r[1], r[2] - r[1], X.fgroup_lds[ph][1], s);
+    launch_fft_frames64(D, ph, s);  // fp64 noise frames (phase 0), fp64 filter frames (phase 1)
+    const int64_t t0 = ph == 0 ? 0 : X.olatile_split, t1 = ph == 0 ? X.olatile_split : D.n.olatiles;
+    const int64_t o0 = ph == 0 ? 0 : X.ola_split, o1 = ph == 0 ? X.ola_split : D.n.olas;
     launch_ola(D, t0, t1 - t0, s);
     launch_ola_max(D, o0, o1 - o0, s);
   };
   phase(0);
-  for (const Batch::Copy& c : B.copies)
+  for (const Batch::Copy& c : X.copies)
     HIPCHK(hipMemcpyAsync(D.fs + c.fs_off, D.fl + c.fl_off, (size_t)c.n * sizeof(float), hipMemcpyDeviceToDevice, s));
   if (join) HIPCHK(hipStreamWaitEvent(s, harm_done, 0));  // the harmonic syllables (fs, out) are final
-  launch_mix(D, 0, B.mixtile_hp, d_out, s);
-  launch_mix_hp(D, B.mixtile_hp, B.mixtile_split - B.mixtile_hp, s);
+  launch_mix(D, 0, X.mixtile_hp, d_out, s);
+  launch_mix_hp(D, X.mixtile_hp, X.mixtile_split - X.mixtile_hp, s);
   phase(1);
-  launch_mix(D, B.mixtile_split, (int64_t)B.mixtiles.size() - B.mixtile_split, d_out, s);
+  launch_mix(D, X.mixtile_split, D.n.mixtiles - X.mixtile_split, d_out, s);
   HIPCHK(hipGetLastError());
 }
 
 // ------------------------------------------- test hook sg_debug_sine_bank
-namespace {
-struct DevMem {  // device buffers of the hook, freed on every way out
-  std::vector<void*> p;
-  template <class T>
-  T* get(size_t n) {
-    void* q = nullptr;
-    HIPCHK(hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)));
-    p.push_back(q);
-    return static_cast<T*>(q);
-  }
-  ~DevMem() {
-    for (void* q : p) (void)hipFree(q);
-  }
-};
-}  // namespace
-
 // The product's classifier and launchers on caller-built tasks (soundgen_hip.h). The
 // device copy of the tasks carries the syllables renumbered 0, 1, ... in order of
 // appearance (one SgSyllable each); nothing else of a record changes.
@@ -972,24 +861,18 @@ void debug_sine_bank(hipStream_t s, const SgWTask* tasks, int64_t ntasks, const 
   for (int c = 0; c < 5; ++c)
     for (int32_t i : *lists[c]) cls[i] = c;
 
-  DevMem M;
+  DevBuf M;  // the hook's device buffers, freed on every way out
   DevicePlan D;
-  auto put = [&](const auto& v) {
-    using V = typename std::decay_t<decltype(v)>::value_type;
-    V* d = M.get<V>(v.size());
-    if (!v.empty()) HIPCHK(hipMemcpyAsync(d, v.data(), v.size() * sizeof(V), hipMemcpyHostToDevice, s));
-    return d;
-  };
-  D.tasks = put(T);
-  D.syls = put(syls);
-  D.tlong = put(C.tlong);
-  D.tshort = put(C.tshort);
-  D.tall = put(C.tall);
-  D.tallp = put(C.tallp);
-  D.thp = put(C.thp);
-  D.srun = put(C.srun);
-  D.trun = put(C.trun);
-  D.tabjobs = put(J);
+  D.tasks = upload(M, T, s);
+  D.syls = upload(M, syls, s);
+  D.tlong = upload(M, C.tlong, s);
+  D.tshort = upload(M, C.tshort, s);
+  D.tall = upload(M, C.tall, s);
+  D.tallp = upload(M, C.tallp, s);
+  D.thp = upload(M, C.thp, s);
+  D.srun = upload(M, C.srun, s);
+  D.trun = upload(M, C.trun, s);
+  D.tabjobs = upload(M, J, s);
   D.amps = M.get<float>((size_t)namps);
   HIPCHK(hipMemcpyAsync(D.amps, amps, (size_t)namps * sizeof(float), hipMemcpyHostToDevice, s));
   D.cknots = M.get<double>(1);  // no contour of the hook's syllables has knots

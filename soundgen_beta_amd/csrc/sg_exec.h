@@ -5,6 +5,7 @@
 #include <utility>
 #include <vector>
 
+#include "sg_arena.h"
 #include "sg_plan.h"
 
 namespace sg {
@@ -21,34 +22,34 @@ struct PcmJob {
   void free();
 };
 
-struct DevicePlan {
+// What the launch sequence reads beside the arena: the slices, ranges, splits and
+// LDS sizes of the plan. device_upload copies it from the Batch; with the section
+// counts (DevicePlan::n) it is all that execution needs, so nothing of the host
+// plan is read after the upload.
+struct ExecInfo {
+  std::vector<Slice> slices;
+  std::vector<Batch::Copy> copies;  // fl -> fs before the filter phase
+  int64_t ptile_hp = 0;             // first crossfade-piece tile of an fp64 syllable
+  int64_t fgroup_range[2][3] = {{0, 0, 0}, {0, 0, 0}};
+  int fgroup_lds[2][2] = {{0, 0}, {0, 0}};
+  int64_t seg_range[2][2] = {{0, 0}, {0, 0}};
+  int64_t olatile_split = 0, ola_split = 0;
+  int64_t mixtile_hp = 0, mixtile_split = 0;
+  int64_t frames64_noise = 0, frames64_w[2] = {0, 0};
+  int32_t frames64_maxwl = 0;
+  int64_t fe_base = 0;              // the envelope area of fl
+};
+
+// The arena pointers (sg_arena.h: one per section, D.segs, D.tasks, ...) and what
+// belongs to an uploaded plan beside them
+struct DevicePlan : ArenaPtrs {
   bool uploaded = false;
   char* arena = nullptr;
   size_t arena_bytes = 0;
-  SgSeg* segs = nullptr;
-  SgEpoch* epochs = nullptr;
-  double* knots = nullptr;
-  float* amps = nullptr;
-  const SgAmpCol* ampcols = nullptr;  // sg_amp_build inputs (read at upload)
-  const SgAmpJob* ampjobs = nullptr;
-  const float* ampsrc = nullptr;
-  SgWTask* tasks = nullptr;
-  int32_t* tall = nullptr;           // indices of tasks with R > SG_ROWS_F32 (sg_sine_bank_tall)
-  std::vector<int32_t> tall_host;
-  int32_t* tlong = nullptr;          // fp32 tasks run one per wave (sg_sine_bank)
-  std::vector<int32_t> tlong_host;
-  int32_t* tshort = nullptr;         // fp32 tasks of <= 64 samples, two per wave (sg_sine_bank_pairs)
-  std::vector<int32_t> tshort_host;
-  int32_t* tallp = nullptr;          // tall tasks of <= 64 samples, two per wave (sg_sine_bank_tall_pairs)
-  std::vector<int32_t> tallp_host;
-  // runs of the two short lists: consecutive entries of one syllable, <= SG_RUN_TASKS each,
-  // one wave per run (positions in tshort / tallp where each run starts, then the list size)
-  int32_t* srun = nullptr;
-  std::vector<int32_t> srun_host;
-  int32_t* trun = nullptr;
-  std::vector<int32_t> trun_host;
-  int32_t* thp = nullptr;            // SG_TASK_HP tasks (sg_sine_bank_hp)
-  std::vector<int32_t> thp_host;
+  ArenaCounts n;  // the elements each section was sized for at upload
+  ExecInfo x;
+  // the sine-bank task classes (sections tall, tlong, tshort, tallp, srun, trun, thp), built at upload
+  std::vector<int32_t> tall_host, tlong_host, tshort_host, tallp_host, srun_host, trun_host, thp_host;
   // wavetable path (SgTabJob): tasks of long static-tone spans
   // (a separate allocation made at upload)
   char* tabbuf = nullptr;              // the wavetable spans' jobs (sg_sine_bank_tab)
@@ -56,44 +57,7 @@ struct DevicePlan {
   SgTabJob* tabjobs = nullptr;         // in task order
   std::vector<SgTabJob> tabjobs_host;
   int64_t tab_samples = 0, tab_terms = 0;  // samples and (sample, row) terms the tables stand in for
-  SgSylTile* fin_tiles_hp = nullptr; // finalize tiles of fp64 syllables (sg_harm_finalize_hp)
-  double* W64 = nullptr;             // fp64 epoch waveforms of SG_TASK_HP tasks
-  double* fh = nullptr;              // fp64 sounds (voiced parts, pre-filter sounds) of fp64 bouts
-  SgFrame64* frames64 = nullptr;     // their filter frames (sg_fft_frames64)
-  int64_t* frames64_tab = nullptr;   // per frame: offset of its root table in roots64
-  double* roots64 = nullptr;         // W_N^t tables (double2), one per window length (sg_roots64)
-  int32_t* roots64_wl = nullptr;
-  int64_t* roots64_off = nullptr;
-  SgPiece* pieces = nullptr;
-  SgSyllable* syls = nullptr;
-  SgSylTile* syl_tiles = nullptr;    // general-path finalize tiles (Batch::fin_tiles)
-  SgCopyTile* copy_tiles = nullptr;
-  SgSylTile* ptiles = nullptr;
-  double* cknots = nullptr;
-  float* W = nullptr;
-  float* taskmax = nullptr;
-  float* ptilemax = nullptr;
-  float* maxes = nullptr;
-  SgFftGeom* geoms = nullptr;
-  SgFrame* frames = nullptr;
-  SgFrameGroup* fgroups = nullptr;
-  SgOla* olas = nullptr;
-  SgOlaTile* olatiles = nullptr;
-  SgSegment* olasegs = nullptr;
-  float* olatilemax = nullptr;
-  float* olamax = nullptr;
-  SgNoiseItem* items = nullptr;
-  SgMix* mixes = nullptr;
-  SgMixTile* mixtiles = nullptr;
-  float* fl = nullptr;
-  float* fs = nullptr;
-  SgEnvTerm* eterms = nullptr;
-  SgEnvCol* ecols = nullptr;
-  SgEnvJob* envjobs = nullptr;
-  SgEnvTask* envtasks = nullptr;
-  double* elog2 = nullptr;
   PcmJob pcm;
-  std::vector<hipEvent_t> ev_slice;  // slice c's maxes are ready (s -> s2)
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
 };
 
@@ -105,20 +69,19 @@ struct SgProfEvent {
   int kernel;
   hipEvent_t e0, e1;
 };
-// Slice pipeline: sine bank + maxes of slice c on s, finalize of slice c on
-// s2 (overlapping the sine bank of c+1); s waits for s2 at the end. prof
-// (optional) receives one event pair per sine-bank and sg_stft_ola launch.
-void device_execute(const Batch& B, DevicePlan& D, float* d_out, hipStream_t s, hipStream_t s2,
-                    std::vector<SgProfEvent>* prof);
+// One uploaded plan: its harmonic chain (per slice: sine banks, maxima, finalize)
+// on s2 while s runs the envelopes and the noise phase; the pre-filter mixes on s
+// wait for both (device_execute_many of one plan). prof (optional) receives one
+// event pair per slice's sine banks and per sg_stft_ola launch, everything on s.
+void device_execute(DevicePlan& D, float* d_out, hipStream_t s, hipStream_t s2, std::vector<SgProfEvent>* prof);
 struct PlanRun {
-  const Batch* B;
   DevicePlan* D;
   float* out;
 };
 void device_execute_many(const std::vector<PlanRun>& runs, hipStream_t s, hipStream_t s2,
                          std::vector<SgProfEvent>* prof);
-void device_execute_spec(const Batch& B, const DevicePlan& D, float* d_out, hipStream_t s,
-                         std::vector<SgProfEvent>* prof, bool join = false, hipEvent_t harm_done = nullptr);
+void device_execute_spec(const DevicePlan& D, float* d_out, hipStream_t s, std::vector<SgProfEvent>* prof,
+                         bool join = false, hipEvent_t harm_done = nullptr);
 
 // Test hook sg_debug_sine_bank (soundgen_hip.h) on stream s, after sine_bank_args_check
 // (sg_sine_check.h); throws SgError
@@ -143,7 +106,7 @@ void launch_sine_bank_tab(const DevicePlan& D, int logn, int64_t j0, int64_t n, 
 void launch_piece_max_hp(const DevicePlan& D, int64_t p0, int64_t n_ptiles, hipStream_t s);
 void launch_harm_finalize_hp(const DevicePlan& D, int64_t n_stiles, hipStream_t s);
 void launch_mix_hp(const DevicePlan& D, int64_t t0, int64_t n_tiles, hipStream_t s);
-void launch_fft_frames64(const DevicePlan& D, const Batch& B, int ph, hipStream_t s);
+void launch_fft_frames64(const DevicePlan& D, int ph, hipStream_t s);
 // sg_fft.hip
 void launch_fft_frames(const DevicePlan& D, int64_t g0, int64_t n_groups, int lds_bytes, hipStream_t s);
 void launch_stft_ola(const DevicePlan& D, int phase, int64_t s0, int64_t n_segs, int lds_bytes, hipStream_t s);
@@ -153,6 +116,6 @@ void launch_fft_probe(const SgFftGeom* geom, const float* fl, float* data, int M
                       hipStream_t s);
 void launch_mix(const DevicePlan& D, int64_t t0, int64_t n_tiles, float* out, hipStream_t s);
 // sg_env.hip: every spectral-envelope job of the plan (getSpectralEnvelope)
-void launch_spec_env(const DevicePlan& D, const Batch& B, hipStream_t s);
+void launch_spec_env(const DevicePlan& D, hipStream_t s);
 
 }  // namespace sg

@@ -2021,17 +2021,11 @@ extern "C" __global__ __launch_bounds__(256) void sg_mix_hp(const SgMixTile* __r
 
 // ---------------------------------------------------------------- launchers
 #include "sg_exec.h"
+#include "sg_launch.h"
 
 #include <map>
 #include <mutex>
 namespace sg {
-// launch failures (bad configuration, LDS over the opted-in size) are loud
-#define SG_LAUNCHED(name)                                                                       \
-  do {                                                                                          \
-    const hipError_t _e = hipGetLastError();                                                    \
-    if (_e != hipSuccess) throw SgError(SG_E_DEVICE, std::string("launch " name ": ") + hipGetErrorString(_e)); \
-  } while (0)
-
 // Dynamic LDS above 64 KB must be opted into (160 KB per CU on gfx950). The
 // attribute is per device: remember the opted-in size per (kernel, device).
 static void lds_opt_in(const void* fn, int lds_bytes, const char* name) {
@@ -2074,17 +2068,17 @@ void launch_fft_probe(const SgFftGeom* geom, const float* fl, float* data, int M
 }
 // phase 0: the noise frames [0, frames64_noise); phase 1: the filter frames after them.
 // The root tables are built before the first of the two launches that has frames.
-void launch_fft_frames64(const DevicePlan& D, const Batch& B, int ph, hipStream_t s) {
-  const int64_t n0 = B.frames64_noise, n = (int64_t)B.frames64.size();
+void launch_fft_frames64(const DevicePlan& D, int ph, hipStream_t s) {
+  const int64_t n0 = D.x.frames64_noise, n = D.n.frames64;
   const int64_t f0 = ph == 0 ? 0 : n0, nf = ph == 0 ? n0 : n - n0;
   if (nf <= 0) return;
   if (ph == 0 || n0 == 0) {
-    hipLaunchKernelGGL(sg_roots64, dim3(16, (unsigned)B.roots64_wl.size()), dim3(256), 0, s, D.roots64_wl,
+    hipLaunchKernelGGL(sg_roots64, dim3(16, (unsigned)D.n.roots64_wl), dim3(256), 0, s, D.roots64_wl,
                        D.roots64_off, reinterpret_cast<double2*>(D.roots64));
     SG_LAUNCHED("sg_roots64");
   }
   // the leading wl = 2204 frames of the phase: one per wavefront
-  const int64_t nw = B.frames64_w[ph];
+  const int64_t nw = D.x.frames64_w[ph];
   if (nw > 0) {
     const int lds = SG_F64W_WAVES * SG_F64W_M * (int)sizeof(double2);  // a frame per wave
     lds_opt_in(reinterpret_cast<const void*>(&sg_fft_frames64w), lds, "sg_fft_frames64w");
@@ -2094,7 +2088,7 @@ void launch_fft_frames64(const DevicePlan& D, const Batch& B, int ph, hipStream_
     SG_LAUNCHED("sg_fft_frames64w");
   }
   if (nf - nw <= 0) return;
-  const int lds = (B.frames64_maxwl + 32) * (int)sizeof(double2);  // two M-point buffers + radix roots
+  const int lds = (D.x.frames64_maxwl + 32) * (int)sizeof(double2);  // two M-point buffers + radix roots
   lds_opt_in(reinterpret_cast<const void*>(&sg_fft_frames64), lds, "sg_fft_frames64");
   hipLaunchKernelGGL(sg_fft_frames64, dim3((unsigned)(nf - nw)), dim3(SG_F64_THREADS), lds, s, D.frames64 + f0 + nw,
                      D.frames64_tab + f0 + nw, reinterpret_cast<const double2*>(D.roots64), D.fl, D.fh, D.fs);

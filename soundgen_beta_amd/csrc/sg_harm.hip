@@ -1294,13 +1294,8 @@ __global__ __launch_bounds__(256) void sg_amp_build(const SgAmpJob* __restrict__
 }
 
 #include "sg_exec.h"
+#include "sg_launch.h"
 namespace sg {
-#define SG_LAUNCHED(name)                                                                       \
-  do {                                                                                          \
-    const hipError_t _e = hipGetLastError();                                                    \
-    if (_e != hipSuccess) throw SgError(SG_E_DEVICE, std::string("launch " name ": ") + hipGetErrorString(_e)); \
-  } while (0)
-
 void launch_amp_build(const DevicePlan& D, int64_t n_jobs, hipStream_t s) {
   if (n_jobs <= 0) return;
   hipLaunchKernelGGL(sg_amp_build, dim3((unsigned)n_jobs), dim3(256), 0, s, D.ampjobs, D.ampcols, D.ampsrc, D.elog2,

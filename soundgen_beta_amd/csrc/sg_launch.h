@@ -1,6 +1,6 @@
-// sg_launch.h — what every host-side launch sequence of the analysis features
-// (sg_mel.hip, sg_ssm.hip, sg_spectrogram.hip, sg_analyze.hip, sg_segment.hip) and the C entry
-// points (theirs and sg_api.cpp's) share: the HIP error check, the buffers of a
+// sg_launch.h — what every host-side launch sequence (the synthesis executor sg_exec.cpp and
+// its launchers; the analysis features sg_mel.hip, sg_ssm.hip, sg_spectrogram.hip, sg_analyze.hip,
+// sg_segment.hip) and the C entry points (theirs and sg_api.cpp's) share: the HIP error check, the buffers of a
 // launch sequence, the exception-to-code mapping of an entry point, the per-stage
 // device clock and the single-sound round trip. Host code that needs the HIP runtime.
 #pragma once
@@ -19,6 +19,13 @@
   do {                                                                                                   \
     hipError_t _e = (x);                                                                                 \
     if (_e != hipSuccess) throw sg::SgError(SG_E_DEVICE, std::string(#x) + ": " + hipGetErrorString(_e)); \
+  } while (0)
+
+// after a kernel launch: launch failures (bad configuration, LDS over the opted-in size) are loud
+#define SG_LAUNCHED(name)                                                                       \
+  do {                                                                                          \
+    const hipError_t _e = hipGetLastError();                                                    \
+    if (_e != hipSuccess) throw sg::SgError(SG_E_DEVICE, std::string("launch " name ": ") + hipGetErrorString(_e)); \
   } while (0)
 
 namespace sg {

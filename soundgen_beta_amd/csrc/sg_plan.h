@@ -88,7 +88,27 @@ struct Slice {
   int64_t c0, c1;    // finalize tiles (fast path, copy_tiles)
 };
 
-struct Batch {
+// What a plan reports of its calls and its work. Neither the upload nor the launch
+// sequence reads it; it is all that a plan keeps of its Batch after
+// sg_plan_release_host.
+struct PlanReport {
+  // ---- per call ----
+  std::vector<int64_t> call_len, call_off;
+  std::vector<int32_t> call_status;
+  std::vector<int32_t> call_fp64;   // bouts of the call on the fp64 filter path
+  std::vector<double> call_rho;     // the largest conditioning estimate over the call's filtered bouts
+  std::vector<double> call_rho_noise;  // the same for the pre-filter noise of its filtered bouts
+  std::vector<std::string> call_msg;
+  int64_t total_out = 0;
+  // ---- stats ----
+  int64_t harm_samples = 0, harm_terms = 0, harm_amp_bytes = 0, fft_frames = 0;
+  double fft_flops = 0;                      // nominal 5 wl log2 wl per transform, every frame path
+  std::vector<double> call_rows, call_flops;  // per call: sine-bank (sample, row) terms, FFT flops
+  int64_t stft_bytes = 0, stft_samples = 0;  // sg_stft_ola: algorithmic bytes, trimmed output samples
+  double stft_flops = 0;                     // sg_stft_ola: nominal 5 wl log2 wl per transform
+};
+
+struct Batch : PlanReport {
   // draws_only: a planning pass that only consumes each call's random draws in the
   // reference's order and raises the errors that precede its last draw, emitting
   // nothing (sg_node's recording pass over one R stream: the per-sample work after a
@@ -188,22 +208,7 @@ struct Batch {
   std::vector<float> ustream;  // derived (finalize_spec)
   std::vector<SgUJob> ujobs;   // derived (finalize_spec)
   std::vector<double> elog2;        // derived: log2(k), k = 1..max nr
-  // ---- per call ----
-  std::vector<int64_t> call_len, call_off;
-  std::vector<int32_t> call_status;
-  std::vector<int32_t> call_fp64;   // bouts of the call on the fp64 filter path
-  std::vector<double> call_rho;     // the largest conditioning estimate over the call's filtered bouts
-  double rho_cur = 0;               // (the call being planned)
-  std::vector<double> call_rho_noise;  // the same for the pre-filter noise of its filtered bouts
-  double rho_noise_cur = 0;
-  std::vector<std::string> call_msg;
-  int64_t total_out = 0;
-  // ---- stats ----
-  int64_t harm_samples = 0, harm_terms = 0, harm_amp_bytes = 0, fft_frames = 0;
-  double fft_flops = 0;                      // nominal 5 wl log2 wl per transform, every frame path
-  std::vector<double> call_rows, call_flops;  // per call: sine-bank (sample, row) terms, FFT flops
-  int64_t stft_bytes = 0, stft_samples = 0;  // sg_stft_ola: algorithmic bytes, trimmed output samples
-  double stft_flops = 0;                     // sg_stft_ola: nominal 5 wl log2 wl per transform
+  double rho_cur = 0, rho_noise_cur = 0;  // call_rho, call_rho_noise of the call being planned
 };
 
 // Plan one generateHarmonics() call; the finalized syllable is written at

@@ -355,6 +355,67 @@ def test_plan_uploaded_pipeline_byte_equal():
         p.close()
 
 
+_RELEASE_16K = dict(sylLen=300, samplingRate=16000, temperature=0, addSilence=0, noiseAnchors=None)
+RELEASE_CASES = [
+    # a filtered bout on the fp64 path whose subharmonic regime changes inside the syllable: its epochs
+    # crossfade, so the syllable's maximum needs the fp64 crossfade maxima (sg_piece_max_hp)
+    ("fp64_crossfade", 2, dict(_RELEASE_16K, pitchAnchors=[250, 450], nonlinBalance=100, subFreq=150, subDep=100,
+                               shortestEpoch=50,
+                               formants={"f1": {"time": 0, "freq": 800, "amp": 30, "width": 100},
+                                         "f2": {"time": 0, "freq": 1500, "amp": 30, "width": 120}})),
+    ("fp32_plain", 1, dict(_RELEASE_16K, pitchAnchors=[180, 240], formants=None)),
+]
+
+
+@pytest.mark.parametrize("name,policy,args", RELEASE_CASES, ids=[c[0] for c in RELEASE_CASES])
+def test_execute_after_release_host_equals_before(oracle, name, policy, args):
+    """An uploaded plan executes the same bytes before and after release_host():
+    the launch sequence reads nothing of the host plan. Every buffer starts as NaN,
+    so a kernel that ran only before the release shows."""
+    import torch
+    from soundgen_beta_amd import batch, native
+    from test_spectral_cpu import N, U
+    L = native.lib()
+    assert L.sg_set_fp64_policy(policy, 100.0) == 0
+    try:
+        plan = batch.Plan([{"kind": "soundgen", "args": args, "normals": N, "uniforms": U}], native.default_context(0))
+        assert plan.status[0] == 0, plan.message(0)
+        assert (plan.precision()[2] > 0) == (policy == 2)  # fp64 tasks exist
+        plan.upload()
+    finally:
+        L.sg_set_fp64_policy(1, native.HP_RHO_DEFAULT)
+    sptr = torch.cuda.current_stream().cuda_stream
+    before = torch.full((max(plan.total, 1),), float("nan"), dtype=torch.float32, device="cuda")
+    after = torch.full_like(before, float("nan"))
+    plan.execute(before.data_ptr(), sptr)
+    torch.cuda.synchronize()
+    plan.release_host()
+    plan.execute(after.data_ptr(), sptr)
+    torch.cuda.synchronize()
+    assert torch.equal(before.view(torch.int32), after.view(torch.int32))  # bytes, padding between calls included
+    # a plan released before its first execute: no cell of its arena holds an earlier execute's value
+    L.sg_set_fp64_policy(policy, 100.0)
+    try:
+        fresh = batch.Plan([{"kind": "soundgen", "args": args, "normals": N, "uniforms": U}], native.default_context(0))
+        fresh.upload()
+    finally:
+        L.sg_set_fp64_policy(1, native.HP_RHO_DEFAULT)
+    fresh.release_host()
+    first = torch.full_like(before, float("nan"))
+    fresh.execute(first.data_ptr(), sptr)
+    torch.cuda.synchronize()
+    fresh.close()
+    assert torch.equal(before.view(torch.int32), first.view(torch.int32))
+    ref = oracle.soundgen(normals=N, uniforms=U, **args)
+    o, n = int(plan.offsets[0]), int(plan.lengths[0])
+    assert torch.isfinite(after[o:o + n]).all()
+    assert n == len(ref)
+    r = _rms(before[o:o + n].cpu().numpy(), ref)
+    print(name, "rms", r)
+    assert r <= TOL, (name, r)
+    plan.close()
+
+
 def test_execute_plans_equals_per_plan_execute():
     """sg_execute_plans (several uploaded plans as one batch, the harmonic chains of
     later plans overlapping the spectral phases of earlier ones on the context's

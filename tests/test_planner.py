@@ -2,6 +2,8 @@
 does all integer bookkeeping of generateHarmonics() — glottal cycles, gcLen,
 subharmonic epochs, kept rows, crossFade zero-crossing trims, fades — and
 must agree with the oracle sample-for-sample (bit-exact lengths)."""
+import shutil
+
 import numpy as np
 import pytest
 
@@ -290,3 +292,78 @@ def test_host_cache_trim_between_plans():
     q = batch.Plan(calls, None)
     assert np.array_equal(q.lengths, want[0]) and np.array_equal(q.offsets, want[1]) and q.stats() == want[2]
     q.close()
+
+
+# The arena's sections in order with the bytes of one element, as this test states them (not read
+# from sg_arena.h): a section holds count elements plus its extra bytes, starts on a multiple of
+# 256 B and takes at least 256 B.
+ARENA_ELEM = [
+    ("segs", 48), ("epochs", 104), ("knots", 8), ("amps", 4), ("ampcols", 80), ("ampjobs", 96), ("ampsrc", 4),
+    ("tasks", 128), ("tall", 4), ("tlong", 4), ("tshort", 4), ("tallp", 4), ("srun", 4), ("trun", 4), ("thp", 4),
+    ("fin_tiles_hp", 48), ("W64", 8), ("fh", 8), ("frames64", 32), ("frames64_tab", 8), ("roots64", 8),
+    ("roots64_wl", 4), ("roots64_off", 8), ("pieces", 112), ("syls", 256), ("syl_tiles", 48), ("copy_tiles", 64),
+    ("ptiles", 48), ("cknots", 8), ("W", 4), ("taskmax", 4), ("ptilemax", 4), ("maxes", 4), ("geoms", 264),
+    ("frames", 24), ("fgroups", 16), ("olas", 80), ("olatiles", 16), ("olasegs", 40), ("olatilemax", 4),
+    ("olamax", 4), ("items", 112), ("mixes", 144), ("mixtiles", 16), ("eterms", 48), ("ecols", 8), ("envjobs", 40),
+    ("envtasks", 8), ("elog2", 8), ("fl", 4), ("fs", 4)]
+ARENA_EXTRA = {"amps": 64 * 4, "fs": 256}
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+def test_arena_sections_layout_and_checked_copy(tmp_path):
+    """The arena table (sg_arena.h) on hand-filled batches, from a stand-alone g++ program that
+    needs no HIP runtime (tests/cpp/arena_layout.cpp): every section's offset and size follow from
+    its printed count, this test's element sizes and the slack rules; the counts follow from the
+    sizes the program gave its arrays; a copy of one element too many is refused by name."""
+    import os
+    import subprocess
+    here = os.path.dirname(os.path.abspath(__file__))
+    csrc = os.path.join(here, "..", "soundgen_beta_amd", "csrc")
+    exe = str(tmp_path / "arena_layout")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-I" + csrc, "-I" + os.path.join(here, "..", "include"),
+                    os.path.join(here, "cpp", "arena_layout.cpp"), os.path.join(csrc, "sg_scratch.cpp"),
+                    "-o", exe, "-lpthread"], check=True)
+    lines = subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split("\n")
+    runs, copies = [], []
+    for ln in lines:
+        w = ln.split()
+        if not w:
+            continue
+        if w[0] == "run":
+            runs.append([])
+        elif w[0] == "copy":
+            copies.append(w[1:])
+        else:
+            runs[-1].append((w[0], int(w[1])) if w[0] == "total" else (w[0], int(w[1]), int(w[2]), int(w[3])))
+    assert len(runs) == 3
+    ntask = 4 + 2 + 7
+    fl_want = [700, 700 + 260, 700 + 50 + 345]  # uploaded floats, envelope area, uniform area
+    for k, rows in enumerate(runs):
+        *secs, total = rows
+        assert [s[0] for s in secs] == [n for n, _ in ARENA_ELEM]  # the declared order
+        end = 0
+        for (name, off, nbytes, count), (_, elem) in zip(secs, ARENA_ELEM):
+            assert off % 256 == 0 and off == end, (k, name)  # aligned, after the previous one, no gap
+            want = count * elem + ARENA_EXTRA.get(name, 0)
+            assert nbytes == max(256, (want + 255) // 256 * 256), (k, name)
+            if count == 0 and name not in ARENA_EXTRA:
+                assert nbytes == 256, name
+            end = off + nbytes
+        assert total == ("total", end) and secs[-1][0] == "fs"
+        n = {s[0]: s[3] for s in secs}
+        # the counts the sizes of the hand-filled arrays give
+        assert n["segs"] == 5 + 9 + 3 and n["tasks"] == ntask and n["eterms"] == 31  # two blocks and a tail
+        assert all(n[c] == ntask for c in ("tall", "tlong", "tshort", "tallp", "thp", "taskmax"))
+        assert n["srun"] == n["trun"] == ntask + 1
+        assert n["frames"] == 10 + 21 and n["olatilemax"] == 17 + 9 and n["roots64"] == 2 * 70
+        assert n["ptilemax"] == n["ptiles"] == 13 and n["maxes"] == n["syls"] == 5 and n["olamax"] == n["olas"] == 6
+        assert n["syl_tiles"] == 8 and n["amps"] == 1000 and n["fs"] == 2001 and n["W"] == 4099
+        assert [c for c in n if n[c] == 0] == ["ampsrc", "fh", "copy_tiles", "cknots", "envjobs", "envtasks"]
+        assert n["fl"] == fl_want[k]
+    assert len({r[-1] for r in runs}) == 3
+    # as many elements as a section holds fit; one more, or the same behind an offset, is refused
+    assert [c[:2] for c in copies] == [["ptiles", "fits"], ["ptiles", "refused"], ["frames", "fits"],
+                                       ["frames", "refused"], ["cknots", "fits"], ["cknots", "refused"]]
+    assert int(copies[0][2]) == 13 * 48 and int(copies[2][2]) == 21 * 24 and int(copies[4][2]) == 0
+    for c in copies[1::2]:
+        assert int(c[2]) == -5 and c[0] in " ".join(c[3:])  # SG_E_DEVICE, the message names the section
