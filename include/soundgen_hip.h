@@ -624,14 +624,18 @@ int sg_pitch_candidates_batch(sg_ctx* ctx, const float* d_wave, const int64_t* o
 /* analyze(): sg_pitch_candidates plus the tail behind the candidates (an additive
  * extension of ABI 5; R/analyze.R:576-707, R/utilities_pitch_postprocessing.R): the
  * prior, findVoicedSegments, pathfinder per voiced segment (interpolate, pathfinding
- * 'none' / 'fast', snake), medianSmoother and the final columns. p: as for
+ * 'none' / 'fast' / 'exact', snake), medianSmoother and the final columns. p: as for
  * sg_pitch_candidates. priorMean / priorSD (semitones): the prior applies when both are
  * numbers (NaN = not numeric: no prior; SG_E_ARG unless positive). minVoicedCands: NaN
  * = 'autom' (also taken when < 1 or above the number of methods). shortestSyl,
  * shortestPause in ms (shortestPause >= 0). interpolWin: a whole number of frames (<= 0:
  * no interpolation). certWeight in [0, 1]. snakeStep <= 0 or NaN: no snake. smooth <= 0
  * or NaN: no smoothing. pathfinding: 0 'none', 1 'fast', 2 'slow' (SG_E_UNSUPPORTED:
- * simulated annealing on R's random stream is not built). smoothVars: bit 0 'pitch', bit
+ * simulated annealing on R's random stream is not built), 3 'exact' (not in the
+ * reference: the path that minimises the reference's own costPerPath(), the cost 'slow'
+ * anneals, found by dynamic programming over a segment's frames; deterministic, no random
+ * stream; the tail's workspace grows by 2 + 3 nCands doubles per frame); any other value
+ * is SG_E_ARG. smoothVars: bit 0 'pitch', bit
  * 1 'dom'. SG_E_UNSUPPORTED also for interpolWin or half the smoothing window above 64
  * frames and for 0 < snakeStep < 0.005. */
 typedef struct sg_analyze_params_full {
@@ -673,6 +677,18 @@ int sg_analyze_batch(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, c
  * are read. */
 int sg_pitch_path(sg_ctx* ctx, const double* table, int32_t frames, int64_t len, const sg_analyze_params_full* p,
                   double* out);
+/* sg_pitch_path plus the list of the sound's voiced segments (an additive extension of ABI
+ * 5): *n_segments of them (at most `frames`), 4 doubles each in `segments` (room for 4 *
+ * frames doubles): the first and the last frame (1-based), nrow (the largest number of
+ * candidates in a frame, after interpolation: the rows left when the all-NA rows are
+ * dropped) and the value costPerPath() (R/utilities_pitch_postprocessing.R:347-372)
+ * gives for the path handed to the snake: certWeight * mean(|path - centre of gravity|) +
+ * (1 - certWeight) * mean(costJumps(path[f], path[f + 1])), both means with na.rm = TRUE;
+ * NaN where a mean has no term (a one-frame segment, or no two neighbouring frames with a
+ * path value). Any pathfinding sg_pitch_path takes; for a one-row segment the cost of its
+ * only path. `out` is what sg_pitch_path gives, bit for bit. */
+int sg_pitch_path_costs(sg_ctx* ctx, const double* table, int32_t frames, int64_t len, const sg_analyze_params_full* p,
+                        double* out, double* segments, int32_t* n_segments);
 /* analyze(summary = TRUE) (an additive extension of ABI 5; R/analyze.R:770-796): one row
  * of SG_ANALYZE_SUMMARY_COLS doubles per sound from its finished table: duration (s: the
  * sound's len / samplingRate), voiced (the proportion of voiced frames), then <var>_mean,

@@ -997,7 +997,7 @@ def pitch_matrices(table):
 # ------------------------------------------- analyze(): the tail behind the candidates
 SMOOTH_VARS = ("pitch", "dom")
 TRACK_COLUMNS = ("pitch", "amplVoiced", "voiced", "harmonics")  # the device table's last four
-PATHFINDING = ("none", "fast", "slow")
+PATHFINDING = ("none", "fast", "slow", "exact")  # the index is sg_analyze_params_full.pathfinding; 'exact' is not in the reference
 PATH_MAX_WIN = 64  # interpolWin and floor(smoothing_ww / 2) on the GPU (kPathMaxWin)
 SNAKE_MIN_STEP = 0.005  # the smallest snakeStep the GPU takes (its iterations are capped by range / snakeStep * 2)
 _SLOW = "pathfinding = 'slow' is simulated annealing through optim() on R's random stream: not built"
@@ -1179,6 +1179,89 @@ def pathfinding_fast(C, A, cog, certWeight, tr):
     return fwd if costF < costB else bwd
 
 
+def _pick_none(C, cog, tr):
+    """'none' (:110-113) as indices: which.min(|cand - centre of gravity|) per frame, None for an empty frame."""
+    picks = []
+    for f in range(len(C)):
+        if not C[f]:
+            picks.append(None)
+            continue
+        d = [abs(v - cog[f]) for v in C[f]]
+        k = _which(d, False)
+        _trace_pick(d, C[f], k, False, tr["choice"])
+        picks.append(k)
+    return picks
+
+
+def cost_per_path(C, cog, picks, certWeight):
+    """costPerPath(), :347-372, of the path that takes candidate picks[f] (0-based; None: no
+    value, which both mean(..., na.rm = TRUE) leave out) of the packed, sorted log2
+    candidates C[f]: certWeight * mean(|cand - cog|) + (1 - certWeight) * mean(costJumps of
+    neighbouring frames). NaN where a mean has no term, as in the reference."""
+    n = len(C)
+    v = [math.nan if picks[f] is None else C[f][picks[f]] for f in range(n)]
+    cert = [abs(v[f] - cog[f]) for f in range(n) if not math.isnan(v[f])]
+    jump = [cost_jumps(v[f], v[f + 1]) for f in range(n - 1) if not (math.isnan(v[f]) or math.isnan(v[f + 1]))]
+    return certWeight * _mean(cert) + (1 - certWeight) * _mean(jump)
+
+
+def pathfinding_exact(C, cog, certWeight, tr):
+    """pathfinding = 'exact', which the reference does not have: the picks (0-based indices,
+    None for an empty frame) of the path that minimises costPerPath() (:347-372), the cost
+    that 'slow' anneals, over the packed, sorted log2 candidates C of a segment of n >= 2
+    frames. n_c frames have a candidate and n_j pairs of neighbouring frames both have one:
+    the denominators of the reference's two means, which do not depend on the path. With wc =
+    certWeight / n_c and wj = (1 - certWeight) / n_j the cost of a path is a sum along the
+    chain, minimised by the recursion (in this order of operations, as sg_path.h's)
+        D(f, i) = wc |C[f][i] - cog[f]|                      in the first frame of a run
+        D(f, i) = wc |C[f][i] - cog[f]| + min_k (D(f - 1, k) + wj costJumps(C[f-1][k], C[f][i]))
+    the lowest k winning ties; at the last frame of every maximal run of non-empty frames
+    the lowest i with the least D is taken and the chosen k are followed back. n_j = 0 (every
+    path costs NaN in the reference): the picks of 'none'. tr["exact"] receives every
+    minimum taken, (the winner, the best of a different pitch value)."""
+    tr.setdefault("exact", [])
+    n = len(C)
+    n_c = sum(1 for f in C if f)
+    n_j = sum(1 for f in range(n - 1) if C[f] and C[f + 1])
+    if n_j == 0:
+        tr.setdefault("choice", [])
+        return _pick_none(C, cog, tr)
+    wc, wj = certWeight / n_c, (1 - certWeight) / n_j
+    D, B = [None] * n, [None] * n
+    for f in range(n):
+        if not C[f]:
+            continue
+        D[f], B[f] = [], []
+        for v in C[f]:
+            node = wc * abs(v - cog[f])
+            if f == 0 or not C[f - 1]:
+                D[f].append(node)
+                B[f].append(-1)
+                continue
+            t = [D[f - 1][k] + wj * cost_jumps(C[f - 1][k], v) for k in range(len(C[f - 1]))]
+            k = _which(t, False)
+            _trace_pick(t, C[f - 1], k, False, tr["exact"])
+            D[f].append(node + t[k])
+            B[f].append(k)
+    picks = [None] * n
+    at = -1
+    for f in range(n - 1, -1, -1):
+        if not C[f]:
+            at = -1
+            continue
+        if at < 0:                                                            # the last frame of a run
+            at = _which(D[f], False)
+            _trace_pick(D[f], C[f], at, False, tr["exact"])
+        picks[f] = at
+        at = B[f][at]
+    return picks
+
+
+def _picks_of(C, path):
+    """The index of each path value among its frame's candidates (the first of equal ones); None for NaN."""
+    return [None if math.isnan(p) else C[f].index(p) for f, p in enumerate(path)]
+
+
 def pathfinder_numpy(pitchCands, pitchCert, certWeight=0.5, pathfinding="fast", interpolWin=3, interpolTol=0.05,
                      interpolCert=0.3, snakeStep=0.05, _trace=None):
     """pathfinder(), R/utilities_pitch_postprocessing.R:28-132, for one voiced segment.
@@ -1187,10 +1270,14 @@ def pathfinder_numpy(pitchCands, pitchCert, certWeight=0.5, pathfinding="fast", 
     puts NA last and all-NA rows are dropped, so nrow is the largest count of a frame).
     Returns the pitch (Hz) per frame. The stated difference (see analyze_numpy): a frame
     that still has no candidate after interpolation keeps NaN, every other frame keeps its
-    aligned choice, and the snake is not run on that segment. _trace (a dict) receives the
-    sides (a, b) of the discrete comparisons."""
+    aligned choice, and the snake is not run on that segment. pathfinding = 'exact' is not in
+    the reference: pathfinding_exact(), the minimum of the reference's costPerPath(), in the
+    place of 'fast'. _trace (a dict) receives the sides (a, b) of the discrete comparisons
+    (`exact`: the minima of pathfinding_exact), and C, cog (the packed, sorted log2 candidates
+    and the centres of gravity), picks (the index taken per frame, None without a value)
+    and cost (cost_per_path of the path handed to the snake)."""
     tr = _trace if _trace is not None else {}
-    for k in ("band", "start", "choice", "fb", "maxiter", "delta", "force"):
+    for k in ("band", "start", "choice", "fb", "maxiter", "delta", "force", "exact"):
         tr.setdefault(k, [])
     tr.update(interpolated=0, direction=None, iterations=0, rows=0)
     if pathfinding == "slow":
@@ -1218,20 +1305,21 @@ def pathfinder_numpy(pitchCands, pitchCert, certWeight=0.5, pathfinding="fast", 
         o = sorted(range(len(C[f])), key=lambda k: C[f][k])
         C[f], A[f] = [C[f][k] for k in o], [A[f][k] for k in o]
     tr["rows"] = max(len(f) for f in C)
+    tr.update(C=C, cog=cog)
     if tr["rows"] <= 1:                                                       # :87-89
+        tr["picks"] = [0 if f else None for f in C]
+        tr["cost"] = cost_per_path(C, cog, tr["picks"], certWeight)
         return [2.0 ** f[0] if f else math.nan for f in C]
     if n >= 2 and pathfinding == "fast":                                      # :93-100
         path = pathfinding_fast(C, A, cog, certWeight, tr)
-    else:                                                                     # :110-113
-        path = []
-        for f in range(n):
-            if not C[f]:
-                path.append(math.nan)
-                continue
-            d = [abs(v - cog[f]) for v in C[f]]
-            k = _which(d, False)
-            _trace_pick(d, C[f], k, False, tr["choice"])
-            path.append(C[f][k])
+        tr["picks"] = _picks_of(C, path)
+    else:
+        if n >= 2 and pathfinding == "exact":                                 # not in the reference
+            tr["picks"] = pathfinding_exact(C, cog, certWeight, tr)
+        else:                                                                 # :110-113
+            tr["picks"] = _pick_none(C, cog, tr)
+        path = [math.nan if k is None else C[f][k] for f, k in enumerate(tr["picks"])]
+    tr["cost"] = cost_per_path(C, cog, tr["picks"], certWeight)
     if _num(snakeStep) and snakeStep > 0 and all(len(f) for f in C):          # snake(), :419-475
         flat = [v for f in C for v in f]
         q = (max(flat) - min(flat)) / snakeStep * 2                           # :426-427
@@ -1439,6 +1527,9 @@ def analyze_numpy(x, samplingRate=None, silence=0.04, windowLength=50, step=None
     (including the backward pass from a NaN median: no start, the last frame NaN,
     cost_pitchJump 0), and the snake is not run on that segment (in the reference its
     first force_new is NA and it breaks at once).
+    Added to the reference: pathfinding = 'exact' (pathfinding_exact(): the path that
+    minimises the reference's own costPerPath(), which 'slow' approximates by annealing;
+    deterministic, by dynamic programming).
     Out of scope: pathfinding = 'slow' (simulated annealing through optim() on R's random
     stream) and smoothVars outside ('pitch', 'dom') raise NotImplementedError, as do the
     plots; the columns pitchAutocor / pitchCep / pitchSpec (:659-667, as.numeric of
@@ -1572,7 +1663,9 @@ def analyze(x, samplingRate=None, silence=0.04, windowLength=50, step=None, over
     launch sequence (sg_anl_path: one 64-lane workgroup per sound; sg_anl_harm). The
     quirks kept, the one stated difference from the reference and what is out of scope
     (pathfinding = 'slow', pitchAutocor / pitchCep / pitchSpec, formants, plots, savePath)
-    are listed at analyze_numpy(), which this is compared against. plot defaults to False;
+    are listed at analyze_numpy(), which this is compared against. pathfinding = 'exact' is
+    not in the reference: the path that minimises its costPerPath() (pathfinding_exact();
+    sg_anl_path_exact), which 'slow' approximates; path_costs() reports what a path costs. plot defaults to False;
     True raises (with summary=True too, before anything runs). summary=True (R/analyze.R:
     770-796) returns the sound's summary row instead, a dict of the 44 floats named by
     SUMMARY_COLUMNS (see summarize_table_numpy): sg_anl_summary makes it from the table in
@@ -1678,8 +1771,26 @@ def pitch_path(table, step, samplingRate, pitchMethods=PITCH_DEFAULT_METHODS, pi
     from a caller-given pitch_candidates()-shaped table (a host dict; a *Cand / *Cert
     group that is absent counts as all NaN). Returns a copy with pitch, voiced, amplVoiced
     added, HNR in dB, dom smoothed, the quartiles blanked; harmonics is all NaN."""
+    return _pitch_path(table, step, samplingRate, locals(), device, False)
+
+
+def path_costs(table, step, samplingRate, pitchMethods=PITCH_DEFAULT_METHODS, pitchFloor=75, pitchCeiling=3500,
+               priorMean="default", priorSD=6, minVoicedCands="autom", shortestSyl=20, shortestPause=60, interpolWin=3,
+               interpolTol=0.3, interpolCert=0.3, pathfinding="fast", certWeight=.5, snakeStep=0.05, smooth=1,
+               smoothVars=SMOOTH_VARS, device=0):
+    """pitch_path() plus what the pathfinder's choice cost (sg_pitch_path_costs): (table,
+    segments), the table as pitch_path() returns it and, per voiced segment in order, a
+    dict of start_frame and end_frame (1-based), rows (the largest number of candidates in
+    a frame after interpolation) and cost: the reference's costPerPath() (cost_per_path())
+    of the path handed to the snake, NaN where it is NaN in the reference (a one-frame
+    segment; no two neighbouring frames with a value). Any pathfinding that pitch_path()
+    takes: the difference between 'fast' and 'exact' is what 'fast' leaves on the table."""
+    return _pitch_path(table, step, samplingRate, locals(), device, True)
+
+
+def _pitch_path(table, step, samplingRate, a, device, costs):
     t = {k: np.array(v, float) for k, v in table.items()}
-    s = _path_settings(t, step, samplingRate, locals())
+    s = _path_settings(t, step, samplingRate, a)
     frames, nC = len(t["ampl"]), s["nCands"]
     length = _path_length(t, samplingRate)
     m = np.full((frames, NFIXED + 6 * nC), math.nan)
@@ -1694,14 +1805,22 @@ def pitch_path(table, step, samplingRate, pitchMethods=PITCH_DEFAULT_METHODS, pi
     ctx = native.default_context(device)
     dp = C.POINTER(C.c_double)
     m = np.ascontiguousarray(m)
-    _check(native.lib().sg_pitch_path(ctx.ptr, m.ctypes.data_as(dp), frames, int(length), C.byref(P), out.ctypes.data_as(dp)),
-           ctx.ptr)
+    if costs:
+        seg, nseg = np.zeros(4 * max(frames, 1)), C.c_int32()
+        _check(native.lib().sg_pitch_path_costs(ctx.ptr, m.ctypes.data_as(dp), frames, int(length), C.byref(P),
+                                                out.ctypes.data_as(dp), seg.ctypes.data_as(dp), C.byref(nseg)), ctx.ptr)
+    else:
+        _check(native.lib().sg_pitch_path(ctx.ptr, m.ctypes.data_as(dp), frames, int(length), C.byref(P),
+                                          out.ctypes.data_as(dp)), ctx.ptr)
     o = out[:frames * (m.shape[1] + 4)].reshape(frames, m.shape[1] + 4)
     for i, k in enumerate(COLUMNS):
         t[k] = o[:, i].copy()
     for i, k in enumerate(TRACK_COLUMNS):
         t[k] = o[:, m.shape[1] + i].copy()
     t["voiced"] = t["voiced"] == 1
+    if costs:
+        return t, [dict(start_frame=int(v[0]), end_frame=int(v[1]), rows=int(v[2]), cost=float(v[3]))
+                   for v in seg[:4 * nseg.value].reshape(-1, 4)]
     return t
 
 

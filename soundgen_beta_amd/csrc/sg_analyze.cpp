@@ -287,7 +287,8 @@ PathPars track_path_pars(const sg_analyze_params_full& p, double* smooth) {
   P.cols = kAnlFixed + 6 * P.nCands + kPathCols;
   if (p.pathfinding == 2)
     throw SgError(SG_E_UNSUPPORTED, "analyze: pathfinding = 'slow' (simulated annealing on R's random stream) is not built");
-  if (p.pathfinding < 0 || p.pathfinding > 2) throw SgError(SG_E_ARG, "analyze: pathfinding must be 0 'none', 1 'fast' or 2 'slow'");
+  if (p.pathfinding < 0 || p.pathfinding > 3)
+    throw SgError(SG_E_ARG, "analyze: pathfinding must be 0 'none', 1 'fast', 2 'slow' or 3 'exact'");
   P.pathfinding = p.pathfinding;
   if (p.smoothVars & ~3) throw SgError(SG_E_ARG, "analyze: smoothVars must be a subset of 'pitch', 'dom'");
   // :598-605 the prior, when priorMean and priorSD are both numbers
@@ -479,7 +480,7 @@ void anl_sweep_bytes(const SweepPlan& W, const int64_t* lengths, int64_t n_calls
       persist[f] += F * (S.cols - kPathCols) * (int64_t)sizeof(double);
       if (W.store_group[r] >= 0) ++users[W.store_group[r]];
     }
-    bytes[2] = std::max(bytes[2], F * (S.cols + path_stride(S.nCands)) * (int64_t)sizeof(double));
+    bytes[2] = std::max(bytes[2], F * (S.cols + path_scratch(S.nCands, S.path.pathfinding)) * (int64_t)sizeof(double));
   }
   for (int f = 0; f < W.n_frame; ++f) bytes[0] = std::max(bytes[0], persist[f]);
   for (int64_t r = 0; r < n_rows; ++r)

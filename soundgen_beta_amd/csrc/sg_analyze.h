@@ -106,8 +106,10 @@ void analyze_device(const AnlSetup& S, const T* d_x, const int64_t* offsets, con
                     double* d_out, const int64_t* out_off, int32_t* frames_out, hipStream_t s, double* kernel_ms,
                     const PitchSetup* pitch = nullptr, const TrackSetup* track = nullptr, double* d_summary = nullptr,
                     double* summary_ms = nullptr);
-// the path stage alone on n rows of P.cols doubles already on the device (sg_pitch_path)
-void path_device(const PathPars& P, int frames, int hw, double* d_rows, hipStream_t s, double* kernel_ms);
+// the path stage alone on n rows of P.cols doubles already on the device (sg_pitch_path); d_segs: nullptr, or
+// path_seg_cells(frames) doubles on the device for the sound's segment list (sg_pitch_path_costs)
+void path_device(const PathPars& P, int frames, int hw, double* d_rows, hipStream_t s, double* kernel_ms,
+                 double* d_segs = nullptr);
 
 // A parameter sweep of analyze(summary = TRUE) (sg_analyze_sweep): what the rows may share, decided from the
 // resolved setups alone. Groups are numbered by first appearance.

@@ -28,6 +28,9 @@
 //   sg_anl_path   one 64-lane workgroup per sound (sg::path_sound, sg_path.h): the prior,
 //                 findVoicedSegments, pathfinder per segment, medianSmoother, voiced /
 //                 amplVoiced, the blanked quartiles, HNR in dB
+//   sg_anl_path_exact  the same with pathfinding 'exact' (the minimum of costPerPath(), not in the
+//                 reference) and the segment list of sg_pitch_path_costs compiled in: launched in
+//                 sg_anl_path's place only for those two
 //   sg_anl_harm   one workgroup per frame with a pitch: the share of |X| above 1.25 *
 //                 pitch, in dB
 // and, where the caller asks for analyze(summary = TRUE) (R/analyze.R:770-796), behind them
@@ -44,6 +47,7 @@
 //                 autocorThres, autocorSmooth and nCands
 // and then, for all (row, sound) pairs of a chunk of rows in one launch each,
 //   sg_anl_sweep_path  sg::path_sound_at from the shared candidate table into the pair's own
+//   sg_anl_sweep_path_exact  the same for the pairs of the rows with pathfinding 'exact'
 //   sg_anl_sweep_harm  sg_anl_harm on grid (frames, rows of the chunk)
 // and sg_anl_summary once per row. A pair's cells are those of sg_analyze_summary_batch bit for bit.
 // On the host the two sequences (analyze_device, analyze_sweep) share what they decide alike: the frames of a
@@ -633,11 +637,13 @@ static_assert(sg::kPathAmpl == sg::kAmpl && sg::kPathHNR == sg::kHNR && sg::kPat
               "sg_path.h names the columns of sg::AnlCol");
 
 constexpr int kPathT = 64;  // one wave per sound
+constexpr int kPathMaxW = 2 + 3 * sg::kAnlMaxCands;  // sg::path_width() at its largest
 
 struct PathSound {
   int64_t row0;  // first double of its table in the output buffer
   int64_t scr0;  // first double of its frames' scratch
   int32_t nf, hw;
+  int64_t seg0;  // first double of its segment list (sg::path_seg_cells), where the launch has one
 };
 
 struct WgSync {
@@ -655,6 +661,34 @@ __global__ __launch_bounds__(kPathT) void sg_anl_path(const PathSound* __restric
   const PathSound S = snds[blockIdx.x];
   if (S.nf <= 0) return;  // workgroup-uniform
   sg::path_sound(P, S.nf, S.hw, out + S.row0, scr + S.scr0, (int)threadIdx.x, kPathT, red, sh, WgSync());
+}
+
+// sg_anl_path with pathfinding 'exact' and the segment list compiled in (sg::kPathExact | sg::kPathSegs), a kernel of
+// its own so that sg_anl_path stays what it was: launched for 'exact' (the scratch is then sg::path_scratch()
+// doubles per frame: the back-pointers; D of two frames in dd) and for sg_pitch_path_costs (segs: the sounds'
+// segment lists, else nullptr)
+__global__ __launch_bounds__(kPathT) void sg_anl_path_exact(const PathSound* __restrict__ snds, sg::PathPars P,
+                                                            double* __restrict__ out, double* __restrict__ scr,
+                                                            double* __restrict__ segs) {
+  __shared__ double red[kPathT];
+  __shared__ double dd[2 * kPathMaxW];
+  __shared__ int64_t sh[3];
+  const PathSound S = snds[blockIdx.x];
+  if (S.nf <= 0) {  // workgroup-uniform
+    if (segs && threadIdx.x == 0) segs[S.seg0] = 0;
+    return;
+  }
+  sg::path_sound<WgSync, sg::kPathExact | sg::kPathSegs>(P, S.nf, S.hw, out + S.row0, scr + S.scr0, (int)threadIdx.x, kPathT,
+                                                         red, sh, WgSync(), dd, segs ? segs + S.seg0 : nullptr);
+}
+
+// the one of the two a launch needs
+void launch_path(dim3 grid, hipStream_t s, const PathSound* d_ps, const sg::PathPars& P, double* d_out, double* d_scr,
+                 double* d_segs) {
+  if (P.pathfinding == 3 || d_segs)
+    hipLaunchKernelGGL(sg_anl_path_exact, grid, dim3(kPathT), 0, s, d_ps, P, d_out, d_scr, d_segs);
+  else
+    hipLaunchKernelGGL(sg_anl_path, grid, dim3(kPathT), 0, s, d_ps, P, d_out, d_scr);
 }
 
 // `harmonics` (R/analyze.R:694-703) for the frame of a workgroup, its row of `cols` doubles at row and its |X| at z:
@@ -719,6 +753,23 @@ __global__ __launch_bounds__(kPathT) void sg_anl_sweep_path(const SweepPair* __r
   const sg::PathPars P = pars[R.row];
   sg::path_sound_at(P, R.nf, R.hw, cands + R.src0, P.cols - sg::kPathCols, work + R.dst0, work + R.scr0, (int)threadIdx.x,
                     kPathT, red, sh, WgSync());
+}
+
+// sg_anl_path_exact for a pair: the pairs of a chunk whose row has pathfinding 'exact'. Both kernels go over all
+// the pairs of a chunk (sg_anl_sweep_harm and the summary index them by row and sound); each is launched only for a
+// chunk that has a pair for it, and in a chunk that has both each gets a copy of the pairs in which the other's have
+// no frames.
+__global__ __launch_bounds__(kPathT) void sg_anl_sweep_path_exact(const SweepPair* __restrict__ pairs,
+                                                                  const sg::PathPars* __restrict__ pars,
+                                                                  const double* __restrict__ cands, double* __restrict__ work) {
+  __shared__ double red[kPathT];
+  __shared__ double dd[2 * kPathMaxW];
+  __shared__ int64_t sh[3];
+  const SweepPair R = pairs[blockIdx.x];
+  if (R.nf <= 0) return;  // workgroup-uniform
+  const sg::PathPars P = pars[R.row];
+  sg::path_sound_at<WgSync, sg::kPathExact>(P, R.nf, R.hw, cands + R.src0, P.cols - sg::kPathCols, work + R.dst0, work + R.scr0,
+                                            (int)threadIdx.x, kPathT, red, sh, WgSync(), dd);
 }
 
 // sg_anl_harm for frame blockIdx.x of the frame group under row blockIdx.y of the chunk; snds: any candidate
@@ -798,7 +849,7 @@ void check_setup(const sg::AnlSetup& A, const sg::PitchSetup* pitch) {
 // a row of the tail: the candidates' columns and sg_path.h's four, as the path's constants have it; `also`: what else
 // the caller requires
 void check_tail_row(const sg::PathPars& P, int cols, int nCands, bool also) {
-  if (P.cols != cols || cols != sg::kAnlFixed + 6 * nCands + sg::kPathCols || !also)
+  if (P.cols != cols || cols != sg::kAnlFixed + 6 * nCands + sg::kPathCols || sg::path_width(nCands) > kPathMaxW || !also)
     throw sg::SgError(SG_E_DEVICE, "analyze: the tail's setup leaves the row");
 }
 
@@ -968,11 +1019,11 @@ void analyze_device(const AnlSetup& A, const T* d_x, const int64_t* offsets, con
   const SpgSetup& P = A.spg;
   const int B = P.bins;
   std::vector<PathSound> ps(track ? n_calls : 0);
-  const int pstride = track ? path_stride(track->path.nCands) : 0;
+  const int pstride = track ? path_scratch(track->path.nCands, track->path.pathfinding) : 0;
   const FrameList L = list_frames(A, lengths, n_calls, [&](int64_t c, int nf, int64_t f0) {
     frames_out[c] = nf;
     if (track)  // the smoothing window is refused before anything is launched
-      ps[c] = PathSound{out_off[c], f0 * pstride, nf, track_hw(track->smooth, P.sr, lengths[c], nf)};
+      ps[c] = PathSound{out_off[c], f0 * pstride, nf, track_hw(track->smooth, P.sr, lengths[c], nf), 0};
   });
   std::vector<AnlSound> snds(n_calls);
   std::vector<SumSound> ss(d_summary ? n_calls : 0);
@@ -1011,7 +1062,7 @@ void analyze_device(const AnlSetup& A, const T* d_x, const int64_t* offsets, con
       const PathSound* d_ps = upload(db, ps, s);
       double* d_scr = db.get<double>((size_t)F * pstride);
       const double* d_lab = upload(db, track->lab, s);
-      hipLaunchKernelGGL(sg_anl_path, dim3((unsigned)n_calls), dim3(kPathT), 0, s, d_ps, track->path, d_out, d_scr);
+      launch_path(dim3((unsigned)n_calls), s, d_ps, track->path, d_out, d_scr, nullptr);
       HIPCHK(hipGetLastError());
       clk.stamp();  // 7: harmonics
       hipLaunchKernelGGL(sg_anl_harm, dim3((unsigned)F), dim3(kT), 0, s, d_fr, d_snd, d_Z, d_lab, B, A.cols, d_out);
@@ -1033,17 +1084,17 @@ template void analyze_device<double>(const AnlSetup&, const double*, const int64
                                      const int64_t*, int32_t*, hipStream_t, double*, const PitchSetup*, const TrackSetup*, double*,
                                      double*);
 
-void path_device(const PathPars& P, int frames, int hw, double* d_rows, hipStream_t s, double* kernel_ms) {
+void path_device(const PathPars& P, int frames, int hw, double* d_rows, hipStream_t s, double* kernel_ms, double* d_segs) {
   double ms = 0;
   StageClock clk(s, kernel_ms ? &ms : nullptr, 1);
   for (int k = 0; kernel_ms && k < kTrackStages; ++k) kernel_ms[k] = 0;
   if (frames <= 0) return;
   check_tail_row(P, P.cols, P.nCands, P.nCands >= 1 && P.nCands <= kAnlMaxCands && hw >= 0);
   DevBuf db;
-  const PathSound* d_ps = upload(db, std::vector<PathSound>(1, PathSound{0, 0, frames, hw}), s);
-  double* d_scr = db.get<double>((size_t)frames * path_stride(P.nCands));
+  const PathSound* d_ps = upload(db, std::vector<PathSound>(1, PathSound{0, 0, frames, hw, 0}), s);
+  double* d_scr = db.get<double>((size_t)frames * path_scratch(P.nCands, P.pathfinding));
   clk.stamp();
-  hipLaunchKernelGGL(sg_anl_path, dim3(1), dim3(kPathT), 0, s, d_ps, P, d_rows, d_scr);
+  launch_path(dim3(1), s, d_ps, P, d_rows, d_scr, d_segs);
   HIPCHK(hipGetLastError());
   clk.stamp();
   HIPCHK(hipStreamSynchronize(s));
@@ -1153,7 +1204,7 @@ void analyze_sweep(sg_ctx* ctx, const float* d_x, const int64_t* offsets, const 
     }
     // the tail: chunks of consecutive rows whose pair tables and scratch fit the cap, at least one row
     const int64_t cap_cells = std::max<int64_t>(1, cap / (int64_t)sizeof(double));
-    auto row_cells = [&](int64_t r) { return F * (W.S[r].cols + path_stride(W.S[r].nCands)); };
+    auto row_cells = [&](int64_t r) { return F * (W.S[r].cols + path_scratch(W.S[r].nCands, W.S[r].path.pathfinding)); };
     std::vector<size_t> chunk_end;
     int64_t work = 0, work_cells = 0;
     size_t first = 0;
@@ -1221,7 +1272,7 @@ void analyze_sweep(sg_ctx* ctx, const float* d_x, const int64_t* offsets, const 
       for (size_t k = k0; k < k1; ++k) {
         const int64_t r = frows[k];
         const TrackSetup& S = W.S[r];
-        const int ccols = S.cols - kPathCols, pstride = path_stride(S.nCands);
+        const int ccols = S.cols - kPathCols, pstride = path_scratch(S.nCands, S.path.pathfinding);
         const size_t i = (size_t)(std::find(cgs.begin(), cgs.end(), W.cand_group[r]) - cgs.begin());
         for (int64_t c = 0; c < n_calls; ++c) {
           SweepPair R;
@@ -1240,7 +1291,19 @@ void analyze_sweep(sg_ctx* ctx, const float* d_x, const int64_t* offsets, const 
       const SweepPair* d_pairs = upload(db, pairs, s);
       const dim3 gP((unsigned)pairs.size());
       if (F > 0) {
-        timed(kSwPath, [&]() { hipLaunchKernelGGL(sg_anl_sweep_path, gP, dim3(kPathT), 0, s, d_pairs, d_pars, d_cand, d_work); });
+        bool plain = false, exact = false;
+        for (size_t k = k0; k < k1; ++k) (W.S[frows[k]].path.pathfinding == 3 ? exact : plain) = true;
+        const SweepPair *d_plain = d_pairs, *d_exact = d_pairs;
+        if (plain && exact) {  // a copy for either kernel in which the other's pairs have no frames
+          std::vector<SweepPair> a = pairs, b = pairs;
+          for (size_t i = 0; i < pairs.size(); ++i) (W.S[pairs[i].row].path.pathfinding == 3 ? a : b)[i].nf = 0;
+          d_plain = upload(db, a, s);
+          d_exact = upload(db, b, s);
+        }
+        timed(kSwPath, [&]() {
+          if (plain) hipLaunchKernelGGL(sg_anl_sweep_path, gP, dim3(kPathT), 0, s, d_plain, d_pars, d_cand, d_work);
+          if (exact) hipLaunchKernelGGL(sg_anl_sweep_path_exact, gP, dim3(kPathT), 0, s, d_exact, d_pars, d_cand, d_work);
+        });
         timed(kSwHarm, [&]() {
           hipLaunchKernelGGL(sg_anl_sweep_harm, dim3((unsigned)F, (unsigned)(k1 - k0)), dim3(kT), 0, s, d_fr, d_zs, d_pairs,
                              (int)n_calls, d_Z, d_lab, B, d_work);
@@ -1336,16 +1399,19 @@ int sg_analyze_batch(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, c
   });
 }
 
-int sg_pitch_path(sg_ctx* ctx, const double* table, int32_t frames, int64_t len, const sg_analyze_params_full* p,
-                  double* out) {
+// sg_pitch_path (segments == nullptr) and sg_pitch_path_costs behind their argument checks
+static int pitch_path_run(sg_ctx* ctx, const char* who, const double* table, int32_t frames, int64_t len,
+                          const sg_analyze_params_full* p, double* out, double* segments, int32_t* n_segments) {
   return guarded(ctx, [&]() {
-    if (!ctx || !p || frames < 0 || len < 0 || (frames > 0 && (!table || !out)))
-      throw sg::SgError(SG_E_ARG, "sg_pitch_path: bad arguments");
+    if (!ctx || !p || frames < 0 || len < 0 || (frames > 0 && (!table || !out)) ||
+        (n_segments && frames > 0 && !segments))
+      throw sg::SgError(SG_E_ARG, std::string(who) + ": bad arguments");
     double smooth = 0;
     const sg::PathPars P = sg::track_path_pars(*p, &smooth);
     const int hw = sg::track_hw(smooth, p->p.a.samplingRate, len, frames);
+    if (n_segments) *n_segments = 0;
     if (frames == 0) return (int)SG_OK;
-    if (!(p->p.a.samplingRate > 0)) throw sg::SgError(SG_E_ARG, "sg_pitch_path: samplingRate must be positive");
+    if (!(p->p.a.samplingRate > 0)) throw sg::SgError(SG_E_ARG, std::string(who) + ": samplingRate must be positive");
     HIPCHK(hipSetDevice(ctx->device));
     const int in_cols = P.cols - sg::kPathCols;
     for (int32_t f = 0; f < frames; ++f) {  // the caller's rows, widened, staged in `out`
@@ -1354,10 +1420,30 @@ int sg_pitch_path(sg_ctx* ctx, const double* table, int32_t frames, int64_t len,
     }
     sg::DevBuf db;
     double* d_rows = sg::upload_sound(db, out, (int64_t)frames * P.cols, ctx->stream);
-    sg::path_device(P, frames, hw, d_rows, ctx->stream, ctx->profiling ? g_track_ms : nullptr);
+    double* d_segs = n_segments ? db.get<double>((size_t)sg::path_seg_cells(frames)) : nullptr;
+    sg::path_device(P, frames, hw, d_rows, ctx->stream, ctx->profiling ? g_track_ms : nullptr, d_segs);
     HIPCHK(hipMemcpy(out, d_rows, (size_t)frames * P.cols * sizeof(double), hipMemcpyDeviceToHost));
+    if (n_segments) {
+      std::vector<double> h((size_t)sg::path_seg_cells(frames));
+      HIPCHK(hipMemcpy(h.data(), d_segs, h.size() * sizeof(double), hipMemcpyDeviceToHost));
+      const int64_t n = (int64_t)h[0];
+      if (!(n >= 0 && n <= frames)) throw sg::SgError(SG_E_DEVICE, "analyze: the segment list leaves its buffer");
+      for (int64_t k = 0; k < n * sg::kPathSegCells; ++k) segments[k] = h[1 + k];
+      *n_segments = (int32_t)n;
+    }
     return (int)SG_OK;
   });
+}
+
+int sg_pitch_path(sg_ctx* ctx, const double* table, int32_t frames, int64_t len, const sg_analyze_params_full* p,
+                  double* out) {
+  return pitch_path_run(ctx, "sg_pitch_path", table, frames, len, p, out, nullptr, nullptr);
+}
+
+int sg_pitch_path_costs(sg_ctx* ctx, const double* table, int32_t frames, int64_t len, const sg_analyze_params_full* p,
+                        double* out, double* segments, int32_t* n_segments) {
+  if (!n_segments) return guarded(ctx, [&]() -> int { throw sg::SgError(SG_E_ARG, "sg_pitch_path_costs: bad arguments"); });
+  return pitch_path_run(ctx, "sg_pitch_path_costs", table, frames, len, p, out, segments, n_segments);
 }
 
 int sg_analyze_summary(sg_ctx* ctx, const double* table, int32_t frames, int32_t cols, int32_t nCands, int64_t len,

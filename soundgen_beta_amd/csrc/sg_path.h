@@ -1,10 +1,12 @@
 // sg_path.h — analyze()'s tail once every frame has its pitch candidates
 // (R/analyze.R:576-707, R/utilities_pitch_postprocessing.R): the prior, findVoicedSegments,
 // pathfinder (interpolate, pathfinding 'none' / 'fast', costJumps, snake, forcePerPath,
-// findGrad), medianSmoother and the final columns. The scalar routines are plain
+// findGrad), medianSmoother and the final columns; and pathfinding 'exact', which the
+// reference does not have: the minimum of its own costPerPath() (:347-372, what 'slow'
+// anneals towards) by dynamic programming, path_exact() below. The scalar routines are plain
 // functions; path_sound() drives them for one sound with `nl` cooperating lanes: the 64
 // lanes of sg_anl_path's workgroup on the device, one lane (and a sync that does nothing)
-// on the host (tests/cpp/path_pins.cpp). path_sound_at() is the same with the candidates in a
+// on the host (tests/cpp/path_pins.cpp, tests/cpp/path_exact_pins.cpp). path_sound_at() is the same with the candidates in a
 // table apart that it leaves untouched (a sweep's pairs, sg_anl_sweep_path;
 // tests/cpp/path_at_pins.cpp). No HIP header is needed on the host side, no dynamic memory
 // anywhere.
@@ -19,14 +21,22 @@
 // Sums over frames (the two path costs, mean(|force|)) are made by a scheme that depends
 // on nl alone: lane l adds its frames l, l + nl, ... in order, then every lane folds the
 // nl partial sums in lane order. A sound's result therefore does not depend on the launch.
+//
+// 'exact' needs path_width() more cells per frame, behind the nf * path_stride() cells of
+// the other modes (path_scratch() doubles per frame in all): the back-pointers of its
+// recursion. The only operation it makes across candidates is a minimum with a
+// lowest-index tie rule, which is associative, unlike the sums above: however the lanes
+// share the (i, k) pairs of a frame, the picks equal those of the one-lane host run.
 #pragma once
 #include <math.h>
 #include <stdint.h>
 
 #if defined(__HIPCC__)
 #define SG_PATH_HD __host__ __device__
+#define SG_PATH_CALL __attribute__((noinline))  // a call of its own: keeps the caller's registers what they were
 #else
 #define SG_PATH_HD
+#define SG_PATH_CALL
 #endif
 
 namespace sg {
@@ -55,7 +65,7 @@ struct PathPars {
   int noRequired;   // max(1, ceiling(shortestSyl / step))
   int nTolerated;   // floor(shortestPause / step)
   int interpolWin;  // 0: interpolate() is not called
-  int pathfinding;  // 0 'none', 1 'fast'
+  int pathfinding;  // 0 'none', 1 'fast', 3 'exact' (2, 'slow', is refused by the setup)
   int do_prior, smooth_pitch, smooth_dom;
   double shape, rate, lconst, prior_norm;  // lconst = shape log(rate) - lgamma(shape); prior_norm = max(dgamma(seq))
   double interpolTol, interpolCert, certWeight;
@@ -65,6 +75,14 @@ struct PathPars {
 
 SG_PATH_HD inline int path_width(int nCands) { return 2 + 3 * nCands; }
 SG_PATH_HD inline int path_stride(int nCands) { return 2 * path_width(nCands) + kPathSlots; }
+// doubles of scratch per frame of a sound: 'exact' keeps path_width() back-pointers per frame behind the rest
+SG_PATH_HD inline int path_scratch(int nCands, int pathfinding) {
+  return path_stride(nCands) + (pathfinding == 3 ? path_width(nCands) : 0);
+}
+// doubles of a sound's optional segment list: the count, then kPathSegCells per voiced segment (first frame, last
+// frame (1-based), nrow after the dropped rows, costPerPath() of the path handed to the snake)
+constexpr int kPathSegCells = 4;
+SG_PATH_HD inline int64_t path_seg_cells(int64_t nf) { return 1 + kPathSegCells * nf; }
 
 // to_dB(), R/utilities_math.R:37-39; a ratio <= 0 gives NaN as log10 does
 SG_PATH_HD inline double path_to_dB(double x) { return 10 * log10(x / (1 - x)); }
@@ -284,19 +302,144 @@ SG_PATH_HD inline double path_reduce(double v, int op, int lane, int nl, double*
   return r;
 }
 
+// The inner minimum of 'exact' for one candidate v of a frame: the k (lowest on ties) of the pc candidates c0[.] of
+// the frame before that minimises D0[k] + wj costJumps(c0[k], v), and that minimum
+SG_PATH_HD inline int path_exact_arg(const double* c0, const double* D0, int pc, double v, double wj, double* best) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  int bk = 0;
+  double bv = 0;
+  for (int k = 0; k < pc; ++k) {
+    const double t = D0[k] + wj * path_cost_jump(c0[k], v);
+    if (k == 0 || t < bv) {
+      bk = k;
+      bv = t;
+    }
+  }
+  *best = bv;
+  return bk;
+}
+
+// the lowest index of the least of D[0 .. cnt)
+SG_PATH_HD inline int path_exact_end(const double* D, int cnt) {
+  int b = 0;
+  for (int i = 1; i < cnt; ++i)
+    if (D[i] < D[b]) b = i;
+  return b;
+}
+
+// pathfinding 'exact' (not in the reference): the path that minimises costPerPath() (:347-372) over the n >= 2
+// frames of a segment at seg, sorted. With n_c frames that have a candidate and n_j neighbouring pairs of them (the
+// denominators of the reference's two mean(..., na.rm = TRUE)), wc = certWeight / n_c, wj = (1 - certWeight) / n_j:
+//   D(f, i) = wc |c[f][i] - cog[f]|                                                  in the first frame of a run
+//   D(f, i) = wc |c[f][i] - cog[f]| + min_k (D(f - 1, k) + wj costJumps(c[f-1][k], c[f][i]))   otherwise
+// the lowest k winning ties; at the last frame of every maximal run of non-empty frames the lowest i with the least D
+// is taken and the chosen k are followed back. Frames are sequential, one sync each; lane i of a frame has candidate
+// i. dd: 2 W doubles shared by the lanes (D of the frame before and of this one); bp: W cells per frame, the chosen
+// k. Returns false, with nothing written to the path, when n_j = 0 (every path costs NaN in the reference): the
+// caller then takes 'none'. Otherwise the path is in kSlotPath (NaN for a frame without candidates); the caller syncs.
+template <class Sync>
+SG_PATH_HD SG_PATH_CALL inline bool path_exact(double* seg, int S, int W, int n, double certWeight, double* bp, double* dd, int lane,
+                                  int nl, double* red, Sync& sync) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const int X = 2 * W;
+  double nc = 0, nj = 0;  // whole numbers: their sums do not depend on the order
+  for (int f = lane; f < n; f += nl)
+    if (seg[(int64_t)f * S + X + kSlotCnt] > 0) {
+      nc += 1;
+      if (f + 1 < n && seg[(int64_t)(f + 1) * S + X + kSlotCnt] > 0) nj += 1;
+    }
+  nc = path_reduce(nc, 0, lane, nl, red, sync);
+  nj = path_reduce(nj, 0, lane, nl, red, sync);
+  if (nj == 0) return false;
+  const double wc = certWeight / nc, wj = (1 - certWeight) / nj;
+  int prev = 0;  // candidates of the frame before
+  for (int f = 0; f < n; ++f) {
+    double* c = seg + (int64_t)f * S;
+    const int cnt = (int)c[X + kSlotCnt];
+    double* cur = dd + (f & 1) * W;
+    const double* old = dd + ((f & 1) ^ 1) * W;
+    if (lane == 0 && prev > 0 && cnt == 0) (c - S)[X + kSlotAux] = path_exact_end(old, prev);  // a run ends before f
+    for (int i = lane; i < cnt; i += nl) {
+      const double node = wc * fabs(c[i] - c[X + kSlotCog]);
+      double best = 0;
+      const int k = prev > 0 ? path_exact_arg(c - S, old, prev, c[i], wj, &best) : -1;
+      cur[i] = prev > 0 ? node + best : node;
+      bp[(int64_t)f * W + i] = k;
+    }
+    prev = cnt;
+    sync();
+  }
+  if (lane == 0) {
+    if (prev > 0) seg[(int64_t)(n - 1) * S + X + kSlotAux] = path_exact_end(dd + ((n - 1) & 1) * W, prev);
+    int at = -1;  // the candidate taken in the frame behind, if the run goes on
+    for (int f = n - 1; f >= 0; --f) {
+      double* c = seg + (int64_t)f * S;
+      if (!(c[X + kSlotCnt] > 0)) {
+        c[X + kSlotPath] = NAN;
+        at = -1;
+        continue;
+      }
+      if (at < 0) at = (int)c[X + kSlotAux];
+      c[X + kSlotPath] = c[at];
+      at = (int)bp[(int64_t)f * W + at];
+    }
+  }
+  return true;
+}
+
+// costPerPath() (:347-372) of the path in kSlotPath over the n frames of the segment at seg: certWeight mean(|path -
+// cog|) + (1 - certWeight) mean(costJumps(path[f], path[f + 1])), both means with na.rm = TRUE (a frame without a
+// path value, and a pair with one, are left out); NaN where a mean has no term, as in the reference. Every lane
+// gets it; the sums as the header's other sums over frames.
+template <class Sync>
+SG_PATH_HD SG_PATH_CALL inline double path_cost(const double* seg, int S, int W, int n, double certWeight, int lane, int nl, double* red,
+                                   Sync& sync) {
+  const int X = 2 * W;
+  double sc = 0, sj = 0, kc = 0, kj = 0;
+  for (int f = lane; f < n; f += nl) {
+    const double* c = seg + (int64_t)f * S;
+    const double p = c[X + kSlotPath];
+    if (p != p) continue;
+    sc += fabs(p - c[X + kSlotCog]);
+    kc += 1;
+    if (f + 1 >= n) continue;
+    const double q = (c + S)[X + kSlotPath];
+    if (q != q) continue;
+    sj += path_cost_jump(p, q);
+    kj += 1;
+  }
+  sc = path_reduce(sc, 0, lane, nl, red, sync);
+  kc = path_reduce(kc, 0, lane, nl, red, sync);
+  sj = path_reduce(sj, 0, lane, nl, red, sync);
+  kj = path_reduce(kj, 0, lane, nl, red, sync);
+  const double cost_cert = sc / kc, cost_jump = sj / kj;  // 0 / 0: NaN
+  return certWeight * cost_cert + (1 - certWeight) * cost_jump;
+}
+
 // One sound: nf rows of src_cols doubles at src_rows (the candidates as pitch_candidates
 // leaves them, in their first P.cols - kPathCols columns) -> nf rows of P.cols doubles at
 // rows: those columns, then pitch, amplVoiced, voiced (harmonics NaN: sg_anl_harm fills it),
 // with the smoothed dom, the blanked quartiles and HNR in dB. src_rows may be rows itself
 // (src_cols == P.cols: the table is rewritten in place, path_sound) or a table apart that
-// stays untouched (a sweep's shared candidates, sg_anl_sweep_path). scr: nf * path_stride()
+// stays untouched (a sweep's shared candidates, sg_anl_sweep_path). scr: nf * path_scratch()
 // doubles; red: nl doubles and sh: 3 int64 shared by the lanes; hw: floor(smoothing_ww / 2).
-// Every lane must call it.
-template <class Sync>
+// kMode says what else is compiled in, so that the modes of the reference do not pay for code they do not run (the
+// default, 0, is the tail as it was): bit 0 (kPathExact) 'exact', P.pathfinding == 3, which needs dd, 2 path_width()
+// doubles shared by the lanes (without the bit, 3 takes 'none': the callers choose the instantiation by P); bit 1
+// (kPathSegs) the segment list: segs, nullptr or path_seg_cells(nf) doubles that receive the sound's voiced
+// segments (kPathSegCells). Every lane must call it.
+constexpr int kPathExact = 1, kPathSegs = 2;
+template <class Sync, int kMode = 0>
 SG_PATH_HD inline void path_sound_at(const PathPars& P, int nf, int hw, const double* src_rows, int src_cols, double* rows,
-                                     double* scr, int lane, int nl, double* red, int64_t* sh, Sync sync) {
+                                     double* scr, int lane, int nl, double* red, int64_t* sh, Sync sync, double* dd = nullptr,
+                                     double* segs = nullptr) {
   const int W = path_width(P.nCands), S = path_stride(P.nCands), X = 2 * W;
   const int c0 = P.cols - kPathCols;
+  int nseg = 0;
   // pitch_matrices (:578-591), log2 (pathfinder :39), the prior (:598-612), the centre of gravity (:43-49)
   for (int f = lane; f < nf; f += nl) {
     const double* row = src_rows + (int64_t)f * src_cols;
@@ -355,6 +498,16 @@ SG_PATH_HD inline void path_sound_at(const PathPars& P, int nf, int hw, const do
       for (int f = lane; f < n; f += nl) {
         double* c = seg + (int64_t)f * S;
         c[X + kSlotHz] = c[X + kSlotCnt] > 0 ? exp2(c[0]) : NAN;
+        if ((kMode & kPathSegs) && segs) c[X + kSlotPath] = c[X + kSlotCnt] > 0 ? c[0] : NAN;
+      }
+      if ((kMode & kPathSegs) && segs) {  // the cost of the only path there is
+        sync();
+        const double cost = path_cost(seg, S, W, n, P.certWeight, lane, nl, red, sync);
+        if (lane == 0) {
+          double* o = segs + 1 + (int64_t)kPathSegCells * nseg;
+          o[0] = (double)sh[1], o[1] = (double)sh[2], o[2] = most, o[3] = cost;
+        }
+        ++nseg;
       }
       continue;
     }
@@ -383,7 +536,9 @@ SG_PATH_HD inline void path_sound_at(const PathPars& P, int nf, int hw, const do
       costB = path_reduce(costB, 0, lane, nl, red, sync);
       if (!(costF < costB))
         for (int f = lane; f < n; f += nl) seg[(int64_t)f * S + X + kSlotPath] = seg[(int64_t)f * S + X + kSlotAux];
-    } else {  // 'none' (:110-113)
+    } else if (!((kMode & kPathExact) && n >= 2 && P.pathfinding == 3 && dd &&  // 'exact'; false: no neighbouring frames
+                 path_exact(seg, S, W, n, P.certWeight, scr + (int64_t)nf * S + (sh[1] - 1) * W, dd, lane, nl, red, sync))) {
+      // 'none' (:110-113)
       for (int f = lane; f < n; f += nl) {
         double* c = seg + (int64_t)f * S;
         double cost;
@@ -392,6 +547,14 @@ SG_PATH_HD inline void path_sound_at(const PathPars& P, int nf, int hw, const do
       }
     }
     sync();
+    if ((kMode & kPathSegs) && segs) {  // before the snake moves the path
+      const double cost = path_cost(seg, S, W, n, P.certWeight, lane, nl, red, sync);
+      if (lane == 0) {
+        double* o = segs + 1 + (int64_t)kPathSegCells * nseg;
+        o[0] = (double)sh[1], o[1] = (double)sh[2], o[2] = most, o[3] = cost;
+      }
+      ++nseg;
+    }
     // snake() (:419-475); not run on a segment with a frame that has no candidate (in the
     // reference its first force_new is NA and it breaks at once)
     if (P.snakeStep > 0 && least > 0) {
@@ -427,6 +590,7 @@ SG_PATH_HD inline void path_sound_at(const PathPars& P, int nf, int hw, const do
     }
   }
   sync();
+  if ((kMode & kPathSegs) && segs && lane == 0) segs[0] = nseg;
   // medianSmoother (:670-681, reading the unsmoothed copies) and the final columns (:685-703)
   for (int f = lane; f < nf; f += nl) {
     double* row = rows + (int64_t)f * P.cols;
@@ -454,10 +618,10 @@ SG_PATH_HD inline void path_sound_at(const PathPars& P, int nf, int hw, const do
 }
 
 // One sound whose table is rewritten in place: rows holds the candidates and receives the result
-template <class Sync>
+template <class Sync, int kMode = 0>
 SG_PATH_HD inline void path_sound(const PathPars& P, int nf, int hw, double* rows, double* scr, int lane, int nl,
-                                  double* red, int64_t* sh, Sync sync) {
-  path_sound_at(P, nf, hw, rows, P.cols, rows, scr, lane, nl, red, sh, sync);
+                                  double* red, int64_t* sh, Sync sync, double* dd = nullptr, double* segs = nullptr) {
+  path_sound_at<Sync, kMode>(P, nf, hw, rows, P.cols, rows, scr, lane, nl, red, sh, sync, dd, segs);
 }
 
 }  // namespace sg

@@ -156,6 +156,8 @@ def lib():
         L.sg_analyze.argtypes = [vp, dp, i64, fpp, dp]
         L.sg_analyze_batch.argtypes = [vp, vp, i64p, i64p, i64, fpp, vp, i64p, i32p]
         L.sg_pitch_path.argtypes = [vp, dp, C.c_int32, i64, fpp, dp]
+        if hasattr(L, "sg_pitch_path_costs"):  # the segments and their path costs: likewise additive
+            L.sg_pitch_path_costs.argtypes = [vp, dp, C.c_int32, i64, fpp, dp, dp, i32p]
         L.sg_debug_track_kernel_ms.argtypes = [dp]
     if hasattr(L, "sg_analyze_summary"):  # analyze(summary = TRUE): likewise additive
         i32p = C.POINTER(C.c_int32)

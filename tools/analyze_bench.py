@@ -13,7 +13,8 @@ long recording at 44.1 kHz. For each workload, after --warmup runs, --steps runs
   new stages; --host-calls bounds how many of the batch's sounds the host tail is timed on
   (its per-sound cost is then scaled to the batch),
 
-with every run's stage times, so the run-to-run spread is on record.
+with every run's stage times, so the run-to-run spread is on record. --pathfinding (default
+'fast') is passed to analyze and to the numpy tail: 'exact' times sg_anl_path_exact.
 
     python tools/analyze_bench.py --out profiles/analyze_bench.json
 """
@@ -52,13 +53,13 @@ def timed(fn, hook, n, warmup, steps):
             "wall_s_min_med_max": [wall[0], round(float(np.median(wall)), 5), wall[-1]], "stage_ms_min_med_max": summary}
 
 
-def host_tail(tables, sr, step):
+def host_tail(tables, sr, step, pathfinding):
     """The numpy tail per sound: seconds."""
     from soundgen_beta_amd import analyze as AN
     t0 = time.perf_counter()
     for t in tables:
         if len(t["ampl"]):
-            AN.pitch_path_numpy(t, step, sr)
+            AN.pitch_path_numpy(t, step, sr, pathfinding=pathfinding)
     return time.perf_counter() - t0
 
 
@@ -69,6 +70,7 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--host-calls", type=int, default=256)
+    ap.add_argument("--pathfinding", default="fast")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
 
@@ -84,7 +86,8 @@ def main():
     ctx = native.default_context(0)
     L.sg_set_profiling(ctx.ptr, 1)
     res = {"tool": "analyze_bench", "calls": a.calls, "samplingRate": sr, "samples": int(lens[lens > 0].sum()),
-           "steps": a.steps, "warmup": a.warmup}
+           "steps": a.steps, "warmup": a.warmup, "pathfinding": a.pathfinding,
+           "library": os.path.relpath(native.LIB_PATH, ROOT)}
 
     def run_all(pitch_fn, analyze_fn, tables_fn, scale):
         out = {"pitch_candidates": timed(pitch_fn, L.sg_debug_pitch_kernel_ms, 6, a.warmup, a.steps),
@@ -97,7 +100,7 @@ def main():
             t0 = time.perf_counter()
             tables = tables_fn()
             fetch = time.perf_counter() - t0
-            host.append({"candidates_to_host_s": round(fetch, 5), "numpy_tail_s": round(host_tail(tables, sr, step) * scale, 5)})
+            host.append({"candidates_to_host_s": round(fetch, 5), "numpy_tail_s": round(host_tail(tables, sr, step, a.pathfinding) * scale, 5)})
         out["host_route"] = {"runs": host, "tail_scaled_by": scale}
         tail = float(np.median([h["numpy_tail_s"] for h in host]))
         out["numpy_tail_s_over_path_and_harmonics_s"] = round(tail / ((st["path"][1] + st["harmonics"][1]) / 1e3), 1)
@@ -106,7 +109,7 @@ def main():
     last = {}
     nh = max(1, min(a.host_calls, a.calls))
     res["batch"] = run_all(lambda: last.update(p=AN.pitch_candidates_batch(data, offs, lens, sr)),
-                           lambda: last.update(r=AN.analyze_batch(data, offs, lens, sr)),
+                           lambda: last.update(r=AN.analyze_batch(data, offs, lens, sr, pathfinding=a.pathfinding)),
                            lambda: AN.pitch_candidates_batch(data, offs, lens, sr, to_host=True)[:nh], a.calls / nh)
     r = last["r"]
     h = r["out"].cpu().numpy()[:sum(r["frames"]) * r["cols"]].reshape(-1, r["cols"])
@@ -120,7 +123,7 @@ def main():
     reps = 1 + n_long // max(1, int(sum(lens[i] for i in idx)))
     rec = np.concatenate([host[offs[i]:offs[i] + lens[i]] for i in idx] * reps)[:n_long].astype(np.float64)
     got = {}
-    res["recording"] = run_all(lambda: got.update(p=AN.pitch_candidates(rec, sr)), lambda: got.update(t=AN.analyze(rec, sr)),
+    res["recording"] = run_all(lambda: got.update(p=AN.pitch_candidates(rec, sr)), lambda: got.update(t=AN.analyze(rec, sr, pathfinding=a.pathfinding)),
                                lambda: [AN.pitch_candidates(rec, sr)], 1.0)
     res["recording"].update(seconds=round(len(rec) / sr, 2), frames=int(len(got["t"]["ampl"])),
                             tracked_frames=int(got["t"]["cond_entropy"].sum()), voiced_frames=int(got["t"]["voiced"].sum()))
