@@ -44,47 +44,32 @@ int set_err(sg_ctx* ctx, int code, const std::string& m) {
 }
 
 using sg::guarded;
+using sg::PK;
 
-// Rolls a Batch back to a checkpoint when planning one call fails.
-struct Checkpoint {
-  size_t segs, epochs, knots, ampsrc, ampcols, ampjobs, tasks, pieces, syls, syl_tiles, cknots, fl, items;
-  size_t frames[2], olas[2], mixes[2], copies, eterms, ecols, envjobs, frames64, ugath;
-  int64_t amp_total, w_total, harm_samples, harm_terms, harm_amp_bytes, fft_frames, fs_total, fe_total, w64_total, fh_total,
-      hp_bouts, hp_noise_bouts, fu_total;
-  double fft_flops;
-  explicit Checkpoint(const sg::Batch& B)
-      : segs(B.segs.size()), epochs(B.epochs.size()), knots(B.knots.size()), ampsrc(B.ampsrc.size()),
-        ampcols(B.ampcols.size()), ampjobs(B.ampjobs.size()),
-        tasks(B.tasks.size()), pieces(B.pieces.size()), syls(B.syls.size()), syl_tiles(B.syl_tiles.size()),
-        cknots(B.cknots.size()), fl(B.fl.size()), items(B.items.size()), copies(B.copies.size()),
-        eterms(B.eterms.size()), ecols(B.ecols.size()), envjobs(B.envjobs.size()), amp_total(B.amp_total), w_total(B.w_total),
-        harm_samples(B.harm_samples), harm_terms(B.harm_terms), harm_amp_bytes(B.harm_amp_bytes),
-        fft_frames(B.fft_frames), fs_total(B.fs_total), fe_total(B.fe_total), w64_total(B.w64_total),
-        fh_total(B.fh_total), hp_bouts(B.hp_bouts), hp_noise_bouts(B.hp_noise_bouts), fft_flops(B.fft_flops) {
-    frames64 = B.frames64.size();
-    ugath = B.ugath.size();
-    fu_total = B.fu_total;
-    for (int p = 0; p < 2; ++p) { frames[p] = B.frames[p].size(); olas[p] = B.olas[p].size(); mixes[p] = B.mixes[p].size(); }
-  }
-  void restore(sg::Batch& B) const {
-    B.segs.resize(segs); B.epochs.resize(epochs); B.knots.resize(knots); B.ampsrc.resize(ampsrc);
-    B.ampcols.resize(ampcols); B.ampjobs.resize(ampjobs); B.amp_total = amp_total;
-    B.tasks.resize(tasks); B.pieces.resize(pieces); B.syls.resize(syls); B.syl_tiles.resize(syl_tiles);
-    B.cknots.resize(cknots); B.fl.resize(fl); B.items.resize(items); B.copies.resize(copies);
-    for (int p = 0; p < 2; ++p) {
-      B.frames[p].resize(frames[p]); B.frame_geom[p].resize(frames[p]);
-      B.olas[p].resize(olas[p]); B.mixes[p].resize(mixes[p]);
-    }
-    B.w_total = w_total; B.harm_samples = harm_samples; B.harm_terms = harm_terms;
-    B.harm_amp_bytes = harm_amp_bytes; B.fft_frames = fft_frames; B.fs_total = fs_total;
-    B.eterms.resize(eterms); B.ecols.resize(ecols); B.envjobs.resize(envjobs); B.fe_total = fe_total;
-    B.frames64.resize(frames64); B.w64_total = w64_total; B.fh_total = fh_total; B.hp_bouts = hp_bouts;
-    B.hp_noise_bouts = hp_noise_bouts;
-    B.ugath.resize(ugath);
-    B.fu_total = fu_total;
-    B.fft_flops = fft_flops;
-  }
-};
+// Checkpoint of a Batch before a call is planned: every row of SG_PLAN_STATE, so a call
+// that fails is rolled back whole (its geometries and their tables in fl included).
+template <PK K, class M, class V>
+void mark_get(M& m, const V& v) {
+  if constexpr (sg::pk_counter(K)) m = v;
+  else m = (int64_t)v.size();
+}
+template <PK K, class V, class M>
+void mark_put(V& v, const M& m) {
+  if constexpr (sg::pk_counter(K)) v = m;
+  else v.resize((size_t)m);
+}
+sg::BatchMark checkpoint(const sg::Batch& B) {
+  sg::BatchMark m;
+#define X(kind, T, name, reserve) mark_get<PK::kind>(m.name, B.name);
+  SG_PLAN_STATE(X, X)
+#undef X
+  return m;
+}
+void restore(sg::Batch& B, const sg::BatchMark& m) {
+#define X(kind, T, name, reserve) mark_put<PK::kind>(B.name, m.name);
+  SG_PLAN_STATE(X, X)
+#undef X
+}
 
 // Plan calls [c0, c1) into B (empty), output slots from offset 0.
 // Bulk-array elements per call over the calls planned so far in this process
@@ -93,7 +78,10 @@ struct Checkpoint {
 // doubling, whose relocation copies and fresh-page faults were ~20 % of
 // planning time. Only the first parts planned in a process grow.
 struct GrowthEstimate {
-  static constexpr int N = 17;
+  static constexpr int N = 0  // the arrays of the rows with reserve = 1
+#define X(kind, T, name, reserve) + (reserve)
+      SG_PLAN_STATE(X, X);
+#undef X
   std::atomic<int64_t> calls{0};
   std::atomic<int64_t> elems[N];
   GrowthEstimate() {
@@ -114,10 +102,11 @@ struct GrowthEstimate {
   }
   template <class F>
   static void each(sg::Batch& B, F&& f) {
-    f(0, B.segs); f(1, B.epochs); f(2, B.knots); f(3, B.ampsrc); f(4, B.tasks);
-    f(5, B.pieces); f(6, B.syl_tiles); f(7, B.fl); f(8, B.cknots); f(9, B.eterms);
-    f(10, B.frames[0]); f(11, B.frames[1]); f(12, B.frame_geom[0]); f(13, B.frame_geom[1]); f(14, B.syls);
-    f(15, B.ecols); f(16, B.ampcols);
+    int i = 0;
+#define X(kind, T, name, reserve) \
+  if constexpr (reserve) f(i++, B.name);
+    SG_PLAN_STATE(X, X)
+#undef X
   }
   void reserve(sg::Batch& B, int64_t n_calls) const {
     const int64_t c = calls.load();
@@ -140,15 +129,9 @@ GrowthEstimate g_growth;
 void plan_range(sg::Batch& B, const sg_call_desc* calls, int64_t c0, int64_t c1, bool stream_stop = true,
                 const std::function<void(int64_t)>* on_done = nullptr) {
   const int64_t n = c1 - c0;
-  B.call_len.assign(n, 0);
-  B.call_off.assign(n, 0);
-  B.call_status.assign(n, 0);
-  B.call_fp64.assign(n, 0);
-  B.call_rho.assign(n, 0.0);
-  B.call_rho_noise.assign(n, 0.0);
-  B.call_rows.assign(n, 0.0);
-  B.call_flops.assign(n, 0.0);
-  B.call_msg.assign(n, "");
+#define X(kind, T, name, reserve) B.name.assign((size_t)n, T::value_type());
+  SG_PLAN_CALLS(X)
+#undef X
   int64_t off = 0;
   // A call drawing from callbacks (R's RNG through the shim) that fails ends the
   // callback stream there: lapply(calls, soundgen) stops at that call's stop(),
@@ -166,7 +149,7 @@ void plan_range(sg::Batch& B, const sg_call_desc* calls, int64_t c0, int64_t c1,
       B.call_len[i] = 0;
       continue;
     }
-    Checkpoint cp(B);
+    const sg::BatchMark cp = checkpoint(B);
     const int first_syl = (int)B.syls.size();
     const int64_t hp0 = B.hp_bouts, rows0 = B.harm_terms;
     const double fl0 = B.fft_flops;
@@ -201,8 +184,7 @@ void plan_range(sg::Batch& B, const sg_call_desc* calls, int64_t c0, int64_t c1,
       B.call_flops[i] = B.fft_flops - fl0;
       off += (L + 63) / 64 * 64;  // 256-B aligned call slots
     } catch (const sg::SgError& e) {
-      cp.restore(B);
-      sg::restore_soundgen_tail(B, first_syl);
+      restore(B, cp);
       B.call_status[i] = e.code;
       B.call_msg[i] = e.what();
       B.call_off[i] = off;
@@ -222,13 +204,20 @@ int plan_threads(int64_t n_calls) {
   return (int)std::min<int64_t>(t, std::max<int64_t>(1, n_calls / 4));
 }
 
-// Where one part's arrays land in the merged batch.
-struct PartBase {
-  int64_t out, fs, fl, w, amp, asrc, acol, ajob, knot, ck, task, seg, syl, piece, st, item, copy, call, epoch, fe, term,
-      col, job;
-  int64_t w64, fh, fr64, fu, ug;
-  int64_t fr[2], ola[2], mix[2];
-};
+// Where one part lands in the merged batch: per row of SG_PLAN_STATE, the elements of
+// an array (the value of a counter) over the parts before it.
+using PartBase = sg::BatchMark;
+template <PK K, class M, class V>
+void part_advance(M& c, const V& s) {
+  if constexpr (K == PK::Sum) c += s;
+  else if constexpr (K == PK::Sum4) c = (c + s + 3) / 4 * 4;  // keeps the parts' 16-B alignment of epoch waveforms
+  else if constexpr (K == PK::Max) c = std::max(c, s);
+  else if constexpr (K != PK::Geo) c += (int64_t)s.size();
+}
+template <PK K, class V, class M>
+void part_copy(V& d, V& s, const M& at) {
+  if constexpr (K == PK::Arr) std::move(s.begin(), s.end(), d.begin() + at);
+}
 
 // Concatenate per-chunk batches in call order, rebasing every cross-reference
 // (scratch, arena and output offsets, table indices). Bases are prefix sums
@@ -259,149 +248,99 @@ void merge_parts(sg::Batch& D, std::vector<sg::Batch>& parts, int threads) {
       }
       gmap[k][g] = j;
     }
-    c.out += S.total_out; c.fs += S.fs_total; c.fl += (int64_t)S.fl.size();
-    c.w = (c.w + S.w_total + 3) / 4 * 4;  // keeps the parts' 16-B alignment of epoch waveforms
-    c.amp += S.amp_total; c.asrc += (int64_t)S.ampsrc.size(); c.acol += (int64_t)S.ampcols.size();
-    c.ajob += (int64_t)S.ampjobs.size();
-    D.amp_lg_rows = std::max(D.amp_lg_rows, S.amp_lg_rows);
-    c.knot += (int64_t)S.knots.size(); c.ck += (int64_t)S.cknots.size();
-    c.task += (int64_t)S.tasks.size(); c.seg += (int64_t)S.segs.size(); c.syl += (int64_t)S.syls.size();
-    c.piece += (int64_t)S.pieces.size(); c.st += (int64_t)S.syl_tiles.size(); c.item += (int64_t)S.items.size();
-    c.copy += (int64_t)S.copies.size(); c.call += (int64_t)S.call_len.size(); c.epoch += (int64_t)S.epochs.size();
-    c.fe += S.fe_total; c.term += (int64_t)S.eterms.size(); c.col += (int64_t)S.ecols.size();
-    c.job += (int64_t)S.envjobs.size();
-    c.w64 += S.w64_total; c.fh += S.fh_total; c.fr64 += (int64_t)S.frames64.size();
-    c.fu += S.fu_total; c.ug += (int64_t)S.ugath.size();
-    D.hp_bouts += S.hp_bouts;
-    D.hp_noise_bouts += S.hp_noise_bouts;
-    for (int ph = 0; ph < 2; ++ph) {
-      c.fr[ph] += (int64_t)S.frames[ph].size(); c.ola[ph] += (int64_t)S.olas[ph].size();
-      c.mix[ph] += (int64_t)S.mixes[ph].size();
-    }
-    D.harm_samples += S.harm_samples; D.harm_terms += S.harm_terms; D.harm_amp_bytes += S.harm_amp_bytes;
-    D.fft_frames += S.fft_frames;
-    D.fft_flops += S.fft_flops;
+#define X(kind, T, name, reserve) part_advance<PK::kind>(c.name, S.name);
+    SG_PLAN_STATE(X, X)
+#undef X
   }
-  D.total_out = c.out; D.fs_total = c.fs; D.w_total = c.w; D.fe_total = c.fe;
-  D.w64_total = c.w64; D.fh_total = c.fh; D.frames64.resize(c.fr64);
-  D.fu_total = c.fu; D.ugath.resize(c.ug);
-  D.ecols.resize(c.col); D.envjobs.resize(c.job);
-  D.call_len.resize(c.call); D.call_off.resize(c.call); D.call_status.resize(c.call); D.call_msg.resize(c.call);
-  D.call_fp64.resize(c.call); D.call_rho.resize(c.call); D.call_rho_noise.resize(c.call); D.call_rows.resize(c.call); D.call_flops.resize(c.call);
-  D.epochs.resize(c.epoch); D.knots.resize(c.knot); D.pieces.resize(c.piece);
-  D.amp_total = c.amp; D.ampsrc.resize(c.asrc); D.ampcols.resize(c.acol); D.ampjobs.resize(c.ajob); D.syls.resize(c.syl); D.syl_tiles.resize(c.st);
-  D.cknots.resize(c.ck); D.items.resize(c.item);
-  // the largest arrays stay in the parts' blocks (moved below, not copied)
-  auto blocks = [&](auto& x, int64_t n) {
-    x.blocks.resize(np);
-    x.base.resize(np);
-    x.n = n;
-  };
-  blocks(D.segs_x, c.seg); blocks(D.tasks_x, c.task); blocks(D.fl_x, c.fl);
-  blocks(D.eterms_x, c.term); D.copies.resize(c.copy);
-  for (int ph = 0; ph < 2; ++ph) {
-    D.frames[ph].resize(c.fr[ph]); D.frame_geom[ph].resize(c.fr[ph]);
-    D.olas[ph].resize(c.ola[ph]); D.mixes[ph].resize(c.mix[ph]);
-  }
-  auto put = [](auto& dst, auto& src, int64_t at) { std::copy(src.begin(), src.end(), dst.begin() + at); };
+  // the merged sizes and totals; the largest arrays stay in the parts' blocks (moved below, not copied)
+#define X(kind, T, name, reserve) \
+  if constexpr (PK::kind != PK::Geo) mark_put<PK::kind>(D.name, c.name);
+#define XB(kind, T, name, reserve) \
+  D.name##_x.blocks.resize(np);    \
+  D.name##_x.base.resize(np);      \
+  D.name##_x.n = c.name;
+  SG_PLAN_STATE(X, XB)
+#undef XB
+#undef X
   auto one = [&](size_t k) {
     sg::Batch& S = parts[k];
     const PartBase& b = base[k];
-    auto ck = [&](SgContour& x) { if (x.kind == 3) x.k_off += b.ck; };
-    for (size_t i = 0; i < S.call_len.size(); ++i) {
-      D.call_len[b.call + i] = S.call_len[i];
-      D.call_off[b.call + i] = S.call_off[i] + b.out;
-      D.call_status[b.call + i] = S.call_status[i];
-      D.call_fp64[b.call + i] = S.call_fp64[i];
-      D.call_rho[b.call + i] = S.call_rho[i];
-      D.call_rho_noise[b.call + i] = S.call_rho_noise[i];
-      D.call_rows[b.call + i] = S.call_rows[i];
-      D.call_flops[b.call + i] = S.call_flops[i];
-      D.call_msg[b.call + i] = std::move(S.call_msg[i]);
-    }
+    auto ck = [&](SgContour& x) { if (x.kind == 3) x.k_off += b.cknots; };
+    for (auto& o : S.call_off) o += b.total_out;
     for (auto& e : S.epochs) {
-      e.w_off += b.w; e.amp_off += b.amp; e.knot_off += b.knot;
-      e.seg_off += (int32_t)b.seg; e.syl += (int32_t)b.syl;
+      e.w_off += b.w_total; e.amp_off += b.amp_total; e.knot_off += b.knots;
+      e.seg_off += (int32_t)b.segs; e.syl += (int32_t)b.syls;
     }
     for (auto& t : S.tasks) {
-      t.w_off += (t.flags & SG_TASK_HP) ? b.w64 : b.w;
-      t.a_off += b.amp; t.d_off += b.amp; t.syl += (int32_t)b.syl;
+      t.w_off += (t.flags & SG_TASK_HP) ? b.w64_total : b.w_total;
+      t.a_off += b.amp_total; t.d_off += b.amp_total; t.syl += (int32_t)b.syls;
     }
     for (auto& s : S.syls)  // a syllable's pieces read W, or W64 for an fp64 syllable
       for (int32_t pi = s.piece0; pi < s.piece0 + s.npiece; ++pi) {
         SgPiece& p = S.pieces[pi];
-        for (int q = 0; q < (p.nterms < 0 ? 1 : p.nterms); ++q) p.t[q].src += s.hp ? b.w64 : b.w;
+        for (int q = 0; q < (p.nterms < 0 ? 1 : p.nterms); ++q) p.t[q].src += s.hp ? b.w64_total : b.w_total;
       }
     for (auto& s : S.syls) {
-      s.out_off += s.hp ? b.fh : (s.dst_fs ? b.fs : b.out);
-      s.piece0 += (int32_t)b.piece; s.max_slot += (int32_t)b.syl; s.task0 += b.task;
+      s.out_off += s.hp ? b.fh_total : (s.dst_fs ? b.fs_total : b.total_out);
+      s.piece0 += (int32_t)b.pieces; s.max_slot += (int32_t)b.syls; s.task0 += b.tasks;
       ck(s.env);
       ck(s.genv);
-      if (s.drift.nk > 0) s.drift.k_off += b.ck;
+      if (s.drift.nk > 0) s.drift.k_off += b.cknots;
     }
     for (auto& t : S.syl_tiles) {
-      t.syl += (int32_t)b.syl; t.piece += (int32_t)b.piece;
-      for (int w = 0; w < 4; ++w) t.wpiece[w] += (int32_t)b.piece;
+      t.syl += (int32_t)b.syls; t.piece += (int32_t)b.pieces;
+      for (int w = 0; w < 4; ++w) t.wpiece[w] += (int32_t)b.pieces;
     }
     for (int ph = 0; ph < 2; ++ph) {
       for (auto& f : S.frames[ph]) {
         // noise: uniforms in fl, or gathered (uniform area, encoded); filter: the sound in fs
-        f.src = ph == 1 ? f.src + b.fs : (f.src < 0 ? f.src - b.fu : f.src + b.fl);
-        f.env = f.env < 0 ? f.env - b.fe : f.env + b.fl;  // envelope area (encoded) or fl
-        if (f.dst >= 0) f.dst += b.fs;
+        f.src = ph == 1 ? f.src + b.fs_total : (f.src < 0 ? f.src - b.fu_total : f.src + b.fl);
+        f.env = f.env < 0 ? f.env - b.fe_total : f.env + b.fl;  // envelope area (encoded) or fl
+        if (f.dst >= 0) f.dst += b.fs_total;
       }
       for (auto& g : S.frame_geom[ph]) g = gmap[k][g];
       for (auto& o : S.olas[ph]) {
-        if (o.fidx >= 0) o.fidx += (int32_t)b.fr[ph];
-        if (!o.fused) o.frames += b.fs;
-        o.out += b.fs;
+        if (o.fidx >= 0) o.fidx += (int32_t)b.frames[ph];
+        if (!o.fused) o.frames += b.fs_total;
+        o.out += b.fs_total;
       }
       for (auto& m : S.mixes[ph]) {
-        m.dst += m.to_fs == 2 ? b.fh : (m.to_fs ? b.fs : b.out);
-        if (m.base_kind != SG_BASE_NONE) m.base += b.fs;
-        if (m.base_kind == SG_BASE_NORM) m.base_ola += (int32_t)b.ola[1];
-        m.item0 += (int32_t)b.item;
+        m.dst += m.to_fs == 2 ? b.fh_total : (m.to_fs ? b.fs_total : b.total_out);
+        if (m.base_kind != SG_BASE_NONE) m.base += b.fs_total;
+        if (m.base_kind == SG_BASE_NORM) m.base_ola += (int32_t)b.olas[1];
+        m.item0 += (int32_t)b.items;
         if (m.am_lo > 0) m.am_tab += b.fl;
         ck(m.mult);
       }
     }
     for (auto& f : S.frames64) {
       // uniforms (fl, or the uniform area encoded) / pre-filter sound (fh)
-      f.src = f.mode == SG_F64_NOISE ? (f.src < 0 ? f.src - b.fu : f.src + b.fl) : f.src + b.fh;
-      f.env = f.env < 0 ? f.env - b.fe : f.env + b.fl;
-      f.dst += b.fs;
+      f.src = f.mode == SG_F64_NOISE ? (f.src < 0 ? f.src - b.fu_total : f.src + b.fl) : f.src + b.fh_total;
+      f.env = f.env < 0 ? f.env - b.fe_total : f.env + b.fl;
+      f.dst += b.fs_total;
     }
     for (auto& it : S.items) {
-      it.raw += (it.flags & SG_ITEM_F64) ? b.fh : b.fs;
-      if (it.flags & SG_ITEM_FILTER_OLA) it.ola += (int32_t)b.ola[1];
-      else if (it.ola >= 0) it.ola += (int32_t)b.ola[0];
+      it.raw += (it.flags & SG_ITEM_F64) ? b.fh_total : b.fs_total;
+      if (it.flags & SG_ITEM_FILTER_OLA) it.ola += (int32_t)b.olas[1];
+      else if (it.ola >= 0) it.ola += (int32_t)b.olas[0];
       ck(it.strength);
     }
-    for (auto& x : S.copies) { x.fl_off += b.fl; x.fs_off += b.fs; }
-    for (auto& j : S.envjobs) { j.out += b.fe; j.term0 += b.term; j.col0 += b.col; }
-    for (auto& g : S.ugath) g.dst += b.fu;
-    put(D.ugath, S.ugath, b.ug);
-    auto move = [&](auto& x, auto& v, int64_t at) {
-      x.blocks[k] = std::move(v);
-      x.base[k] = at;
-    };
+    for (auto& x : S.copies) { x.fl_off += b.fl; x.fs_off += b.fs_total; }
+    for (auto& j : S.envjobs) { j.out += b.fe_total; j.term0 += b.eterms; j.col0 += b.ecols; }
+    for (auto& g : S.ugath) g.dst += b.fu_total;
     for (auto& j : S.ampjobs) {
-      j.amp_off += b.amp;
-      if (j.src_off >= 0) j.src_off += b.asrc;
-      if (j.col0 >= 0) j.col0 += b.acol;
+      j.amp_off += b.amp_total;
+      if (j.src_off >= 0) j.src_off += b.ampsrc;
+      if (j.col0 >= 0) j.col0 += b.ampcols;
     }
-    put(D.ampsrc, S.ampsrc, b.asrc); put(D.ampcols, S.ampcols, b.acol); put(D.ampjobs, S.ampjobs, b.ajob);
-    move(D.eterms_x, S.eterms, b.term); move(D.segs_x, S.segs, b.seg);
-    move(D.tasks_x, S.tasks, b.task); move(D.fl_x, S.fl, b.fl);
-    put(D.ecols, S.ecols, b.col); put(D.envjobs, S.envjobs, b.job);
-    put(D.epochs, S.epochs, b.epoch); put(D.knots, S.knots, b.knot); put(D.pieces, S.pieces, b.piece);
-    put(D.syls, S.syls, b.syl); put(D.syl_tiles, S.syl_tiles, b.st); put(D.cknots, S.cknots, b.ck);
-    put(D.items, S.items, b.item); put(D.copies, S.copies, b.copy);
-    put(D.frames64, S.frames64, b.fr64);
-    for (int ph = 0; ph < 2; ++ph) {
-      put(D.frames[ph], S.frames[ph], b.fr[ph]); put(D.frame_geom[ph], S.frame_geom[ph], b.fr[ph]);
-      put(D.olas[ph], S.olas[ph], b.ola[ph]); put(D.mixes[ph], S.mixes[ph], b.mix[ph]);
-    }
+    // the rebased part to its place: arrays copied, the block arrays moved
+#define X(kind, T, name, reserve) part_copy<PK::kind>(D.name, S.name, b.name);
+#define XB(kind, T, name, reserve)           \
+  D.name##_x.blocks[k] = std::move(S.name);  \
+  D.name##_x.base[k] = b.name;
+    SG_PLAN_STATE(X, XB)
+#undef XB
+#undef X
   };
   std::atomic<size_t> next{0};
   auto work = [&]() {

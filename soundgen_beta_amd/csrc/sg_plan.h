@@ -5,6 +5,8 @@
 #include <cstdint>
 #include <functional>
 #include <memory>
+#include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -73,8 +75,6 @@ inline const T& bulk_at(const Blocks<T>& x, const bulk<T>& v, int64_t i) {  // d
   return x.blocks[lo][(size_t)(i - x.base[lo])];
 }
 
-struct DeviceArrays;  // sg_api.cpp
-
 // FFT/OLA job of the noise source or the formant filter (seewave istft/stft)
 struct SgFftJob;
 
@@ -88,22 +88,108 @@ struct Slice {
   int64_t c0, c1;    // finalize tiles (fast path, copy_tiles)
 };
 
+// ---- the state that planning one call changes, declared once ----
+// Every member of Batch (its PlanReport included) that planning a call appends to or
+// advances is one row X(kind, type, name, reserve) of SG_PLAN_STATE. Generated from the
+// rows: the members themselves, BatchMark (what a failed call is rolled back to, and
+// where a part lands in a merged batch), the arrays a part reserves up front (reserve =
+// 1: GrowthEstimate) and the prefix sums, resizes and copies of merge_parts (sg_api.cpp).
+// So a member that a planner function grows has to be a row: a failed call leaves
+// nothing behind, and a batch planned in parts merges it.
+enum class PK {
+  Arr,   // array: rolled back by its size, the parts' concatenated
+  Blk,   // array whose parts stay blocks of the merged batch (name_x: Blocks, moved, no copy)
+  Sum,   // counter: the parts' sum
+  Sum4,  // counter: the parts' sum, every part starting on a multiple of 4 (16 B of floats)
+  Max,   // the largest of the parts
+  Geo,   // geoms: rolled back like an array, the parts' matched by window length
+};
+constexpr bool pk_counter(PK k) { return k == PK::Sum || k == PK::Sum4 || k == PK::Max; }
+
+// the per-call report arrays: one element per call, sized before the calls are planned
+#define SG_PLAN_CALLS(X)                                                                                        \
+  X(Arr, std::vector<int64_t>, call_len, 0)                                                                     \
+  X(Arr, std::vector<int64_t>, call_off, 0)                                                                     \
+  X(Arr, std::vector<int32_t>, call_status, 0)                                                                  \
+  X(Arr, std::vector<int32_t>, call_fp64, 0)     /* bouts of the call on the fp64 filter path */                \
+  X(Arr, std::vector<double>, call_rho, 0)       /* the largest conditioning estimate over its filtered bouts */ \
+  X(Arr, std::vector<double>, call_rho_noise, 0) /* the same for the pre-filter noise of its filtered bouts */  \
+  X(Arr, std::vector<std::string>, call_msg, 0)                                                                 \
+  X(Arr, std::vector<double>, call_rows, 0)      /* sine-bank (sample, row) terms */                            \
+  X(Arr, std::vector<double>, call_flops, 0)     /* FFT flops */
+// the sums of the report
+#define SG_PLAN_SUMS(X)                                                                                         \
+  X(Sum, int64_t, total_out, 0) /* output samples, 256-B aligned call slots (set once the calls are planned) */ \
+  X(Sum, int64_t, harm_samples, 0)                                                                              \
+  X(Sum, int64_t, harm_terms, 0)                                                                                \
+  X(Sum, int64_t, harm_amp_bytes, 0)                                                                            \
+  X(Sum, int64_t, fft_frames, 0)                                                                                \
+  X(Sum, double, fft_flops, 0) /* nominal 5 wl log2 wl per transform, every frame path */
+// the descriptors; XB: the Blk rows; XP: a row of two arrays, one per phase (name[2])
+#define SG_BATCH_STATE(X, XB, XP)                                                                               \
+  /* ---- harmonic source ---- */                                                                               \
+  XB(Blk, bulk<SgSeg>, segs, 1)                                                                                 \
+  X(Arr, bulk<SgEpoch>, epochs, 1)                                                                              \
+  X(Arr, bulk<double>, knots, 1)                                                                                \
+  /* amplitude blocks: device-only (amp_total floats, sg_amp_build at upload) from */                           \
+  /* one SgAmpJob per epoch: the formula over ampcols, or a copy of ampsrc */                                   \
+  X(Sum, int64_t, amp_total, 0)                                                                                 \
+  X(Arr, bulk<SgAmpCol>, ampcols, 1)                                                                            \
+  X(Arr, std::vector<SgAmpJob>, ampjobs, 0)                                                                     \
+  X(Arr, bulk<float>, ampsrc, 1)    /* host-built [G][Rp] blocks (the fallback path) */                         \
+  X(Max, int64_t, amp_lg_rows, 0)   /* largest H: the log2 table the device formula reads */                    \
+  XB(Blk, bulk<SgWTask>, tasks, 1)                                                                              \
+  X(Arr, bulk<SgPiece>, pieces, 1)                                                                              \
+  X(Arr, std::vector<SgSyllable>, syls, 1)                                                                      \
+  X(Arr, bulk<SgSylTile>, syl_tiles, 1)                                                                         \
+  X(Arr, bulk<double>, cknots, 1)   /* contour / linear knot data */                                            \
+  X(Sum4, int64_t, w_total, 0)      /* epoch-waveform scratch (floats) */                                       \
+  X(Sum, int64_t, w64_total, 0)     /* fp64 epoch-waveform scratch W64 (doubles; SG_TASK_HP tasks) */           \
+  /* ---- spectral part (noise, formant filter, assembly) ---- */                                               \
+  XB(Blk, bulk<float>, fl, 1)       /* host-initialised floats (windows, twiddles, uniforms, envelopes, ...) */ \
+  X(Sum, int64_t, fs_total, 0)      /* scratch floats (frames, sounds, raw noise) */                            \
+  X(Sum, int64_t, fh_total, 0)      /* fp64 sound scratch fh (doubles): voiced parts and sounds of fp64 bouts */ \
+  X(Geo, std::vector<SgFftGeom>, geoms, 0)          /* their twiddles and windows are in fl */                  \
+  XP(Arr, std::vector<SgFrame>, frames, 1)          /* [0] noise frames, [1] filter frames */                   \
+  XP(Arr, std::vector<int32_t>, frame_geom, 1)       /* in step with frames */                                  \
+  XP(Arr, std::vector<SgOla>, olas, 0)              /* [0] noise OLAs, [1] filter OLAs (device: [0] then [1]) */ \
+  /* filter / noise frames of fp64 (ill-conditioned) bouts: sg_fft_frames64 */                                  \
+  X(Arr, std::vector<SgFrame64>, frames64, 0)                                                                   \
+  X(Arr, std::vector<SgNoiseItem>, items, 0)        /* items[].ola indexes the device OLA table */              \
+  XP(Arr, std::vector<SgMix>, mixes, 0)             /* [0] pre-filter sounds (fs), [1] final output */          \
+  X(Arr, std::vector<Batch::Copy>, copies, 0)       /* fl -> fs before the filter phase */                      \
+  X(Sum, int64_t, hp_bouts, 0)       /* bouts whose formant filter runs the fp64 path */                        \
+  X(Sum, int64_t, hp_noise_bouts, 0) /* bouts whose pre-filter noise runs the fp64 frame kernel */              \
+  /* device spectral envelopes (sg_spec_env): per-column/track terms, per-column */                             \
+  /* factors, jobs; outputs in the envelope area (fe_total floats after fe_base, */                             \
+  /* the end of the uploaded fl floats, fixed at finalize_spec). Until then a */                                \
+  /* frame's env < 0 encodes envelope-area offset -(env + 1). */                                                \
+  XB(Blk, bulk<SgEnvTerm>, eterms, 1)                                                                           \
+  X(Arr, std::vector<SgEnvCol>, ecols, 1)                                                                       \
+  X(Arr, std::vector<SgEnvJob>, envjobs, 0)                                                                     \
+  X(Sum, int64_t, fe_total, 0)                                                                                  \
+  /* generateNoise()'s runif(nr * nc) read from an injected draw array are not */                               \
+  /* copied per item: the item records the caller's range and its offset in the */                              \
+  /* uniform area (fu_total floats after fu_base, device-only, after the envelope */                            \
+  /* area); finalize_spec copies the union of the ranges once (ustream, floats) and */                          \
+  /* sg_ugather expands the items at upload. Until then a noise frame's src < 0 */                              \
+  /* encodes uniform-area offset -(src + 1). */                                                                 \
+  X(Arr, std::vector<Batch::UGather>, ugath, 0)                                                                   \
+  X(Sum, int64_t, fu_total, 0)
+// every row to X, the Blk rows to XB; a per-phase row reaches X (the macro of that name
+// where SG_PLAN_STATE is used) as its two arrays, name[0] and name[1]
+#define SG_PLAN_STATE(X, XB) SG_PLAN_CALLS(X) SG_PLAN_SUMS(X) SG_BATCH_STATE(X, XB, SG_PHASE_ROWS)
+#define SG_PHASE_ROWS(kind, T, name, reserve) X(kind, T, name[0], reserve) X(kind, T, name[1], reserve)
+
 // What a plan reports of its calls and its work. Neither the upload nor the launch
 // sequence reads it; it is all that a plan keeps of its Batch after
 // sg_plan_release_host.
 struct PlanReport {
-  // ---- per call ----
-  std::vector<int64_t> call_len, call_off;
-  std::vector<int32_t> call_status;
-  std::vector<int32_t> call_fp64;   // bouts of the call on the fp64 filter path
-  std::vector<double> call_rho;     // the largest conditioning estimate over the call's filtered bouts
-  std::vector<double> call_rho_noise;  // the same for the pre-filter noise of its filtered bouts
-  std::vector<std::string> call_msg;
-  int64_t total_out = 0;
-  // ---- stats ----
-  int64_t harm_samples = 0, harm_terms = 0, harm_amp_bytes = 0, fft_frames = 0;
-  double fft_flops = 0;                      // nominal 5 wl log2 wl per transform, every frame path
-  std::vector<double> call_rows, call_flops;  // per call: sine-bank (sample, row) terms, FFT flops
+#define X(kind, T, name, reserve) T name{};
+  SG_PLAN_CALLS(X)
+  SG_PLAN_SUMS(X)
+#undef X
+  // ---- derived (finalize_spec) ----
   int64_t stft_bytes = 0, stft_samples = 0;  // sg_stft_ola: algorithmic bytes, trimmed output samples
   double stft_flops = 0;                     // sg_stft_ola: nominal 5 wl log2 wl per transform
 };
@@ -115,49 +201,38 @@ struct Batch : PlanReport {
   // call's last draw -- amplitude columns, phase segments, wave tasks, envelope terms,
   // frames, mixes -- runs once, in the parallel replay)
   bool draws_only = false;
-  // ---- harmonic source ----
-  bulk<SgSeg> segs;
-  bulk<SgEpoch> epochs;
-  bulk<double> knots;
-  // amplitude blocks: device-only (amp_total floats, sg_amp_build at upload) from
-  // one SgAmpJob per epoch: the formula over ampcols, or a copy of ampsrc
-  int64_t amp_total = 0;
-  bulk<SgAmpCol> ampcols;
-  std::vector<SgAmpJob> ampjobs;
-  bulk<float> ampsrc;         // host-built [G][Rp] blocks (the fallback path)
-  int64_t amp_lg_rows = 0;    // largest H: the log2 table the device formula reads
-  bulk<SgWTask> tasks;
-  bulk<SgPiece> pieces;
-  std::vector<SgSyllable> syls;
-  bulk<SgSylTile> syl_tiles;
-  std::vector<SgSylTile> fin_tiles;    // derived (finalize_plan): syl_tiles the fast path does not take
-  std::vector<SgCopyTile> copy_tiles;  // derived (finalize_plan): fast-path finalize tiles
+  struct Copy { int64_t fl_off, fs_off, n; };
+  struct UGather {
+    const double* src;
+    int64_t n, dst, ntot;
+  };
+  // ---- changed by planning a call: the rows of SG_BATCH_STATE, nothing else ----
+#define X(kind, T, name, reserve) T name{};
+#define XB(kind, T, name, reserve) \
+  T name{};                        \
+  Blocks<T::value_type> name##_x;  // merged batch: the parts' blocks ahead of name
+#define XP(kind, T, name, reserve) T name[2];
+  SG_BATCH_STATE(X, XB, XP)
+#undef XP
+#undef XB
+#undef X
+  double rho_cur = 0, rho_noise_cur = 0;  // call_rho, call_rho_noise of the call being planned
+  // ---- derived once all calls are planned (finalize_plan, finalize_spec) ----
+  std::vector<SgSylTile> fin_tiles;    // syl_tiles the fast path does not take
+  std::vector<SgCopyTile> copy_tiles;  // fast-path finalize tiles
   std::vector<SgSylTile> ptiles;   // tiles over multi-term (crossfade) pieces: [fp32 syllables..., fp64 syllables...]
-  int64_t ptile_hp = 0;            // derived: first ptile of an fp64 syllable
-  std::vector<SgSylTile> fin_tiles_hp;  // derived: finalize tiles of fp64 syllables (sg_harm_finalize_hp)
+  int64_t ptile_hp = 0;            // first ptile of an fp64 syllable
+  std::vector<SgSylTile> fin_tiles_hp;  // finalize tiles of fp64 syllables (sg_harm_finalize_hp)
   std::vector<Slice> slices;
-  // ---- spectral part (noise, formant filter, assembly) ----
-  bulk<float> fl;                 // host-initialised floats (windows, twiddles, uniforms, envelopes, ...)
-  int64_t fs_total = 0;                  // scratch floats (frames, sounds, raw noise)
-  std::vector<SgFftGeom> geoms;
-  std::vector<SgFrame> frames[2];        // [0] noise frames, [1] filter frames
-  std::vector<int32_t> frame_geom[2];
-  std::vector<SgOla> olas[2];            // [0] noise OLAs, [1] filter OLAs (device: [0] then [1])
-  std::vector<SgFrame64> frames64;       // filter / noise frames of fp64 (ill-conditioned) bouts: sg_fft_frames64
-  // derived (finalize_spec): the window lengths of the fp64 frames, their root tables
-  // W_N^t (offsets in double2 units), each frame's table offset, the largest window
+  // the window lengths of the fp64 frames, their root tables W_N^t (offsets in double2
+  // units), each frame's table offset, the largest window
   std::vector<int32_t> roots64_wl;
   std::vector<int64_t> roots64_off, frames64_tab;
   int64_t roots64_total = 0;
   int32_t frames64_maxwl = 0;
-  int64_t frames64_noise = 0;  // finalize_spec: frames64 holds the noise frames first
+  int64_t frames64_noise = 0;  // frames64 holds the noise frames first
   // per phase: its leading frames of wl = 2204, one per wavefront in sg_fft_frames64w (the rest: sg_fft_frames64)
   int64_t frames64_w[2] = {0, 0};
-  std::vector<SgNoiseItem> items;        // items[].ola indexes the device OLA table
-  std::vector<SgMix> mixes[2];           // [0] pre-filter sounds (fs), [1] final output
-  struct Copy { int64_t fl_off, fs_off, n; };
-  std::vector<Copy> copies;              // fl -> fs before the filter phase
-  // derived (finalize_spec)
   std::vector<SgFrameGroup> fgroups;
   // per phase (0 noise, 1 filter): groups [r1, r2) run sg_fft_frames ([r0, r1) empty: wavefront-kernel
   // geometries run fused in sg_stft_ola, fgroup_lds[ph][0] = its dynamic LDS)
@@ -173,42 +248,20 @@ struct Batch : PlanReport {
   std::vector<SgMixTile> mixtiles;
   int64_t mixtile_split = 0;
   int64_t mixtile_hp = 0;                // pre-filter tiles [mixtile_hp, mixtile_split) write fh (sg_mix_hp)
-  bulk<double> cknots;   // contour / linear knot data
-  int64_t w_total = 0;          // epoch-waveform scratch (floats)
-  int64_t w64_total = 0;        // fp64 epoch-waveform scratch W64 (doubles; SG_TASK_HP tasks)
-  int64_t fh_total = 0;         // fp64 sound scratch fh (doubles): voiced parts and sounds of fp64 bouts
-  int64_t hp_bouts = 0;         // bouts whose formant filter runs the fp64 path
-  int64_t hp_noise_bouts = 0;   // bouts whose pre-filter noise runs the fp64 frame kernel
-  // device spectral envelopes (sg_spec_env): per-column/track terms, per-column
-  // factors, jobs; outputs in the envelope area (fe_total floats after fe_base,
-  // the end of the uploaded fl floats, fixed at finalize_spec). Until then a
-  // frame's env < 0 encodes envelope-area offset -(env + 1).
-  bulk<SgEnvTerm> eterms;
-  // merged batch: the parts' blocks ahead of segs, tasks, fl, eterms (Blocks)
-  Blocks<SgSeg> segs_x;
-  Blocks<float> fl_x;
-  Blocks<SgWTask> tasks_x;
-  Blocks<SgEnvTerm> eterms_x;
-  std::vector<SgEnvCol> ecols;
-  std::vector<SgEnvJob> envjobs;
-  int64_t fe_total = 0, fe_base = 0;
-  std::vector<SgEnvTask> envtasks;  // derived (finalize_spec)
-  // generateNoise()'s runif(nr * nc) read from an injected draw array are not
-  // copied per item: the item records the caller's range and its offset in the
-  // uniform area (fu_total floats after fu_base, device-only, after the envelope
-  // area); finalize_spec copies the union of the ranges once (ustream, floats) and
-  // sg_ugather expands the items at upload. Until then a noise frame's src < 0
-  // encodes uniform-area offset -(src + 1).
-  struct UGather {
-    const double* src;
-    int64_t n, dst, ntot;
-  };
-  std::vector<UGather> ugath;
-  int64_t fu_total = 0, fu_base = 0;
-  std::vector<float> ustream;  // derived (finalize_spec)
-  std::vector<SgUJob> ujobs;   // derived (finalize_spec)
-  std::vector<double> elog2;        // derived: log2(k), k = 1..max nr
-  double rho_cur = 0, rho_noise_cur = 0;  // call_rho, call_rho_noise of the call being planned
+  int64_t fe_base = 0, fu_base = 0;      // the envelope and uniform areas of fl
+  std::vector<SgEnvTask> envtasks;
+  std::vector<float> ustream;
+  std::vector<SgUJob> ujobs;
+  std::vector<double> elog2;  // log2(k), k = 1..max nr
+};
+
+// The per-call state of a Batch at one moment: an array's size, a counter's value.
+struct BatchMark {
+#define X(kind, T, name, reserve) std::conditional_t<pk_counter(PK::kind), T, int64_t> name{};
+#define XP(kind, T, name, reserve) int64_t name[2]{};
+  SG_PLAN_CALLS(X) SG_PLAN_SUMS(X) SG_BATCH_STATE(X, X, XP)
+#undef XP
+#undef X
 };
 
 // Plan one generateHarmonics() call; the finalized syllable is written at
@@ -246,8 +299,6 @@ void tile_syllables(Batch& B, int first_syl);
 
 // Plan one soundgen() call (R/soundgen.R:208-862); returns the bout length.
 int64_t plan_soundgen(Batch& B, const sg_soundgen_args& a, Rng& R, int64_t out_off, int first_syl);
-// Roll back soundgen-specific batch state after a failed call.
-void restore_soundgen_tail(Batch& B, int first_syl);
 // Build derived tables (piece tiles) once all calls are planned.
 void finalize_plan(Batch& B);
 void finalize_spec(Batch& B);

@@ -807,8 +807,6 @@ int64_t plan_soundgen(Batch& B, const sg_soundgen_args& a_in, Rng& R, int64_t ou
   return total + 2 * nsil;
 }
 
-void restore_soundgen_tail(Batch&, int) {}
-
 }  // namespace sg
 
 extern "C" int sg_set_fp64_policy(int32_t mode, double rho) {

@@ -292,6 +292,20 @@ def test_parallel_plan_output_byte_equal(monkeypatch):
     assert np.array_equal(y1.view(np.uint32), y7.view(np.uint32))
 
 
+def test_failed_call_does_not_change_the_next():
+    """A call that fails after creating an FFT geometry (test_planner._rollback_calls)
+    leaves nothing in the plan: the call behind it synthesizes exactly the samples it
+    gives alone."""
+    from test_planner import _rollback_calls
+    from soundgen_beta_amd import batch, native
+    good, bad = _rollback_calls()
+    alone = batch.synthesize([good], device=0)[0]
+    err, y = batch.synthesize([bad, good], device=0)
+    assert isinstance(err, native.SoundgenError)
+    assert len(alone) == 4800
+    assert np.array_equal(y, alone)
+
+
 def test_sharded_batch_byte_equal():
     """bench.py's strong scaling splits ONE batch over ranks (dist.shard, LPT).
     Every call synthesizes the same bytes whether planned in the whole batch or in

@@ -116,6 +116,39 @@ def test_parallel_planning_equals_serial(monkeypatch):
         assert s1[k] == s7[k], k
 
 
+def _rollback_calls():
+    """(good, bad): two soundgen calls with the same 640-point window. bad plans its
+    unvoiced noise, which creates that window's FFT geometry (twiddles and windows in
+    fl), then fails in plan_envelope with SG_E_UNSUPPORTED (-4): more than 128 formant
+    tracks."""
+    U = np.random.default_rng(1).uniform(size=400000)
+
+    def call(formants):
+        return {"kind": "soundgen", "uniforms": U, "args": dict(
+            sylLen=300, samplingRate=16000, temperature=0, addSilence=0, windowLength=40, overlap=75,
+            formants=formants, pitchAnchors=[150.0, 170.0],
+            noiseAnchors={"time": [0, 300], "value": [-20.0, -20.0]}, formantsNoise=None)}
+    bad = call({"f%d" % (i + 1): {"time": 0, "freq": 300 + 50 * i, "amp": 20, "width": 100} for i in range(140)})
+    return call("a"), bad
+
+
+@pytest.mark.parametrize("threads,reps", [("1", 1), ("1", 16), ("2", 16)], ids=["one", "serial", "parts"])
+def test_failed_call_leaves_nothing_behind(monkeypatch, threads, reps):
+    """A call that fails after creating an FFT geometry is rolled back whole (every row
+    of SG_PLAN_STATE, sg_plan.h): the good calls behind it plan exactly as they do
+    without it, serially and in parts of [bad, good] (2 threads: 16 parts of 2 calls)."""
+    good, bad = _rollback_calls()
+    monkeypatch.setenv("SG_PLAN_THREADS", threads)
+    p = batch.Plan([bad, good] * reps, None)
+    q = batch.Plan([good] * reps, None)
+    assert list(p.status) == [-4, 0] * reps, p.message(0)
+    assert (q.status == 0).all()
+    assert p.device_bytes() == q.device_bytes()
+    assert p.stats() == q.stats()
+    assert np.array_equal(p.lengths[1::2], q.lengths) and np.array_equal(p.offsets[1::2], q.offsets)
+    assert q.lengths.min() > 0
+
+
 def test_fast_zero_crossing_search_equals_exact(tmp_path):
     """The crossFade zero-crossing search evaluates the epoch waveform by Clenshaw
     with an error bound and falls back to R's row-by-row sum near zero
