@@ -1122,6 +1122,65 @@ int sg_debug_analyze_sweep_kernel_ms(double* out);
  * sg_compare_sounds_pairs (2 doubles). */
 int sg_debug_mel_pair_kernel_ms(double* out);
 
+/* ---- stft(), istft() and invert_spectrogram(): sound from a spectrogram (an additive
+ * extension of ABI 5; no reference counterpart). p is spectrogram()'s parameter block and
+ * binds the same decisions: wl, the pad of zp, N = wl + 2 pad, M = N / 2 bins, the frame
+ * starts of getFrameBank's seq(), the window; smoothing, denoising, method and output are not
+ * read beyond their validation. Every refusal of sg_spectrogram_size applies with the same
+ * code and text, before anything is launched and before ctx is looked at.
+ *
+ * A spectrum is stored frame after frame with `rows` cells a frame: rows = M (the shape of
+ * spectrogram()'s matrix: DC in, Nyquist out) or M + 1 (with the Nyquist bin); anything else is
+ * SG_E_ARG. A complex cell is two doubles (re, im).
+ *   Analysis A: frame i is w[t] x[s_i + t], zero-padded as getFrameBank pads it; bins 0 .. M of
+ *   its N-point DFT, unscaled.
+ *   Synthesis A+ (least squares): the M + 1 bins extended Hermitian (a missing Nyquist bin is
+ *   0), the real part of the inverse DFT / N, the pad dropped, then x^[t] = sum_i w[t - s_i]
+ *   y_i[t - s_i] / sum_i w[t - s_i]^2 over the frames that cover t, in frame order. A sample whose
+ *   denominator is 0 (no frame covers it, or only zeros of the window do) is 0. No other floor.
+ * The sound that comes back is in the domain of getFrameBank's normalised sound: the original
+ * scale is not in a spectrogram. */
+/* Host only, no device: for a sound of len samples wl, n_fft, bins (= M) and frames as
+ * sg_spectrogram_size gives them, the samples A+ returns (len), and the bytes of workspace the
+ * sound takes inside sg_spg_istft_batch / sg_invert_spectrogram_batch. rows: 0, or a row
+ * count to validate. */
+int sg_invert_size(int64_t len, const sg_spectrogram_params* p, int32_t rows, int32_t* wl, int32_t* n_fft, int32_t* bins,
+                   int32_t* frames, int64_t* samples, int64_t* workspace_bytes);
+/* The message of the calling thread's last failed sg_invert_size ("" if none). */
+const char* sg_invert_size_error(void);
+/* A of n_calls sounds in DEVICE memory (call c: lengths[c] samples at offsets[c] of d_wave,
+ * fp32, or fp64 when is_f64), each normalised as getFrameBank normalises it (the statistics are
+ * spectrogram()'s, bit for bit). d_out (device): call c's frames x rows complex cells at complex
+ * cell out_off[c]. A sound shorter than the window has no frames. */
+int sg_spg_stft_batch(sg_ctx* ctx, const void* d_wave, int32_t is_f64, const int64_t* offsets, const int64_t* lengths,
+                      int64_t n_calls, const sg_spectrogram_params* p, int32_t rows, double* d_out,
+                      const int64_t* out_off);
+/* A+ of n_calls spectra in DEVICE memory (call c: frames x rows complex cells at complex cell
+ * spec_off[c] of d_spec, frames as sg_invert_size gives them for lengths[c]). d_out (device)
+ * receives lengths[c] doubles at out_off[c]. */
+int sg_spg_istft_batch(sg_ctx* ctx, const double* d_spec, const int64_t* spec_off, const int64_t* lengths, int64_t n_calls,
+                       const sg_spectrogram_params* p, int32_t rows, double* d_out, const int64_t* out_off);
+/* Griffin & Lim's alternating projections on n_calls magnitude matrices in DEVICE memory (call
+ * c: frames x rows doubles at mag_off[c] of d_mag, as sg_spectrogram_batch leaves them; d_phase:
+ * the initial phases in the same layout, or NULL for zero). X_0 = S exp(i phi_0); n_iter times
+ * x = A+ X, Z = A x, X = S Z / |Z| on the constrained bins (X = S where |Z| = 0; the Nyquist bin of
+ * an M-row matrix is unconstrained, starts at 0 and is carried through); d_out (device) receives
+ * A+ X, lengths[c] doubles at out_off[c], and serves as x in between. err_out (host, n_calls x
+ * n_iter doubles, call-major, or NULL): e_k = sqrt(sum (|A x_k| - S)^2 / sum S^2) over the
+ * constrained bins, k = 1 .. n_iter (NaN for a sound without frames or with S = 0). The batch
+ * runs in chunks of consecutive sounds whose workspaces (sg_invert_size) fit workspace_cap bytes
+ * (0: 1 GiB; at least one sound a chunk); one launch sequence per iteration serves a chunk, with
+ * no wait inside the loop. A sound's samples and errors are the same bit for bit alone, in any
+ * batch, at any position and under any cap. SG_E_ARG for a negative or NaN magnitude. */
+int sg_invert_spectrogram_batch(sg_ctx* ctx, const double* d_mag, const int64_t* mag_off, const double* d_phase,
+                                const int64_t* lengths, int64_t n_calls, const sg_spectrogram_params* p, int32_t rows,
+                                int32_t n_iter, int64_t workspace_cap, double* d_out, const int64_t* out_off,
+                                double* err_out);
+/* The device milliseconds of the last of the three on a context with sg_set_profiling on, summed
+ * over iterations and chunks (6 doubles): normalisation statistics, the forward frames (with the
+ * projection inside the iteration), X_0, the inverse frames, the overlap-add, the error fold. */
+int sg_debug_invert_kernel_ms(double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -126,6 +126,17 @@ def lib():
         L.sg_spectrogram.argtypes = [vp, dp, i64, spp, dp]
         L.sg_spectrogram_batch.argtypes = [vp, vp, i64p, i64p, i64, spp, vp, i64p, i32p, i32p]
         L.sg_debug_spectrogram_kernel_ms.argtypes = [dp]
+    if hasattr(L, "sg_invert_size"):  # stft(), istft(), invert_spectrogram(): likewise additive
+        i32p = C.POINTER(C.c_int32)
+        spp = C.POINTER(_abi.sg_spectrogram_params)
+        L.sg_invert_size.argtypes = [i64, spp, C.c_int32, i32p, i32p, i32p, i32p, i64p, i64p]
+        L.sg_invert_size_error.argtypes = []
+        L.sg_invert_size_error.restype = C.c_char_p
+        L.sg_spg_stft_batch.argtypes = [vp, vp, C.c_int32, i64p, i64p, i64, spp, C.c_int32, vp, i64p]
+        L.sg_spg_istft_batch.argtypes = [vp, vp, i64p, i64p, i64, spp, C.c_int32, vp, i64p]
+        L.sg_invert_spectrogram_batch.argtypes = [vp, vp, i64p, vp, i64p, i64, spp, C.c_int32, C.c_int32, i64, vp, i64p,
+                                                  dp]
+        L.sg_debug_invert_kernel_ms.argtypes = [dp]
     if hasattr(L, "sg_debug_fft64"):  # the fp64 transform alone (tests/test_fft64.py): likewise additive
         L.sg_debug_fft64.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, dp, dp]
     if hasattr(L, "sg_debug_sine_bank"):  # the sine-bank kernels on caller-built tasks (tests/test_sine_bank.py)
