@@ -164,13 +164,6 @@ __device__ __forceinline__ bool peak_at(const double* a, int c, int h, double v)
 }
 
 template <typename T>
-__device__ __forceinline__ double norm_sample(const T* xc, int64_t i, const SpgStat& st) {
-  double s = (double)xc[i];
-  if (st.scaled) s = (s - st.mean) / st.sd;
-  return s / st.m;
-}
-
-template <typename T>
 __global__ __launch_bounds__(kT) void sg_anl_ampl(const T* __restrict__ x, const AnlFrame* __restrict__ frames,
                                                   const AnlSound* __restrict__ snds, const SpgStat* __restrict__ stat,
                                                   int wl, int cols, double* __restrict__ out,
@@ -182,7 +175,7 @@ __global__ __launch_bounds__(kT) void sg_anl_ampl(const T* __restrict__ x, const
   const T* xc = x + S.base + F.a;  // host: F.a + wl < S.len
   double acc = 0;
   for (int i = threadIdx.x; i <= wl; i += kT) {
-    const double v = norm_sample(xc, i, st);
+    const double v = sg::spg_normalise((double)xc[i], st);
     acc += v * v;
   }
   acc = block_reduce<kT>(acc, 0, red);
@@ -379,7 +372,7 @@ __global__ __launch_bounds__(kT) void sg_anl_acf(const T* __restrict__ x, const 
   double acc = 0;
   if (threadIdx.x < 4) xw[wl + threadIdx.x] = 0.0;  // the zeros the lag groups run into
   for (int i = threadIdx.x; i < wl; i += kT) {
-    const double v = norm_sample(xc, i, st) * win[i];
+    const double v = sg::spg_normalise((double)xc[i], st) * win[i];
     xw[i] = v;
     acc += v;
   }
@@ -474,8 +467,8 @@ struct PitchK {
 // the peaks, the 1.8 rule, the order, the discount. Row i (1-based) of the reference's
 // table holds DFT bin i - 1 and is labelled samplingRate / i / 2 * (L / B); cepf holds
 // the labels of the band's rows, which are bins [c0, c0 + nc).
-// LDS: two M-point buffers, fft64's 32 radix roots, l + 1 doubles (|C_k|, k <= L / 2:
-// by conjugate symmetry they hold the maximum over all L bins)
+// LDS: fft64_lds_bytes(M), then l + 1 doubles (|C_k|, k <= L / 2: by conjugate symmetry
+// they hold the maximum over all L bins)
 __global__ __launch_bounds__(kT) void sg_anl_cep(const AnlFrame* __restrict__ frames, const AnlSound* __restrict__ snds,
                                                  const double* __restrict__ Z, const double2* __restrict__ TN,
                                                  const double* __restrict__ cepf, PitchK K, double* __restrict__ out) {
@@ -483,10 +476,9 @@ __global__ __launch_bounds__(kT) void sg_anl_cep(const AnlFrame* __restrict__ fr
   __shared__ double red[kT];
   __shared__ int npk;
   const int M = K.M, B = K.B, nl = K.nc;
-  double2* a = lds_cep;
-  double2* b = a + M;
-  double2* rt = b + M;
-  double* cep = reinterpret_cast<double*>(rt + 32);
+  const Fft64Lds L = fft64_carve(lds_cep, M);
+  double2 *a = L.a, *b = L.b, *rt = L.rt;
+  double* cep = static_cast<double*>(L.end);
   const AnlFrame F = frames[blockIdx.x];
   const AnlSound S = snds[F.snd];
   double* row = out + S.row0 + (int64_t)F.f * K.cols;
@@ -501,10 +493,7 @@ __global__ __launch_bounds__(kT) void sg_anl_cep(const AnlFrame* __restrict__ fr
       a[n] = make_double2(j >= 0 && j < B ? z[j] / mx : 0.0, 0.0);
     }
   } else {
-    for (int n = threadIdx.x; n < M; n += kT) {
-      const int j = 2 * n - K.pad;
-      a[n] = make_double2(j >= 0 && j < B ? z[j] / mx : 0.0, j + 1 >= 0 && j + 1 < B ? z[j + 1] / mx : 0.0);
-    }
+    load_packed64(a, M, K.pad, B, [z, mx](int j) { return z[j] / mx; });
   }
   if (threadIdx.x == 0) npk = 0;
   __syncthreads();
@@ -512,17 +501,14 @@ __global__ __launch_bounds__(kT) void sg_anl_cep(const AnlFrame* __restrict__ fr
   if (K.odd) {
     for (int k = threadIdx.x; k <= K.l; k += kT) cep[k] = hypot(a[k].x, a[k].y);
   } else {
-    // X_k = E_k + W_L^k O_k as in sg_spg_frames; X_M = Re Z_0 - Im Z_0
+    // |X_k| of the packed frame; X_M = Re Z_0 - Im Z_0, its own branch: without the rounding of W_L^M
     for (int k = threadIdx.x; k <= M; k += kT) {
       if (k == M) {
         cep[k] = fabs(a[0].x - a[0].y);
         continue;
       }
-      const double2 p = a[k], q = a[k == 0 ? 0 : M - k], w = TN[k];
-      const double2 e = make_double2(0.5 * (p.x + q.x), 0.5 * (p.y - q.y));
-      const double2 o = make_double2(0.5 * (p.y + q.y), -0.5 * (p.x - q.x));
-      const double re = e.x + (o.x * w.x - o.y * w.y), im = e.y + (o.x * w.y + o.y * w.x);
-      cep[k] = hypot(re, im);
+      const double2 X = untangle64(a, k, M, TN);
+      cep[k] = hypot(X.x, X.y);
     }
   }
   __syncthreads();
@@ -853,12 +839,6 @@ void check_tail_row(const sg::PathPars& P, int cols, int nCands, bool also) {
     throw sg::SgError(SG_E_DEVICE, "analyze: the tail's setup leaves the row");
 }
 
-template <class K>
-void allow_dyn_lds(K kernel, int lds) {
-  if (lds > 48 * 1024)
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-}
-
 // The frames of the sounds of one launch sequence, sound after sound, and where each sound's lie
 struct FrameList {
   std::vector<AnlFrame> fr;
@@ -951,7 +931,7 @@ void candidate_stages(DevBuf& db, hipStream_t s, FrameGroup<T>& G, const sg::Anl
     if (acf == kAcfFromStore) {
       const int lds = A.nlag * (int)(sizeof(double) + sizeof(int));
       launch(kCsPeaks, [&]() {
-        allow_dyn_lds(&sg_anl_acf_peaks, lds);
+        sg::lds_opt_in(&sg_anl_acf_peaks, lds, "sg_anl_acf_peaks");
         hipLaunchKernelGGL(sg_anl_acf_peaks, gF, bT, (size_t)lds, s, G.fr, d_snd, d_store, d_lagf, K, d_out);
       });
     } else {
@@ -960,7 +940,7 @@ void candidate_stages(DevBuf& db, hipStream_t s, FrameGroup<T>& G, const sg::Anl
       const int lds = (wl + 4 + A.nlag) * (int)sizeof(double);
       const auto kernel = acf == kAcfStore ? &sg_anl_acf<T, true> : &sg_anl_acf<T, false>;
       launch(kCsAcf, [&]() {
-        allow_dyn_lds(kernel, lds);
+        sg::lds_opt_in(kernel, lds, "sg_anl_acf");
         hipLaunchKernelGGL(kernel, gF, bT, (size_t)lds, s, G.x, G.fr, d_snd, G.stat, G.win, d_filt, d_lagf, K, d_out,
                            acf == kAcfStore ? d_store : nullptr);
       });
@@ -975,8 +955,8 @@ void candidate_stages(DevBuf& db, hipStream_t s, FrameGroup<T>& G, const sg::Anl
     double2* d_TN = db.get<double2>((size_t)N);
     const double* d_cepf = upload(db, Q.cepf, s);
     sg::fill_roots64(d_TN, N, s);
-    const int lds = (2 * X.M + 32) * (int)sizeof(double2) + (X.l + 1) * (int)sizeof(double);
-    allow_dyn_lds(&sg_anl_cep, lds);
+    const int lds = fft64_lds_bytes(X.M) + (X.l + 1) * (int)sizeof(double);
+    sg::lds_opt_in(&sg_anl_cep, lds, "sg_anl_cep");
     launch(kCsCep, [&]() { hipLaunchKernelGGL(sg_anl_cep, gF, bT, (size_t)lds, s, G.fr, d_snd, G.Z, d_TN, d_cepf, X, d_out); });
   }
   mark(kCsBana, false);

@@ -1550,9 +1550,9 @@ __device__ __forceinline__ float fade_in_out(int lf, int64_t L, int64_t k) {  //
 //            the overlap-add (sg_ola; that round-off is relative to the filtered
 //            output, ~1e-8 RMS)
 // The transform (fft64: Stockham autosort, out of place between two M-point LDS
-// buffers, 35 KB for wl = 2204: 4 workgroups per CU) and the contract of its table
-// of roots are in sg_fft64_dev.h, shared with spectrogram()'s frames
-// (sg_spectrogram.hip). One table per window length (sg_roots64), L2-resident.
+// buffers, 35 KB for wl = 2204: 4 workgroups per CU), the contract of its table of
+// roots, the LDS layout and the untangling are in sg_fft64_dev.h, shared with the
+// analysis features. One table per window length (sg_roots64), L2-resident.
 
 // Per window length N = 2M of the plan's fp64 frames: W_N^t = exp(-2 pi i t / N), t < N,
 // then seewave's hamming and hanning (ftwindow) as pairs (w[2n], w[2n + 1]), n < M
@@ -1579,9 +1579,8 @@ extern "C" __global__ __launch_bounds__(SG_F64_THREADS) void sg_fft_frames64(
   const SgFrame64 F = frames[blockIdx.x];
   const int N = F.wl, M = N / 2;
   const double2* __restrict__ TN = tabs + frame_tab[blockIdx.x];
-  double2* a = lds64;        // M points
-  double2* b = a + M;        // M points
-  double2* rt = b + M;       // radix roots (<= 31)
+  const Fft64Lds L = fft64_carve(lds64, M);
+  double2 *a = L.a, *b = L.b, *rt = L.rt;
   const double2* __restrict__ ham = TN + N;  // window pairs (sg_roots64)
   const double2* __restrict__ han = ham + M;
   const bool noise = F.mode == SG_F64_NOISE;
@@ -1601,10 +1600,7 @@ extern "C" __global__ __launch_bounds__(SG_F64_THREADS) void sg_fft_frames64(
   const float* uni = fl + F.src;
   auto Yat = [&](int kk) -> double2 {  // Y_kk, 0 <= kk < M
     if (noise) return make_double2((double)uni[kk] * (double)env[kk], 0.0);
-    const double2 p = a[kk], q = a[kk == 0 ? 0 : M - kk], w = TN[kk];
-    const double2 e = make_double2(0.5 * (p.x + q.x), 0.5 * (p.y - q.y));
-    const double2 o = make_double2(0.5 * (p.y + q.y), -0.5 * (p.x - q.x));
-    const double2 xk = make_double2(e.x + (o.x * w.x - o.y * w.y), e.y + (o.x * w.y + o.y * w.x));
+    const double2 xk = untangle64(a, kk, M, TN);
     const double sc = invN * (double)env[kk];
     return make_double2(xk.x * sc, xk.y * sc);
   };
@@ -2023,27 +2019,10 @@ extern "C" __global__ __launch_bounds__(256) void sg_mix_hp(const SgMixTile* __r
 #include "sg_exec.h"
 #include "sg_launch.h"
 
-#include <map>
-#include <mutex>
 namespace sg {
-// Dynamic LDS above 64 KB must be opted into (160 KB per CU on gfx950). The
-// attribute is per device: remember the opted-in size per (kernel, device).
-static void lds_opt_in(const void* fn, int lds_bytes, const char* name) {
-  static std::mutex mu;
-  static std::map<std::pair<const void*, int>, int> done;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) throw SgError(SG_E_DEVICE, std::string(name) + ": hipGetDevice failed");
-  std::lock_guard<std::mutex> lk(mu);
-  int& have = done[{fn, dev}];
-  if (lds_bytes <= have) return;
-  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess)
-    throw SgError(SG_E_DEVICE, std::string(name) + ": dynamic LDS " + std::to_string(lds_bytes) + " B refused");
-  have = lds_bytes;
-}
-
 void launch_fft_frames(const DevicePlan& D, int64_t g0, int64_t n_groups, int lds_bytes, hipStream_t s) {
   if (n_groups <= 0) return;
-  lds_opt_in(reinterpret_cast<const void*>(&sg_fft_frames), lds_bytes, "sg_fft_frames");
+  lds_opt_in(&sg_fft_frames, lds_bytes, "sg_fft_frames");
   hipLaunchKernelGGL(sg_fft_frames, dim3((unsigned)n_groups), dim3(SG_FFT_THREADS), lds_bytes, s, D.fgroups + g0,
                      D.frames,
                      D.geoms, D.fl, D.fs);
@@ -2052,7 +2031,7 @@ void launch_fft_frames(const DevicePlan& D, int64_t g0, int64_t n_groups, int ld
 void launch_stft_ola(const DevicePlan& D, int phase, int64_t s0, int64_t n_segs, int lds_bytes, hipStream_t s) {
   if (n_segs <= 0) return;
   auto* k = phase == 0 ? &sg_stft_ola_noise : &sg_stft_ola;
-  lds_opt_in(reinterpret_cast<const void*>(k), lds_bytes, phase == 0 ? "sg_stft_ola_noise" : "sg_stft_ola");
+  lds_opt_in(k, lds_bytes, phase == 0 ? "sg_stft_ola_noise" : "sg_stft_ola");
   const int W = sg_fft_waves(phase);
   if (n_segs % W) throw SgError(SG_E_DEVICE, "sg_stft_ola: segment count not a multiple of the workgroup's waves");
   hipLaunchKernelGGL(k, dim3((unsigned)(n_segs / W)), dim3(W * 64), lds_bytes, s,
@@ -2081,15 +2060,15 @@ void launch_fft_frames64(const DevicePlan& D, int ph, hipStream_t s) {
   const int64_t nw = D.x.frames64_w[ph];
   if (nw > 0) {
     const int lds = SG_F64W_WAVES * SG_F64W_M * (int)sizeof(double2);  // a frame per wave
-    lds_opt_in(reinterpret_cast<const void*>(&sg_fft_frames64w), lds, "sg_fft_frames64w");
+    lds_opt_in(&sg_fft_frames64w, lds, "sg_fft_frames64w");
     hipLaunchKernelGGL(sg_fft_frames64w, dim3((unsigned)((nw + SG_F64W_WAVES - 1) / SG_F64W_WAVES)),
                        dim3(SG_F64W_WAVES * 64), lds, s, D.frames64 + f0, nw, D.frames64_tab + f0,
                        reinterpret_cast<const double2*>(D.roots64), D.fl, D.fh, D.fs);
     SG_LAUNCHED("sg_fft_frames64w");
   }
   if (nf - nw <= 0) return;
-  const int lds = (D.x.frames64_maxwl + 32) * (int)sizeof(double2);  // two M-point buffers + radix roots
-  lds_opt_in(reinterpret_cast<const void*>(&sg_fft_frames64), lds, "sg_fft_frames64");
+  const int lds = fft64_lds_bytes(D.x.frames64_maxwl / 2);  // the longest frame's, M = wl / 2 as in the kernel
+  lds_opt_in(&sg_fft_frames64, lds, "sg_fft_frames64");
   hipLaunchKernelGGL(sg_fft_frames64, dim3((unsigned)(nf - nw)), dim3(SG_F64_THREADS), lds, s, D.frames64 + f0 + nw,
                      D.frames64_tab + f0 + nw, reinterpret_cast<const double2*>(D.roots64), D.fl, D.fh, D.fs);
   SG_LAUNCHED("sg_fft_frames64");

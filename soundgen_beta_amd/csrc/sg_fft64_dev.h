@@ -1,9 +1,17 @@
-// sg_fft64_dev.h — the fp64 complex transform that sg_fft.hip (the fp64 formant
-// filter frames, sg_fft_frames64), sg_spectrogram.hip (spectrogram()'s frames) and
-// sg_segment.hip (the rows and columns of segment()'s whole-sound transform)
-// share on the device: an M-point mixed-radix Stockham FFT (radices 2, 4 and the
-// odd primes <= 31, M <= 2048) of one frame per SG_F64_THREADS-thread workgroup,
-// and the contract of its table of roots. Included by .hip files only.
+// sg_fft64_dev.h — the fp64 transforms that five files share on the device: sg_fft.hip (the fp64
+// formant filter frames, sg_fft_frames64), sg_spectrogram.hip (spectrogram()'s frames),
+// sg_invert.hip (stft(), istft(), invert_spectrogram()), sg_analyze.hip (the cepstral tracker)
+// and sg_segment.hip (the rows and columns of segment()'s whole-sound transform). One frame per
+// SG_F64_THREADS-thread workgroup. Included by .hip files only.
+//
+//   fft64            the complex transform: an M-point mixed-radix Stockham FFT (radices 2, 4 and
+//                    the odd primes <= 31, M <= 2048), and the contract of its table of roots
+//   fft64_lds_bytes  the dynamic LDS of an M-point frame (host and device), and
+//   fft64_carve      its layout: two M-point buffers, the radix roots, then the caller's own
+//   load_packed64    N = 2M real points, zero-padded, as z_n = s(2n - pad) + i s(2n + 1 - pad)
+//   untangle64       X_k, 0 <= k <= M, of those N real points from the M-point transform of z
+// The inverse packing (the Hermitian extension fed to the inverse transform) is not here:
+// sg_inv_frames and sg_fft_frames64 extend differently and round differently.
 //
 // Stockham autosort, out of place between two M-point LDS buffers. Per stage of
 // radix R: (a) every input times its twiddle, in place; (b) odd R: one work item
@@ -20,7 +28,20 @@
 #include <hip/hip_runtime.h>
 
 constexpr int SG_F64_THREADS = 256;  // threads per fp64 frame (r04: 128 / 512 / 1,024 slower)
+constexpr int SG_F64_MAX_RADIX = 31;   // fft64's largest radix
+constexpr int SG_F64_ROOT_SLOTS = 32;  // W_R^t, t < R, of the stage under way: the largest radix, rounded up
+static_assert(SG_F64_MAX_RADIX <= SG_F64_ROOT_SLOTS, "a stage's roots fill rt[0 .. R)");
 namespace {
+// Bytes of dynamic LDS an M-point frame needs, and how they are laid out: a, b (M points each),
+// rt (SG_F64_ROOT_SLOTS), and `end`, the first byte behind them, for what the kernel adds
+__host__ __device__ constexpr int fft64_lds_bytes(int M) { return (2 * M + SG_F64_ROOT_SLOTS) * (int)sizeof(double2); }
+struct Fft64Lds {
+  double2 *a, *b, *rt;
+  void* end;
+};
+__device__ __forceinline__ Fft64Lds fft64_carve(double2* lds, int M) {
+  return Fft64Lds{lds, lds + M, lds + 2 * M, lds + 2 * M + SG_F64_ROOT_SLOTS};
+}
 // W_N^t as the tables hold it (sincospi: exact at the quadrant points)
 __device__ __forceinline__ double2 root64(int t, int N) {
   double sn, cs;
@@ -102,7 +123,8 @@ __device__ void stage64(double2* __restrict__ src, double2* __restrict__ dst, in
   }
   __syncthreads();
 }
-// M-point complex DFT of *a (result in *a, *b scratch); TN: W_N^t (t < 2M), global; rt: LDS (32)
+// M-point complex DFT of *a (result in *a, *b scratch); TN: W_N^t (t < 2M), global; rt: LDS
+// (SG_F64_ROOT_SLOTS points: every rt[threadIdx.x] below is written for threadIdx.x < R <= SG_F64_MAX_RADIX)
 __device__ void fft64(double2*& a, double2*& b, int M, const double2* __restrict__ TN,
                                    double2* __restrict__ rt, bool inv) {
   if (M == 1102) {  // 2 x 19 x 29, the stage order of the loop below, sizes folded
@@ -120,7 +142,7 @@ __device__ void fft64(double2*& a, double2*& b, int M, const double2* __restrict
   while (rest > 1) {
     int R = rest % 4 == 0 ? 4 : rest % 2 == 0 ? 2 : 0;
     if (!R)
-      for (int p : {3, 5, 7, 11, 13, 17, 19, 23, 29, 31})
+      for (int p : {3, 5, 7, 11, 13, 17, 19, 23, 29, SG_F64_MAX_RADIX})
         if (rest % p == 0) { R = p; break; }
     if (R != 2 && R != 4) {  // odd radix: W_R^t = W_N^(t 2M / R), t < R
       if (threadIdx.x < R) rt[threadIdx.x] = TN[threadIdx.x * (2 * M / R)];
@@ -137,5 +159,27 @@ __device__ void fft64(double2*& a, double2*& b, int M, const double2* __restrict
     Ns *= R;
     rest /= R;
   }
+}
+// N = 2M real points s(j - pad), j - pad in [0, len), zeros around them, packed for fft64:
+// a[n] = s(2n - pad) + i s(2n + 1 - pad), n < M. sample(j), 0 <= j < len, gives s(j).
+template <class Sample>
+__device__ __forceinline__ void load_packed64(double2* a, int M, int pad, int len, Sample&& sample) {
+  for (int n = threadIdx.x; n < M; n += SG_F64_THREADS) {
+    double v[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int j = 2 * n + h - pad;
+      v[h] = j >= 0 && j < len ? sample(j) : 0.0;
+    }
+    a[n] = make_double2(v[0], v[1]);
+  }
+}
+// X_k, 0 <= k <= M, of the N real points from a = fft64 of their packing:
+// X_k = E_k + W_N^k O_k, E = (Z_k + conj Z_{M-k}) / 2, O = -i (Z_k - conj Z_{M-k}) / 2; Z_M = Z_0, W_N^M = TN[M]
+__device__ __forceinline__ double2 untangle64(const double2* a, int k, int M, const double2* __restrict__ TN) {
+  const double2 p = a[k == M ? 0 : k], q = a[(k == 0 || k == M) ? 0 : M - k], w = TN[k];
+  const double2 e = make_double2(0.5 * (p.x + q.x), 0.5 * (p.y - q.y));
+  const double2 o = make_double2(0.5 * (p.y + q.y), -0.5 * (p.x - q.x));
+  return make_double2(e.x + (o.x * w.x - o.y * w.y), e.y + (o.x * w.y + o.y * w.x));
 }
 }  // namespace

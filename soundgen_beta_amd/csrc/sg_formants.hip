@@ -60,10 +60,8 @@ struct FmtK {
 
 template <typename T>
 __device__ __forceinline__ double fmt_sample(const T* xc, int i, const SpgStat& st, const double* __restrict__ win, int windowed) {
-  double s = (double)xc[i];
-  if (!windowed) return s;
-  if (st.scaled) s = (s - st.mean) / st.sd;  // as norm_sample of sg_analyze.hip
-  return s / st.m * win[i];
+  const double s = (double)xc[i];
+  return windowed ? sg::spg_normalise(s, st) * win[i] : s;
 }
 
 // LDS: n + kLagPad doubles (the frame), 4 * ceil((order + 1) / 4) * kLagSegs doubles (the segment sums)
@@ -78,7 +76,7 @@ __global__ __launch_bounds__(kT) void sg_fmt_lags(const T* __restrict__ x, const
   const int n = K.n, p = K.order;
   double* y = lds_fmt;
   double* part = lds_fmt + n + kLagPad;
-  SpgStat st{0, 1, 1, 0, 0, 0, 0};
+  SpgStat st = sg::kSpgStatIdentity;
   if (K.windowed) st = stat[F.snd];
   const T* xc = x + F.x0;  // host: the frame's n samples lie in the buffer
   double acc = 0;

@@ -8,9 +8,8 @@
 // A spectrum is kept frame after frame, `rows` bins a frame (rows = M: the reference's
 // shape, or M + 1 with the Nyquist bin), complex cells as double2.
 //
-//   sg_inv_stft     one workgroup per frame: sg_spg_frames' front end (normalisation on the
-//                   fly or none, the window, zero padding, the packed real transform, the
-//                   untangling) storing X_k, k < rows, as double2
+//   sg_inv_stft     one workgroup per frame: sg_spg_frames' body (spg_forward_frame,
+//                   sg_spectrogram_dev.h) storing X_k, k < rows, as double2
 //   sg_inv_project  the same transform of the iteration's sound (no normalisation: that
 //                   belongs to spectrogram()'s input, not to A) with the projection fused
 //                   behind it: X = S Z / |Z| on a constrained bin (X = S where |Z| = 0), X = Z
@@ -39,15 +38,16 @@
 #include <vector>
 
 #include "sg_dev64.h"
-#include "sg_fft64_dev.h"
 #include "sg_invert.h"
 #include "sg_launch.h"
 #include "sg_rmath.h"
-#include "sg_spectrogram.h"
+#include "sg_spectrogram_dev.h"
 
 namespace {
 
 using sg::DevBuf;
+using sg::lds_opt_in;
+using sg::SpgFrame;
 using sg::SpgStat;
 using sg::upload;
 
@@ -59,11 +59,6 @@ struct InvSound {
   int32_t f0, nf;      // frames [f0, f0 + nf) of the launch
 };
 
-struct InvFrame {
-  int64_t o;       // first sample within the sound
-  int32_t snd, f;  // sound, frame within the sound
-};
-
 struct InvTile {
   int32_t snd, c;  // samples [c kInvTile, (c + 1) kInvTile) of the sound
 };
@@ -71,53 +66,37 @@ struct InvTile {
 constexpr int kT = 256;
 static_assert(SG_F64_THREADS == kT && sg::kInvTile == kT, "fft64 strides by SG_F64_THREADS; a lane per sample of a tile");
 
-// A of one frame. stat == nullptr: the samples as they are. PROJECT: see the head of the file;
-// mag has mrows rows a frame, out M + 1, and part receives the frame's two sums.
-template <typename T, bool PROJECT>
-__device__ __forceinline__ void forward_frame(const T* __restrict__ x, const InvFrame* __restrict__ frames,
-                                              const InvSound* __restrict__ snds, const SpgStat* __restrict__ stat,
-                                              const double* __restrict__ win, const double2* __restrict__ TN, int wl,
-                                              int pad, int M, int rows, double2* __restrict__ out,
-                                              const double* __restrict__ mag, int mrows, double* __restrict__ part) {
+// A of a frame (spg_forward_frame); stat == nullptr: the samples as they are
+template <typename T>
+__global__ __launch_bounds__(kT) void sg_inv_stft(const T* __restrict__ x, const SpgFrame* __restrict__ frames,
+                                                  const InvSound* __restrict__ snds, const SpgStat* __restrict__ stat,
+                                                  const double* __restrict__ win, const double2* __restrict__ TN, int wl,
+                                                  int pad, int M, int rows, double2* __restrict__ out) {
   extern __shared__ double2 lds64[];
-  double2* a = lds64;
-  double2* b = a + M;
-  double2* rt = b + M;
-  const InvFrame F = frames[blockIdx.x];
+  const SpgFrame F = frames[blockIdx.x];
   const InvSound S = snds[F.snd];
-  SpgStat st{0, 1, 1, 0, 0, 0, 0};
-  if (stat) st = stat[F.snd];
-  const T* xc = x + S.xbase + F.o;  // host: F.o + wl <= S.len
-  for (int n = threadIdx.x; n < M; n += kT) {
-    double v[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int j = 2 * n + h - pad;
-      double s = 0;
-      if (j >= 0 && j < wl) {
-        s = (double)xc[j];
-        if (stat) {
-          if (st.scaled) s = (s - st.mean) / st.sd;
-          s = s / st.m;
-        }
-        s = s * win[j];
-      }
-      v[h] = s;
-    }
-    a[n] = make_double2(v[0], v[1]);
-  }
-  __syncthreads();
-  fft64(a, b, M, TN, rt, false);
-  // X_k = E_k + W_N^k O_k, E = (Z_k + conj Z_{M-k}) / 2, O = -i (Z_k - conj Z_{M-k}) / 2; Z_M = Z_0, W_N^M = -1
   double2* row = out + S.spec0 + (int64_t)F.f * rows;
-  const double* mrow = PROJECT ? mag + S.mag0 + (int64_t)F.f * mrows : nullptr;
+  // host: F.o + wl <= S.len
+  spg_forward_frame(lds64, x + S.xbase + F.o, stat ? stat + F.snd : nullptr, win, TN, wl, pad, M, rows,
+                    [row](int k, double re, double im) { row[k] = make_double2(re, im); });
+}
+
+// A of a frame of the iteration's sound with the projection behind it (see the head of the file):
+// mag has mrows rows a frame, X M + 1, and part receives the frame's two sums
+__global__ __launch_bounds__(kT) void sg_inv_project(const double* __restrict__ x, const SpgFrame* __restrict__ frames,
+                                                     const InvSound* __restrict__ snds, const double* __restrict__ win,
+                                                     const double2* __restrict__ TN, int wl, int pad, int M,
+                                                     double2* __restrict__ X, const double* __restrict__ mag, int mrows,
+                                                     double* __restrict__ part) {
+  extern __shared__ double2 lds64[];
+  __shared__ double red[kT];
+  const SpgFrame F = frames[blockIdx.x];
+  const InvSound S = snds[F.snd];
+  double2* row = X + S.spec0 + (int64_t)F.f * (M + 1);
+  const double* mrow = mag + S.mag0 + (int64_t)F.f * mrows;
   double num = 0, den = 0;
-  for (int k = threadIdx.x; k < rows; k += kT) {
-    const double2 p = a[k == M ? 0 : k], q = a[(k == 0 || k == M) ? 0 : M - k], w = TN[k];
-    const double2 e = make_double2(0.5 * (p.x + q.x), 0.5 * (p.y - q.y));
-    const double2 o = make_double2(0.5 * (p.y + q.y), -0.5 * (p.x - q.x));
-    double re = e.x + (o.x * w.x - o.y * w.y), im = e.y + (o.x * w.y + o.y * w.x);
-    if (PROJECT && k < mrows) {
+  spg_forward_frame(lds64, x + S.xbase + F.o, nullptr, win, TN, wl, pad, M, M + 1, [&](int k, double re, double im) {
+    if (k < mrows) {
       const double s = mrow[k], az = hypot(re, im), d = az - s;
       num += d * d;
       den += s * s;
@@ -130,32 +109,13 @@ __device__ __forceinline__ void forward_frame(const T* __restrict__ x, const Inv
       }
     }
     row[k] = make_double2(re, im);
+  });
+  num = block_reduce<kT>(num, 0, red);
+  den = block_reduce<kT>(den, 0, red);
+  if (threadIdx.x == 0) {
+    part[2 * (int64_t)blockIdx.x] = num;
+    part[2 * (int64_t)blockIdx.x + 1] = den;
   }
-  if constexpr (PROJECT) {
-    __shared__ double red[kT];
-    num = block_reduce<kT>(num, 0, red);
-    den = block_reduce<kT>(den, 0, red);
-    if (threadIdx.x == 0) {
-      part[2 * (int64_t)blockIdx.x] = num;
-      part[2 * (int64_t)blockIdx.x + 1] = den;
-    }
-  }
-}
-
-template <typename T>
-__global__ __launch_bounds__(kT) void sg_inv_stft(const T* __restrict__ x, const InvFrame* __restrict__ frames,
-                                                  const InvSound* __restrict__ snds, const SpgStat* __restrict__ stat,
-                                                  const double* __restrict__ win, const double2* __restrict__ TN, int wl,
-                                                  int pad, int M, int rows, double2* __restrict__ out) {
-  forward_frame<T, false>(x, frames, snds, stat, win, TN, wl, pad, M, rows, out, nullptr, 0, nullptr);
-}
-
-__global__ __launch_bounds__(kT) void sg_inv_project(const double* __restrict__ x, const InvFrame* __restrict__ frames,
-                                                     const InvSound* __restrict__ snds, const double* __restrict__ win,
-                                                     const double2* __restrict__ TN, int wl, int pad, int M,
-                                                     double2* __restrict__ X, const double* __restrict__ mag, int mrows,
-                                                     double* __restrict__ part) {
-  forward_frame<double, true>(x, frames, snds, nullptr, win, TN, wl, pad, M, M + 1, X, mag, mrows, part);
 }
 
 // err[c n_iter + it] of sound c = c0 + its index in the chunk: one wave per sound, lane l adds the
@@ -174,10 +134,10 @@ __global__ __launch_bounds__(64) void sg_inv_fold(const double* __restrict__ par
   if (threadIdx.x == 0) err[(c0 + blockIdx.x) * n_iter + it] = sqrt(num / den);
 }
 
-__global__ __launch_bounds__(kT) void sg_inv_start(const InvFrame* __restrict__ frames, const InvSound* __restrict__ snds,
+__global__ __launch_bounds__(kT) void sg_inv_start(const SpgFrame* __restrict__ frames, const InvSound* __restrict__ snds,
                                                    const double* __restrict__ mag, const double* __restrict__ phase, int M,
                                                    int mrows, double2* __restrict__ X, int32_t* __restrict__ bad) {
-  const InvFrame F = frames[blockIdx.x];
+  const SpgFrame F = frames[blockIdx.x];
   const InvSound S = snds[F.snd];
   const double* mrow = mag + S.mag0 + (int64_t)F.f * mrows;
   const double* prow = phase ? phase + S.mag0 + (int64_t)F.f * mrows : nullptr;
@@ -204,15 +164,14 @@ __global__ __launch_bounds__(kT) void sg_inv_start(const InvFrame* __restrict__ 
 // The N-point Hermitian spectrum goes through the M-point complex inverse of z_n = y_2n + i y_2n+1:
 // Z_k = E_k + i O_k with 2 E_k = X_k + conj X_{M-k}, 2 O_k = (X_k - conj X_{M-k}) conj W_N^k; the halves
 // are left out and the result divided by N = 2 M. Im X_0 and Im X_M drop out of the real part.
-__global__ __launch_bounds__(kT) void sg_inv_frames(const double2* __restrict__ X, const InvFrame* __restrict__ frames,
+__global__ __launch_bounds__(kT) void sg_inv_frames(const double2* __restrict__ X, const SpgFrame* __restrict__ frames,
                                                     const InvSound* __restrict__ snds, const double* __restrict__ win,
                                                     const double2* __restrict__ TN, int wl, int pad, int M, int rows,
                                                     double* __restrict__ ws) {
   extern __shared__ double2 lds64[];
-  double2* a = lds64;
-  double2* b = a + M;
-  double2* rt = b + M;
-  const InvFrame F = frames[blockIdx.x];
+  const Fft64Lds L = fft64_carve(lds64, M);
+  double2 *a = L.a, *b = L.b, *rt = L.rt;
+  const SpgFrame F = frames[blockIdx.x];
   const InvSound S = snds[F.snd];
   const double2* row = X + S.spec0 + (int64_t)F.f * rows;
   for (int k = threadIdx.x; k < M; k += kT) {
@@ -239,14 +198,14 @@ __global__ __launch_bounds__(kT) void sg_inv_frames(const double2* __restrict__ 
 }
 
 __global__ __launch_bounds__(kT) void sg_inv_ola(const InvTile* __restrict__ tiles, const InvSound* __restrict__ snds,
-                                                 const InvFrame* __restrict__ frames, const double* __restrict__ win,
+                                                 const SpgFrame* __restrict__ frames, const double* __restrict__ win,
                                                  const double* __restrict__ ws, int wl, double by,
                                                  double* __restrict__ out) {
   const InvTile J = tiles[blockIdx.x];
   const InvSound S = snds[J.snd];
   const int64_t t = (int64_t)J.c * kT + threadIdx.x;
   if (t >= S.len) return;
-  const InvFrame* fr = frames + S.f0;
+  const SpgFrame* fr = frames + S.f0;
   const sg::InvCover c = sg::inv_cover(t, wl, (int64_t)S.nf, by, [fr](int64_t i) { return fr[i].o; });
   const double* y = ws + S.ws0;
   double num = 0, den = 0;
@@ -266,7 +225,7 @@ thread_local std::string g_inv_size_err;
 // the other from 0 unless spec_off says where each spectrum is.
 struct InvTables {
   std::vector<InvSound> snds;
-  std::vector<InvFrame> fr;
+  std::vector<SpgFrame> fr;
   std::vector<InvTile> tiles;
   int64_t spec_cells = 0, ws_cells = 0;
 };
@@ -287,14 +246,12 @@ InvTables inv_tables(const sg::SpgSetup& S, int64_t c0, int64_t c1, const int64_
     Q.ws0 = T.ws_cells;
     Q.f0 = (int32_t)T.fr.size();
     Q.nf = nf;
-    if ((int64_t)T.fr.size() + nf > 2147483647LL || (int64_t)T.tiles.size() + len / kT + 1 > 2147483647LL)
+    if ((int64_t)T.tiles.size() + len / kT + 1 > 2147483647LL)
       throw sg::SgError(SG_E_UNSUPPORTED, "invert: the frames of one launch exceed 2^31");
-    for (int f = 0; f < nf; ++f) {
-      const int64_t o = sg::spg_frame_start(S, len, f);
-      if (o < 0 || o + S.wl > len || o != sg::inv_frame_start(S.by, S.wl, len, f))
+    sg::spg_list_frames(S, len, nf, (int32_t)(c - c0), "invert", T.fr);
+    for (int f = 0; f < nf; ++f)  // sg_invert.h's restatement, which sg_inv_ola's cover walks
+      if (T.fr[(size_t)Q.f0 + f].o != sg::inv_frame_start(S.by, S.wl, len, f))
         throw sg::SgError(SG_E_DEVICE, "invert: a frame leaves its sound");
-      T.fr.push_back(InvFrame{o, (int32_t)(c - c0), f});
-    }
     if (with_tiles)
       for (int64_t k = 0; k * kT < len; ++k) T.tiles.push_back(InvTile{(int32_t)(c - c0), (int32_t)k});
     T.spec_cells += (int64_t)nf * rows;
@@ -303,18 +260,10 @@ InvTables inv_tables(const sg::SpgSetup& S, int64_t c0, int64_t c1, const int64_
   return T;
 }
 
-int lds_bytes(int M) { return (2 * M + 32) * (int)sizeof(double2); }
-
-template <class K>
-void allow_lds(K kernel, int lds) {
-  if (lds > 48 * 1024)
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-}
-
 // what every launch of a sequence shares
 struct InvDev {
   const InvSound* snd;
-  const InvFrame* fr;
+  const SpgFrame* fr;
   const InvTile* tiles;
   const double* win;
   const double2* TN;
@@ -326,7 +275,7 @@ void synthesize(const sg::SpgSetup& S, const InvDev& D, const double2* d_X, int 
                 sg::StageClock& clk, hipStream_t s) {
   clk.stamp(3);
   if (D.F) {
-    hipLaunchKernelGGL(sg_inv_frames, dim3(D.F), dim3(kT), (size_t)lds_bytes(S.bins), s, d_X, D.fr, D.snd, D.win, D.TN, S.wl,
+    hipLaunchKernelGGL(sg_inv_frames, dim3(D.F), dim3(kT), (size_t)fft64_lds_bytes(S.bins), s, d_X, D.fr, D.snd, D.win, D.TN, S.wl,
                        S.pad, S.bins, rows, d_ws);
     SG_LAUNCHED("sg_inv_frames");
   }
@@ -375,8 +324,8 @@ void stft_device(sg_ctx* ctx, const sg::SpgSetup& S, const T* d_x, const int64_t
   clk.stamp(0);
   sg::spg_stats_device<T>(d_x, offsets, lens.data(), n_calls, d_stat, s);
   clk.stamp(1);
-  const int lds = lds_bytes(S.bins);
-  allow_lds(&sg_inv_stft<T>, lds);
+  const int lds = fft64_lds_bytes(S.bins);
+  lds_opt_in(&sg_inv_stft<T>, lds, "sg_inv_stft");
   hipLaunchKernelGGL(sg_inv_stft<T>, dim3(D.F), dim3(kT), (size_t)lds, s, d_x, D.fr, D.snd, d_stat, D.win, D.TN, S.wl, S.pad,
                      S.bins, rows, d_out);
   SG_LAUNCHED("sg_inv_stft");
@@ -445,7 +394,7 @@ int sg_spg_istft_batch(sg_ctx* ctx, const double* d_spec, const int64_t* spec_of
     DevBuf db;
     const InvDev D = upload_tables(db, S, Tb, s);
     double* d_ws = db.get<double>((size_t)Tb.ws_cells);
-    allow_lds(&sg_inv_frames, lds_bytes(S.bins));
+    lds_opt_in(&sg_inv_frames, fft64_lds_bytes(S.bins), "sg_inv_frames");
     synthesize(S, D, reinterpret_cast<const double2*>(d_spec), rows, d_ws, d_out, clk, s);
     clk.stamp(-1);
     HIPCHK(hipStreamSynchronize(s));
@@ -468,9 +417,9 @@ int sg_invert_spectrogram_batch(sg_ctx* ctx, const double* d_mag, const int64_t*
     if (n_calls == 0) return SG_OK;
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    const int M = S.bins, lds = lds_bytes(M);
-    allow_lds(&sg_inv_frames, lds);
-    allow_lds(&sg_inv_project, lds);
+    const int M = S.bins, lds = fft64_lds_bytes(M);
+    lds_opt_in(&sg_inv_frames, lds, "sg_inv_frames");
+    lds_opt_in(&sg_inv_project, lds, "sg_inv_project");
     const std::vector<int64_t> ends = chunk_ends(S, lengths, n_calls, workspace_cap > 0 ? workspace_cap : sg::kInvWorkspaceCap);
     sg::StageClock clk(s, ctx->profiling ? g_inv_ms : nullptr, sg::kInvStages);
     clk.zero();

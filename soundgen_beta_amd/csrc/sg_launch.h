@@ -1,14 +1,17 @@
 // sg_launch.h — what every host-side launch sequence (the synthesis executor sg_exec.cpp and
 // its launchers; the analysis features sg_mel.hip, sg_ssm.hip, sg_spectrogram.hip, sg_analyze.hip,
 // sg_segment.hip) and the C entry points (theirs and sg_api.cpp's) share: the HIP error check, the buffers of a
-// launch sequence, the exception-to-code mapping of an entry point, the per-stage
+// launch sequence, the opt-in for dynamic LDS, the exception-to-code mapping of an entry point, the per-stage
 // device clock and the single-sound round trip. Host code that needs the HIP runtime.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <map>
+#include <mutex>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "sg_ctx.h"
@@ -59,6 +62,28 @@ T* upload(DevBuf& db, const std::vector<T>& v, hipStream_t s) {
     HIPCHK(hipMemcpyAsync(d, db.host.back().data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s));
   }
   return d;
+}
+
+// The one opt-in for dynamic LDS. A launch may ask for more dynamic LDS than the runtime grants a
+// kernel by default (up to the 160 KB of a gfx950 CU) only after the kernel's function attribute
+// for the largest dynamic size says so. So every launch with dynamic LDS states its size here
+// first, whatever the size. The attribute is per device: the opted-in size is remembered per
+// (kernel, device) and raised only when a launch needs more.
+inline void lds_opt_in(const void* fn, int lds_bytes, const char* name) {
+  static std::mutex mu;
+  static std::map<std::pair<const void*, int>, int> done;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) throw SgError(SG_E_DEVICE, std::string(name) + ": hipGetDevice failed");
+  std::lock_guard<std::mutex> lk(mu);
+  int& have = done[{fn, dev}];
+  if (lds_bytes <= have) return;
+  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess)
+    throw SgError(SG_E_DEVICE, std::string(name) + ": dynamic LDS " + std::to_string(lds_bytes) + " B refused");
+  have = lds_bytes;
+}
+template <class K>
+void lds_opt_in(K* kernel, int lds_bytes, const char* name) {
+  lds_opt_in(reinterpret_cast<const void*>(kernel), lds_bytes, name);
 }
 
 // The body of a C entry point: f()'s value, or the code of what it throws with

@@ -209,7 +209,8 @@ __global__ __launch_bounds__(kT) void sg_seg_fft_one(const T* __restrict__ x, co
   const SegSound S = snds[c];
   const SegStat Q = st[c];
   const int N = 1 << S.p;
-  double2 *a = seg_lds, *b = seg_lds + N, *rt = seg_lds + 2 * N;
+  const Fft64Lds L = fft64_carve(seg_lds, N);
+  double2 *a = L.a, *b = L.b, *rt = L.rt;
   const T* px = x + S.x0;
   for (int j = threadIdx.x; j < N; j += kT) a[j] = make_double2(seg_padded(px, S, Q, j), 0.0);
   __syncthreads();
@@ -231,7 +232,8 @@ __global__ __launch_bounds__(kT) void sg_seg_cols_fwd(const T* __restrict__ x, c
   const SegSound S = snds[I.snd];
   const SegStat Q = st[I.snd];
   const int N1 = 1 << S.lg1, N2 = 1 << (S.p - S.lg1), N = 1 << S.p, n2 = I.idx;
-  double2 *a = seg_lds, *b = seg_lds + N1, *rt = seg_lds + 2 * N1;
+  const Fft64Lds L = fft64_carve(seg_lds, N1);
+  double2 *a = L.a, *b = L.b, *rt = L.rt;
   const T* px = x + S.x0;
   for (int n1 = threadIdx.x; n1 < N1; n1 += kT) a[n1] = make_double2(seg_padded(px, S, Q, (int64_t)N2 * n1 + n2), 0.0);
   __syncthreads();
@@ -245,7 +247,8 @@ __global__ __launch_bounds__(kT) void sg_seg_rows(const SegSound* __restrict__ s
   const SegItem I = rows[blockIdx.x];
   const SegSound S = snds[I.snd];
   const int N1 = 1 << S.lg1, N2 = 1 << (S.p - S.lg1), N = 1 << S.p, k1 = I.idx;
-  double2 *a = seg_lds, *b = seg_lds + N2, *rt = seg_lds + 2 * N2;
+  const Fft64Lds L = fft64_carve(seg_lds, N2);
+  double2 *a = L.a, *b = L.b, *rt = L.rt;
   double2* w = W + S.w0 + (int64_t)k1 * N2;
   for (int n2 = threadIdx.x; n2 < N2; n2 += kT) a[n2] = w[n2];
   __syncthreads();
@@ -265,7 +268,8 @@ __global__ __launch_bounds__(kT) void sg_seg_cols_inv(const SegSound* __restrict
   const SegItem I = cols[blockIdx.x];
   const SegSound S = snds[I.snd];
   const int N1 = 1 << S.lg1, N2 = 1 << (S.p - S.lg1), q = I.idx;
-  double2 *a = seg_lds, *b = seg_lds + N1, *rt = seg_lds + 2 * N1;
+  const Fft64Lds L = fft64_carve(seg_lds, N1);
+  double2 *a = L.a, *b = L.b, *rt = L.rt;
   const double2* w = W + S.w0 + q;
   for (int k1 = threadIdx.x; k1 < N1; k1 += kT) a[k1] = w[(int64_t)k1 * N2];
   __syncthreads();
@@ -393,13 +397,6 @@ double g_seg_ms[sg::kSegStages];  // of the last profiled launch sequence
 
 // first root of the table of an M = 2^lg-point frame (2 M roots) among the tables of 2^1 .. 2^11
 int root_table(int lg) { return (1 << (lg + 1)) - 4; }
-
-template <class K>
-void allow_lds(K kernel, int bytes) {
-  if (bytes > 48 * 1024)
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-}
-int lds_bytes(int M) { return (2 * M + 32) * (int)sizeof(double2); }
 
 // What a sweep launches behind the raw envelopes in place of the one smoothing and the one
 // tail: launch() on the stream, finish() once it is synchronised (ms: the device time of the
@@ -564,27 +561,27 @@ void segment_run(const sg_segment_params& p, const std::vector<SegPlan>& plans, 
     const SegItem* d_rows = upload(db, rows, s);
     if (!ones.empty()) {
       const int32_t* d_ones = upload(db, ones, s);
-      allow_lds(&sg_seg_fft_one<T>, lds_bytes(M1));
-      hipLaunchKernelGGL(sg_seg_fft_one<T>, dim3((unsigned)ones.size()), bT, (size_t)lds_bytes(M1), s, d_x, d_snd, d_ones,
+      sg::lds_opt_in(&sg_seg_fft_one<T>, fft64_lds_bytes(M1), "sg_seg_fft_one");
+      hipLaunchKernelGGL(sg_seg_fft_one<T>, dim3((unsigned)ones.size()), bT, (size_t)fft64_lds_bytes(M1), s, d_x, d_snd, d_ones,
                          d_st, d_TN, d_raw);
       HIPCHK(hipGetLastError());
     }
     if (!cols.empty()) {
-      allow_lds(&sg_seg_cols_fwd<T>, lds_bytes(Mc));
-      hipLaunchKernelGGL(sg_seg_cols_fwd<T>, dim3((unsigned)cols.size()), bT, (size_t)lds_bytes(Mc), s, d_x, d_snd, d_cols,
+      sg::lds_opt_in(&sg_seg_cols_fwd<T>, fft64_lds_bytes(Mc), "sg_seg_cols_fwd");
+      hipLaunchKernelGGL(sg_seg_cols_fwd<T>, dim3((unsigned)cols.size()), bT, (size_t)fft64_lds_bytes(Mc), s, d_x, d_snd, d_cols,
                          d_st, d_TN, d_W);
       HIPCHK(hipGetLastError());
     }
     clk.stamp();  // rows
     if (!rows.empty()) {
-      allow_lds(&sg_seg_rows, lds_bytes(Mr));
-      hipLaunchKernelGGL(sg_seg_rows, dim3((unsigned)rows.size()), bT, (size_t)lds_bytes(Mr), s, d_snd, d_rows, d_TN, d_W);
+      sg::lds_opt_in(&sg_seg_rows, fft64_lds_bytes(Mr), "sg_seg_rows");
+      hipLaunchKernelGGL(sg_seg_rows, dim3((unsigned)rows.size()), bT, (size_t)fft64_lds_bytes(Mr), s, d_snd, d_rows, d_TN, d_W);
       HIPCHK(hipGetLastError());
     }
     clk.stamp();  // inverse columns
     if (!cols.empty()) {
-      allow_lds(&sg_seg_cols_inv, lds_bytes(Mc));
-      hipLaunchKernelGGL(sg_seg_cols_inv, dim3((unsigned)cols.size()), bT, (size_t)lds_bytes(Mc), s, d_snd, d_cols, d_TN,
+      sg::lds_opt_in(&sg_seg_cols_inv, fft64_lds_bytes(Mc), "sg_seg_cols_inv");
+      hipLaunchKernelGGL(sg_seg_cols_inv, dim3((unsigned)cols.size()), bT, (size_t)fft64_lds_bytes(Mc), s, d_snd, d_cols, d_TN,
                          d_W, d_raw);
       HIPCHK(hipGetLastError());
     }
@@ -672,7 +669,7 @@ struct Sweep : SegBehind {
     double* d_work = db.get<double>((size_t)work_cells);
     const int32_t lds_values = g_sweep_staging ? std::min(max_m, (int32_t)kSweepLdsValues) : 0;
     const size_t lds = (size_t)lds_values * sizeof(double);
-    allow_lds(&sg_seg_sweep_tail, (int)lds);
+    sg::lds_opt_in(&sg_seg_sweep_tail, (int)lds, "sg_seg_sweep_tail");
     int64_t r0 = 0;
     for (int64_t r1 : chunk_end) {
       hipLaunchKernelGGL(sg_seg_sweep_tail, dim3((unsigned)((r1 - r0) * n_calls)), dim3(kTailT), lds, s, d_slots, d_rows,

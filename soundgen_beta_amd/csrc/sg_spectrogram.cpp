@@ -86,6 +86,16 @@ int64_t spg_frame_start(const SpgSetup& S, int64_t len, int i) {
   return (int64_t)std::floor(v < to ? v : to) - 1;  // pmin(x, to); indexing truncates
 }
 
+void spg_list_frames(const SpgSetup& S, int64_t len, int nf, int32_t snd, const char* who, std::vector<SpgFrame>& fr) {
+  if ((int64_t)fr.size() + nf > 2147483647LL)
+    throw SgError(SG_E_UNSUPPORTED, std::string(who) + ": the frames of one launch exceed 2^31");
+  for (int f = 0; f < nf; ++f) {
+    const int64_t o = spg_frame_start(S, len, f);
+    if (o < 0 || o + S.wl > len) throw SgError(SG_E_DEVICE, std::string(who) + ": a frame leaves its sound");
+    fr.push_back(SpgFrame{o, snd, f});
+  }
+}
+
 std::vector<double> spg_window(int wl, int wn) {
   std::vector<double> w(wl);
   const double n = (double)(wl - 1);

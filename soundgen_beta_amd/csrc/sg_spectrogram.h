@@ -33,11 +33,29 @@ int64_t spg_frame_start(const SpgSetup& S, int64_t len, int i);
 // ftwindow_modif(wl, wn) in R's operation order
 std::vector<double> spg_window(int wl, int wn);
 
+// A frame of a launch, as the frame kernels of spectrogram(), stft() and invert_spectrogram() read it
+struct SpgFrame {
+  int64_t o;       // first sample within the sound
+  int32_t snd, f;  // sound (of the launch's table), frame within the sound
+};
+// The nf = spg_frames(S, len) frames of sound snd appended to fr. Refuses, in the name of the
+// feature `who`, a frame that leaves its sound and more than 2^31 frames in one launch.
+void spg_list_frames(const SpgSetup& S, int64_t len, int nf, int32_t snd, const char* who, std::vector<SpgFrame>& fr);
+
 // getFrameBank's normalisation of a sound (device): x -> ((x - mean) / sd) / m when scaled, else x / m
 struct SpgStat {
   double mean, sd, m, mn, mx;
   int32_t scaled, pad;
 };
+// the statistics that leave a sample as it is, bit for bit: what a sound has before its own are known
+constexpr SpgStat kSpgStatIdentity{0, 1, 1, 0, 0, 0, 0};
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline double spg_normalise(double s, const SpgStat& st) {
+  if (st.scaled) s = (s - st.mean) / st.sd;
+  return s / st.m;
+}
 
 // The normalisation statistics alone, as spectrogram_device computes them (the same kernels in
 // the same order: bit-equal), for a caller that rebuilds frames without a spectrogram

@@ -12,9 +12,8 @@
 //                     scale(); sg_spg_stats_fold folds a sound's chunks in a fixed order
 //   sg_spg_roots      W_N^t, t < N: a table fft64 reads (fill_roots64: the launch's frame
 //                     length here, the cepstrum's transform in sg_analyze.hip)
-//   sg_spg_frames     one workgroup per frame: normalisation on the fly, the window
-//                     (host table, R's operation order), zero padding, the packed real
-//                     transform through fft64, the untangling, |X_k| for k < N / 2
+//   sg_spg_frames     one workgroup per frame: |X_k| for k < N / 2 (spg_forward_frame,
+//                     sg_spectrogram_dev.h; the window is a host table in R's operation order)
 //   sg_spg_deriv      :180-185 sqrt(dZ_dt^2 + dZ_df^2): along bins / along frames
 //   sg_spg_medbins    :192-196 smoothTime: rollmedian(fill = 0) along a frame's bins
 //   sg_spg_medframes  :197-201 smoothFreq: rollmedian(fill = 0) along a bin's frames
@@ -38,10 +37,9 @@
 #include <vector>
 
 #include "sg_dev64.h"
-#include "sg_fft64_dev.h"
 #include "sg_launch.h"
 #include "sg_rmath.h"
-#include "sg_spectrogram.h"
+#include "sg_spectrogram_dev.h"
 
 namespace {
 
@@ -58,10 +56,7 @@ struct SpgSound {
 // a select, not an index: a dynamic index would put the struct into scratch
 __device__ __forceinline__ int64_t cell0(const SpgSound& S, int w) { return w ? S.cell0[1] : S.cell0[0]; }
 
-struct SpgFrame {
-  int64_t o;        // first sample within the sound
-  int32_t snd, f;   // sound, frame within the sound
-};
+using sg::SpgFrame;
 
 struct SpgChunk {
   int32_t snd, c;
@@ -166,62 +161,33 @@ __global__ __launch_bounds__(kT) void sg_spg_roots(double2* __restrict__ TN, int
 }
 
 // Test hook (sg_debug_fft64): fft64 alone, one workgroup per frame of M complex
-// points, unscaled. LDS as sg_spg_frames: two M-point buffers and the 32 radix roots.
+// points, unscaled. LDS: fft64_lds_bytes(M).
 __global__ __launch_bounds__(kT) void sg_fft64_probe(const double2* __restrict__ in, const double2* __restrict__ TN,
                                                      int M, int inv, double2* __restrict__ out) {
   extern __shared__ double2 lds64[];
-  double2* a = lds64;
-  double2* b = a + M;
-  double2* rt = b + M;
+  Fft64Lds L = fft64_carve(lds64, M);
   const double2* x = in + (int64_t)blockIdx.x * M;
-  for (int n = threadIdx.x; n < M; n += kT) a[n] = x[n];
+  for (int n = threadIdx.x; n < M; n += kT) L.a[n] = x[n];
   __syncthreads();
-  fft64(a, b, M, TN, rt, inv != 0);
+  fft64(L.a, L.b, M, TN, L.rt, inv != 0);
   double2* y = out + (int64_t)blockIdx.x * M;
-  for (int k = threadIdx.x; k < M; k += kT) y[k] = a[k];
+  for (int k = threadIdx.x; k < M; k += kT) y[k] = L.a[k];
 }
 
-// |X_k|, k < M = N / 2, of every frame: N = wl + 2 pad points, the wl windowed
-// samples in the middle. LDS: two M-point buffers and fft64's 32 radix roots.
+// |X_k|, k < M = N / 2, of every frame (spg_forward_frame). LDS: fft64_lds_bytes(M).
 template <typename T>
 __global__ __launch_bounds__(kT) void sg_spg_frames(const T* __restrict__ x, const SpgFrame* __restrict__ frames,
                                                     const SpgSound* __restrict__ snds, const SpgStat* __restrict__ stat,
                                                     const double* __restrict__ win, const double2* __restrict__ TN,
                                                     int wl, int pad, int M, double* __restrict__ out) {
   extern __shared__ double2 lds64[];
-  double2* a = lds64;
-  double2* b = a + M;
-  double2* rt = b + M;
   const SpgFrame F = frames[blockIdx.x];
   const SpgSound S = snds[F.snd];
   const SpgStat st = stat[F.snd];
-  const T* xc = x + S.base + F.o;  // host: F.o + wl <= S.len
-  for (int n = threadIdx.x; n < M; n += kT) {
-    double v[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int j = 2 * n + h - pad;
-      double s = 0;
-      if (j >= 0 && j < wl) {
-        s = (double)xc[j];
-        if (st.scaled) s = (s - st.mean) / st.sd;
-        s = (s / st.m) * win[j];
-      }
-      v[h] = s;
-    }
-    a[n] = make_double2(v[0], v[1]);
-  }
-  __syncthreads();
-  fft64(a, b, M, TN, rt, false);
-  // X_k = E_k + W_N^k O_k, E = (Z_k + conj Z_{M-k}) / 2, O = -i (Z_k - conj Z_{M-k}) / 2
   double* row = out + S.cell0[0] + (int64_t)F.f * M;
-  for (int k = threadIdx.x; k < M; k += kT) {
-    const double2 p = a[k], q = a[k == 0 ? 0 : M - k], w = TN[k];
-    const double2 e = make_double2(0.5 * (p.x + q.x), 0.5 * (p.y - q.y));
-    const double2 o = make_double2(0.5 * (p.y + q.y), -0.5 * (p.x - q.x));
-    const double re = e.x + (o.x * w.x - o.y * w.y), im = e.y + (o.x * w.y + o.y * w.x);
-    row[k] = hypot(re, im);
-  }
+  // host: F.o + wl <= S.len
+  spg_forward_frame(lds64, x + S.base + F.o, &st, win, TN, wl, pad, M, M,
+                    [row](int k, double re, double im) { row[k] = hypot(re, im); });
 }
 
 __global__ __launch_bounds__(kT) void sg_spg_deriv(const SpgFrame* __restrict__ frames, const SpgSound* __restrict__ snds,
@@ -507,8 +473,7 @@ int32_t stat_chunks(std::vector<SpgChunk>& chunks, int64_t c, int64_t len) {
 }
 
 // The normalisation statistics of n_calls sounds on stream s, nothing awaited: both passes over the chunks, each
-// folded per sound. d_stat holds kStatInit on entry; d_part: 3 doubles per chunk
-const SpgStat kStatInit{0, 1, 1, 0, 0, 0, 0};
+// folded per sound. d_stat holds kSpgStatIdentity on entry; d_part: 3 doubles per chunk
 template <typename T>
 void stats_launch(const T* d_x, const SpgChunk* d_ch, size_t nchunks, const SpgSound* d_snd, int64_t n_calls, SpgStat* d_stat,
                   double* d_part, hipStream_t s) {
@@ -554,14 +519,8 @@ void spectrogram_device(const SpgSetup& S, const T* d_x, const int64_t* offsets,
     if (S.processed && S.kFreq > nf)
       throw SgError(SG_E_ARG, "spectrogram: smoothFreq is larger than the " + std::to_string(nf) + " frames of call " +
                                   std::to_string((long long)c));
-    if ((int64_t)fr.size() + nf > 2147483647LL)
-      throw SgError(SG_E_UNSUPPORTED, "spectrogram: the frames of one launch exceed 2^31");
     stat_chunks(chunks, c, Q.len);
-    for (int f = 0; f < nf; ++f) {
-      const int64_t o = spg_frame_start(S, lengths[c], f);
-      if (o < 0 || o + S.wl > lengths[c]) throw SgError(SG_E_DEVICE, "spectrogram: a frame leaves its sound");
-      fr.push_back(SpgFrame{o, (int32_t)c, f});
-    }
+    spg_list_frames(S, lengths[c], nf, (int32_t)c, "spectrogram", fr);
     cells += (int64_t)nf * B;
     nfmax = std::max(nfmax, nf);
   }
@@ -578,7 +537,7 @@ void spectrogram_device(const SpgSetup& S, const T* d_x, const int64_t* offsets,
   // the keys of +Inf (no positive cell yet) and -Inf (no maximum yet)
   const unsigned long long kinf = dkey(INFINITY), kninf = dkey(-INFINITY);
   SpgRange* d_range = upload(db, std::vector<SpgRange>(n_calls, SpgRange{kinf, kninf, kninf, 0.0, 0.0, 0, 0}), s);
-  SpgStat* d_stat = upload(db, std::vector<SpgStat>(n_calls, kStatInit), s);
+  SpgStat* d_stat = upload(db, std::vector<SpgStat>(n_calls, kSpgStatIdentity), s);
   double* d_part = db.get<double>(3 * chunks.size());
   double2* d_TN = db.get<double2>((size_t)S.N);
   const dim3 gF((unsigned)F), bT(kT);
@@ -588,10 +547,8 @@ void spectrogram_device(const SpgSetup& S, const T* d_x, const int64_t* offsets,
     HIPCHK(hipMemcpyAsync(d_stat_out, d_stat, (size_t)n_calls * sizeof(SpgStat), hipMemcpyDeviceToDevice, s));
   clk.stamp();  // 1: frames
   fill_roots64(d_TN, S.N, s);
-  const int lds = (2 * B + 32) * (int)sizeof(double2);
-  if (lds > 48 * 1024)
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&sg_spg_frames<T>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+  const int lds = fft64_lds_bytes(B);
+  lds_opt_in(&sg_spg_frames<T>, lds, "sg_spg_frames");
   hipLaunchKernelGGL(sg_spg_frames<T>, gF, bT, (size_t)lds, s, d_x, d_fr, d_snd, d_stat, d_win, d_TN, S.wl, S.pad, B,
                      d_out);
   HIPCHK(hipGetLastError());
@@ -683,7 +640,7 @@ void spg_stats_device(const T* d_x, const int64_t* offsets, const int64_t* lengt
   DevBuf db;
   const SpgSound* d_snd = upload(db, snds, s);
   const SpgChunk* d_ch = upload(db, chunks, s);
-  const SpgStat* d_init = upload(db, std::vector<SpgStat>(n_calls, kStatInit), s);
+  const SpgStat* d_init = upload(db, std::vector<SpgStat>(n_calls, kSpgStatIdentity), s);
   double* d_part = db.get<double>(3 * chunks.size());
   HIPCHK(hipMemcpyAsync(d_stat, d_init, (size_t)n_calls * sizeof(SpgStat), hipMemcpyDeviceToDevice, s));
   stats_launch<T>(d_x, d_ch, chunks.size(), d_snd, n_calls, d_stat, d_part, s);
@@ -760,10 +717,8 @@ int sg_debug_fft64(sg_ctx* ctx, int32_t M, int32_t inverse, int32_t nframes, con
     double2* d_TN = db.get<double2>((size_t)2 * M);
     HIPCHK(hipMemcpyAsync(d_in, in, n * sizeof(double2), hipMemcpyHostToDevice, s));
     sg::fill_roots64(d_TN, 2 * M, s);
-    const int lds = (2 * M + 32) * (int)sizeof(double2);
-    if (lds > 48 * 1024)
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&sg_fft64_probe),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    const int lds = fft64_lds_bytes(M);
+    sg::lds_opt_in(&sg_fft64_probe, lds, "sg_fft64_probe");
     hipLaunchKernelGGL(sg_fft64_probe, dim3((unsigned)nframes), dim3(kT), (size_t)lds, s, d_in, d_TN, (int)M,
                        (int)inverse, d_out);
     HIPCHK(hipGetLastError());

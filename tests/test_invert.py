@@ -34,8 +34,14 @@ SR = 16000
 # The smallest shapes that reach every branch: windows of 8, 44 (half 2 x 11), 62 (half 2 x 31),
 # 96 and 2204 points (half 1102 = 2 x 19 x 29, fft64's folded branch); a sound of wl + 1 samples
 # (one frame and an uncovered sample), a few hundred, 6000; a fractional step (20.8 points); a
-# step longer than the window (uncovered samples); zero padding; 'hanning' (zero denominators).
+# step longer than the window (uncovered samples); zero padding; 'hanning' (zero denominators);
+# the smallest frame spectrogram() accepts (4 points, half 2); an odd pad, where a packed pair
+# (2n - pad, 2n + 1 - pad) straddles the frame's edge, one half a sample and the other a zero:
+# pad 1 around 4 points (half 3) and pad 3 around 8 (half 7).
 CASES = {
+    "w4": dict(n=400, kw=dict(windowLength=0.25)),
+    "w4_pad1": dict(n=400, kw=dict(windowLength=0.25, zp=6)),
+    "w8_pad3": dict(n=400, kw=dict(windowLength=0.5, zp=14)),
     "w8_one_frame": dict(n=9, kw=dict(windowLength=0.5)),
     "w44_fractional": dict(n=300, kw=dict(windowLength=2.75, step=1.3)),
     "w62_hanning": dict(n=500, kw=dict(windowLength=3.9, wn="hanning")),
