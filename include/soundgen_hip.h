@@ -1181,6 +1181,61 @@ int sg_invert_spectrogram_batch(sg_ctx* ctx, const double* d_mag, const int64_t*
  * projection inside the iteration), X_0, the inverse frames, the overlap-add, the error fold. */
 int sg_debug_invert_kernel_ms(double* out);
 
+/* ---- time_stretch(), shift_pitch() and resample(): a phase vocoder between A and A+ above and a
+ * band-limited resampler (an additive extension of ABI 5; no reference counterpart). fp64, no
+ * floating-point atomics: a sound's samples are the same bit for bit alone, in any batch, at any
+ * position and under any workspace cap. Formants move with the pitch; there is no transient
+ * handling and no phase locking.
+ *
+ *   Time stretch. X = A x without getFrameBank's normalisation, M + 1 rows, F_in frames starting at
+ *   s_i; the output has out_len samples, F_out frames starting at t_j, g_j = t_j - t_j-1, and a
+ *   position q_j in [0, F_in - 1] per output frame. i = min(floor(q_j), F_in - 1), a = q_j - i,
+ *   i1 = min(i + 1, F_in - 1), h = s_i1 - s_i;
+ *     m_j[k] = (1 - a) |X_i[k]| + a |X_i1[k]|,
+ *     d = arg X_i1[k] - arg X_i[k] - 2 pi ((k h) mod N) / N, wrapped d -= 2 pi rint(d / 2 pi), (d / h)_j = d / h
+ *     (0 where h = 0),
+ *     psi_0[k] = arg X_i(0)[k], psi_j[k] = psi_j-1[k] + 2 pi ((k g_j) mod N) / N + g_j (d / h)_j-1, wrapped alike
+ *     after every step,
+ *   X'_j[k] = m_j[k] exp(i psi_j[k]) and the result is A+ X'. With q_j = j and out_len = len, X' = X up to
+ *   rounding.
+ *   Resample. up and down reduced by their gcd, D = max(up, down), n_out = ceil(n up / down):
+ *     y[r] = sum_m x[m] (up / D) sinc(num / D) (1 + cos(pi num / (16 D))) / 2,  num = r down - m up,
+ *   over 0 <= m < n with |num| < 16 D in ascending m; sin(pi num / D) is taken on num reduced mod 2 D
+ *   (exactly 0 at the non-zero multiples of D), so up = down returns x bit for bit. */
+/* Host only, no device. With p: for a sound of len samples and an output of out_len, the frames of
+ * both (frames_in, frames_out) and the bytes of workspace the sound takes inside
+ * sg_time_stretch_batch; every refusal of sg_spectrogram_size applies with its code and text.
+ * With p = NULL: for len samples and the ratio up : down, n_out and the most taps an output sample
+ * has. SG_E_ARG for up or down below 1 or at 2^31 and above, max / min above 64 after reduction, or
+ * n_out at 2^31 and above. The outputs of the other form may be NULL. */
+int sg_stretch_size(int64_t len, const sg_spectrogram_params* p, int64_t out_len, int64_t up, int64_t down, int32_t* frames_in,
+                    int32_t* frames_out, int64_t* workspace_bytes, int64_t* n_out, int64_t* taps);
+/* The message of the calling thread's last failed sg_stretch_size ("" if none). */
+const char* sg_stretch_size_error(void);
+/* The vocoder on n_calls sounds in DEVICE memory (call c: lengths[c] samples at offsets[c] of
+ * d_wave, fp32, or fp64 when is_f64). out_lengths[c]: the samples of call c's result, written as
+ * doubles at out_off[c] of d_out (device). positions (HOST): call c's pos_count[c] positions at
+ * positions[pos_off[c]]. SG_E_ARG, before ctx is looked at, for a count that is not the frame count
+ * of out_lengths[c], a position that is NaN or outside [0, F_in - 1], or an output shorter than the
+ * window. A sound shorter than the window has no frames, as in sg_spg_stft_batch: its count and
+ * positions are not read and its result is out_lengths[c] zeros. The batch runs in chunks of
+ * consecutive sounds whose workspaces (sg_stretch_size) fit workspace_cap bytes (0: 1 GiB; at least
+ * one sound a chunk). d_spec (device, or NULL): receives X', F_out x (M + 1) complex cells at
+ * complex cell spec_off[c]. */
+int sg_time_stretch_batch(sg_ctx* ctx, const void* d_wave, int32_t is_f64, const int64_t* offsets, const int64_t* lengths,
+                          int64_t n_calls, const sg_spectrogram_params* p, const int64_t* out_lengths, const double* positions,
+                          const int64_t* pos_off, const int64_t* pos_count, double* d_out, const int64_t* out_off,
+                          int64_t workspace_cap, double* d_spec, const int64_t* spec_off);
+/* The resampler on n_calls sounds in DEVICE memory, call c by up[c] : down[c]: n_out doubles
+ * (sg_stretch_size) at out_off[c] of d_out (device). The refusals are sg_stretch_size's, before
+ * ctx is looked at. */
+int sg_resample_batch(sg_ctx* ctx, const void* d_wave, int32_t is_f64, const int64_t* offsets, const int64_t* lengths,
+                      int64_t n_calls, const int64_t* up, const int64_t* down, double* d_out, const int64_t* out_off);
+/* The device milliseconds of the last of the two on a context with sg_set_profiling on, summed
+ * over chunks (5 doubles): the resampler, the forward frames, the vocoder, the inverse frames, the
+ * overlap-add. */
+int sg_debug_stretch_kernel_ms(double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,7 @@ import os
 import numpy as np
 
 from . import _abi, native, rargs
+from .stretch import resample, shift_pitch, time_stretch  # noqa: F401  (no R counterpart in the pinned reference)
 
 
 def _ctx(device):

@@ -39,6 +39,7 @@
 
 #include "sg_dev64.h"
 #include "sg_invert.h"
+#include "sg_invert_ops.h"
 #include "sg_launch.h"
 #include "sg_rmath.h"
 #include "sg_spectrogram_dev.h"
@@ -336,21 +337,57 @@ void stft_device(sg_ctx* ctx, const sg::SpgSetup& S, const T* d_x, const int64_t
 
 // consecutive sounds whose workspaces fit the cap; at least one sound a chunk
 std::vector<int64_t> chunk_ends(const sg::SpgSetup& S, const int64_t* lengths, int64_t n_calls, int64_t cap) {
-  std::vector<int64_t> ends;
-  int64_t used = 0;
-  for (int64_t c = 0; c < n_calls; ++c) {
-    const int64_t need = sg::inv_workspace_bytes(sg::spg_frames(S, lengths[c] > 0 ? lengths[c] : 0), S.wl, S.bins);
-    if (used > 0 && used + need > cap) {
-      ends.push_back(c);
-      used = 0;
-    }
-    used += need;
-  }
-  ends.push_back(n_calls);
-  return ends;
+  std::vector<int64_t> need((size_t)n_calls);
+  for (int64_t c = 0; c < n_calls; ++c)
+    need[(size_t)c] = sg::inv_workspace_bytes(sg::spg_frames(S, lengths[c] > 0 ? lengths[c] : 0), S.wl, S.bins);
+  return sg::inv_chunk_ends(need, cap);
 }
 
 }  // namespace
+
+// ---- the pair as launch sequences, for the features between A and A+ (sg_invert_ops.h)
+namespace sg {
+
+std::vector<int64_t> inv_chunk_ends(const std::vector<int64_t>& need, int64_t cap) {
+  std::vector<int64_t> ends;
+  int64_t used = 0;
+  for (size_t c = 0; c < need.size(); ++c) {
+    if (used > 0 && used + need[c] > cap) {
+      ends.push_back((int64_t)c);
+      used = 0;
+    }
+    used += need[c];
+  }
+  ends.push_back((int64_t)need.size());
+  return ends;
+}
+
+template <typename T>
+void inv_forward_launch(const SpgSetup& S, const T* d_x, const int64_t* offsets, const int64_t* lengths, int64_t c0,
+                        int64_t c1, double2* d_X, DevBuf& db, hipStream_t s) {
+  const InvTables Tb = inv_tables(S, c0, c1, offsets, lengths, nullptr, nullptr, S.bins + 1, false);
+  if (Tb.fr.empty()) return;
+  const InvDev D = upload_tables(db, S, Tb, s);
+  const int lds = fft64_lds_bytes(S.bins);
+  lds_opt_in(&sg_inv_stft<T>, lds, "sg_inv_stft");
+  hipLaunchKernelGGL(sg_inv_stft<T>, dim3(D.F), dim3(kT), (size_t)lds, s, d_x, D.fr, D.snd, (const SpgStat*)nullptr, D.win, D.TN,
+                     S.wl, S.pad, S.bins, S.bins + 1, d_X);
+  SG_LAUNCHED("sg_inv_stft");
+}
+template void inv_forward_launch<float>(const SpgSetup&, const float*, const int64_t*, const int64_t*, int64_t, int64_t,
+                                        double2*, DevBuf&, hipStream_t);
+template void inv_forward_launch<double>(const SpgSetup&, const double*, const int64_t*, const int64_t*, int64_t, int64_t,
+                                         double2*, DevBuf&, hipStream_t);
+
+void inv_synthesis_launch(const SpgSetup& S, const double2* d_X, const int64_t* out_off, const int64_t* lengths,
+                          int64_t c0, int64_t c1, double* d_ws, double* d_out, DevBuf& db, StageClock& clk, hipStream_t s) {
+  const InvTables Tb = inv_tables(S, c0, c1, out_off, lengths, nullptr, nullptr, S.bins + 1, true);
+  const InvDev D = upload_tables(db, S, Tb, s);
+  lds_opt_in(&sg_inv_frames, fft64_lds_bytes(S.bins), "sg_inv_frames");
+  synthesize(S, D, d_X, S.bins + 1, d_ws, d_out, clk, s);
+}
+
+}  // namespace sg
 
 using sg::guarded;
 

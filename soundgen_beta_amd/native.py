@@ -137,6 +137,16 @@ def lib():
         L.sg_invert_spectrogram_batch.argtypes = [vp, vp, i64p, vp, i64p, i64, spp, C.c_int32, C.c_int32, i64, vp, i64p,
                                                   dp]
         L.sg_debug_invert_kernel_ms.argtypes = [dp]
+    if hasattr(L, "sg_stretch_size"):  # time_stretch(), shift_pitch(), resample(): likewise additive
+        i32p = C.POINTER(C.c_int32)
+        spp = C.POINTER(_abi.sg_spectrogram_params)
+        L.sg_stretch_size.argtypes = [i64, spp, i64, i64, i64, i32p, i32p, i64p, i64p, i64p]
+        L.sg_stretch_size_error.argtypes = []
+        L.sg_stretch_size_error.restype = C.c_char_p
+        L.sg_time_stretch_batch.argtypes = [vp, vp, C.c_int32, i64p, i64p, i64, spp, i64p, dp, i64p, i64p, vp, i64p, i64, vp,
+                                            i64p]
+        L.sg_resample_batch.argtypes = [vp, vp, C.c_int32, i64p, i64p, i64, i64p, i64p, vp, i64p]
+        L.sg_debug_stretch_kernel_ms.argtypes = [dp]
     if hasattr(L, "sg_debug_fft64"):  # the fp64 transform alone (tests/test_fft64.py): likewise additive
         L.sg_debug_fft64.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, dp, dp]
     if hasattr(L, "sg_debug_sine_bank"):  # the sine-bank kernels on caller-built tasks (tests/test_sine_bank.py)
