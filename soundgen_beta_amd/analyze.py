@@ -447,10 +447,8 @@ def _params(s):
                                   WINDOWS.index(s["wn"]), methods)
 
 
-def _raise(rc, msg):
-    if rc == -1:
-        raise ValueError(msg)
-    raise native.SoundgenError(rc, msg)
+def _host_check(rc):
+    native.host_check(rc, native.lib().sg_analyze_frames_size_error, value_error=True)
 
 
 def frame_decisions_native(length, s):
@@ -460,8 +458,7 @@ def frame_decisions_native(length, s):
     o = [C.c_int32() for _ in range(6)]
     extra = (C.c_int32 * 8)()
     rc = L.sg_analyze_frames_size(int(length), C.byref(P), *[C.byref(v) for v in o], extra)
-    if rc < 0:
-        _raise(rc, L.sg_analyze_frames_size_error().decode())
+    _host_check(rc)
     keys = ("wl", "bins", "frames", "cols", "lag_first", "lag_last")
     d = {k: v.value for k, v in zip(keys, o)}
     d.update(zip(("rowLow", "rowHigh", "cut0", "ncut", "pitchFloor_idx", "domSmooth_bins", "autocorSmooth"), extra))
@@ -473,8 +470,7 @@ def ampl_starts_native(length, s, frames):
     P = _params(s)
     out = np.zeros(max(frames, 1), dtype=np.int64)
     rc = L.sg_analyze_frames_ampl_starts(int(length), C.byref(P), out.ctypes.data_as(C.POINTER(C.c_int64)), frames)
-    if rc < 0:
-        _raise(rc, L.sg_analyze_frames_size_error().decode())
+    _host_check(rc)
     return out[:frames]
 
 
@@ -488,8 +484,7 @@ def _table(m, nC, length, sr, step):
 
 
 def _check(rc, ctx):
-    if rc < 0:
-        _raise(rc, native.lib().sg_last_error(ctx).decode())
+    native.host_check(rc, lambda: native.lib().sg_last_error(ctx), value_error=True)
 
 
 def _run(sound, sr, s, decisions, params, table, entry, device):
@@ -899,14 +894,12 @@ def pitch_decisions_native(length, s):
     frames, cols = C.c_int32(), C.c_int32()
     extra = (C.c_int32 * 24)()
     rc = L.sg_pitch_candidates_size(int(length), C.byref(P), C.byref(frames), C.byref(cols), extra)
-    if rc < 0:
-        _raise(rc, L.sg_analyze_frames_size_error().decode())
+    _host_check(rc)
     d = dict(zip(PITCH_SIZE_KEYS, extra))
     d.update(frames=frames.value, cols=cols.value)
     lab = np.zeros(max(d["ncep"], 1))
     rc = L.sg_pitch_candidates_cep_labels(C.byref(P), lab.ctypes.data_as(C.POINTER(C.c_double)), d["ncep"])
-    if rc < 0:
-        _raise(rc, L.sg_analyze_frames_size_error().decode())
+    _host_check(rc)
     d["cepf"] = lab[:d["ncep"]]
     return d
 
@@ -917,8 +910,7 @@ def _pitch_frames_native(length, P):
     L = native.lib()
     fr, cl = C.c_int32(), C.c_int32()
     rc = L.sg_pitch_candidates_size(int(length), C.byref(P), C.byref(fr), C.byref(cl), None)
-    if rc < 0:
-        _raise(rc, L.sg_analyze_frames_size_error().decode())
+    _host_check(rc)
     return fr.value
 
 
@@ -1621,8 +1613,7 @@ def track_decisions_native(length, s):
     frames, cols = C.c_int32(), C.c_int32()
     extra = (C.c_int32 * 8)()
     rc = L.sg_analyze_size(int(length), C.byref(P), C.byref(frames), C.byref(cols), extra)
-    if rc < 0:
-        _raise(rc, L.sg_analyze_frames_size_error().decode())
+    _host_check(rc)
     d = pitch_decisions_native(length, s)
     d.update(zip(TRACK_SIZE_KEYS, extra))
     d.update(frames=frames.value, cols=cols.value)
@@ -1633,8 +1624,7 @@ def _track_frames_native(length, P):
     L = native.lib()
     fr, cl = C.c_int32(), C.c_int32()
     rc = L.sg_analyze_size(int(length), C.byref(P), C.byref(fr), C.byref(cl), None)
-    if rc < 0:
-        _raise(rc, L.sg_analyze_frames_size_error().decode())
+    _host_check(rc)
     return fr.value
 
 
@@ -2041,8 +2031,7 @@ def sweep_plan(samplingRate, rows):
     n = len(rows)
     g = [np.zeros(max(n, 1), dtype=np.int32) for _ in range(3)]
     rc = L.sg_analyze_sweep_plan(P, n, *[v.ctypes.data_as(C.POINTER(C.c_int32)) for v in g])
-    if rc < 0:
-        _raise(rc, L.sg_analyze_frames_size_error().decode())
+    _host_check(rc)
     return tuple(v[:n] for v in g)
 
 
@@ -2057,8 +2046,7 @@ def sweep_size(lengths, samplingRate, rows):
     out = np.zeros(3, dtype=np.int64)
     i64p = C.POINTER(C.c_int64)
     rc = L.sg_analyze_sweep_size(lens.ctypes.data_as(i64p), len(lens), P, len(rows), out.ctypes.data_as(i64p))
-    if rc < 0:
-        _raise(rc, L.sg_analyze_frames_size_error().decode())
+    _host_check(rc)
     return dict(frame_group=int(out[0]), store=int(out[1]), row=int(out[2]))
 
 

@@ -491,45 +491,31 @@ void anl_sweep_bytes(const SweepPlan& W, const int64_t* lengths, int64_t n_calls
 }  // namespace sg
 
 namespace {
-thread_local std::string g_anl_err;
-// sg_analyze_frames_size is called once per sound of a batch: the setup of the last parameters is kept
-thread_local sg_analyze_params g_last_p;
-thread_local sg::AnlSetup g_last_S;
-thread_local bool g_have = false;
+using sg::bad_arguments;
+using sg::host_guarded;
 
-const sg::AnlSetup& cached_setup(const sg_analyze_params& p) {
-  if (!g_have || std::memcmp(&p, &g_last_p, sizeof p) != 0) {
-    g_have = false;
-    g_last_S = sg::anl_setup(p);
-    g_last_p = p;
-    g_have = true;
+// A size function is called once per sound of a batch: the setup make(p) of the thread's last
+// parameters is kept, and unset while it is rebuilt (a throwing make leaves no stale pair)
+template <class P, class S>
+const S& memo(S (*make)(const P&), const P& p) {
+  thread_local P last_p;
+  thread_local S last_S;
+  thread_local bool have = false;
+  if (!have || std::memcmp(&p, &last_p, sizeof p) != 0) {
+    have = false;
+    last_S = make(p);
+    last_p = p;
+    have = true;
   }
-  return g_last_S;
-}
-
-template <class F>
-int size_guard(F&& f) {
-  try {
-    f();
-    return SG_OK;
-  } catch (const sg::SgError& e) {
-    g_anl_err = e.what();
-    return e.code;
-  } catch (...) {
-    g_anl_err = "out of host memory";
-    return SG_E_NOMEM;
-  }
+  return last_S;
 }
 }  // namespace
 
 extern "C" int sg_analyze_frames_size(int64_t len, const sg_analyze_params* p, int32_t* wl, int32_t* bins, int32_t* frames,
                                       int32_t* cols, int32_t* lag_first, int32_t* lag_last, int32_t* extra) {
-  if (!p || !wl || !bins || !frames || !cols || !lag_first || !lag_last) {
-    g_anl_err = "sg_analyze_frames_size: bad arguments";
-    return SG_E_ARG;
-  }
-  return size_guard([&]() {
-    const sg::AnlSetup& S = cached_setup(*p);
+  return host_guarded([&]() {
+    if (!p || !wl || !bins || !frames || !cols || !lag_first || !lag_last) bad_arguments("sg_analyze_frames_size");
+    const sg::AnlSetup& S = memo(sg::anl_setup, *p);
     *wl = S.spg.wl;
     *bins = S.spg.bins;
     *frames = sg::anl_frames(S, len);
@@ -544,12 +530,9 @@ extern "C" int sg_analyze_frames_size(int64_t len, const sg_analyze_params* p, i
 }
 
 extern "C" int sg_analyze_frames_ampl_starts(int64_t len, const sg_analyze_params* p, int64_t* starts, int32_t n) {
-  if (!p || (n > 0 && !starts)) {
-    g_anl_err = "sg_analyze_frames_ampl_starts: bad arguments";
-    return SG_E_ARG;
-  }
-  return size_guard([&]() {
-    const sg::AnlSetup& S = cached_setup(*p);
+  return host_guarded([&]() {
+    if (!p || (n > 0 && !starts)) bad_arguments("sg_analyze_frames_ampl_starts");
+    const sg::AnlSetup& S = memo(sg::anl_setup, *p);
     const int frames = sg::anl_frames(S, len);
     if (n > frames) throw sg::SgError(SG_E_ARG, "sg_analyze_frames_ampl_starts: n exceeds the frame count");
     for (int f = 0; f < n; ++f) starts[f] = sg::anl_ampl_start(S, len, frames, f);
@@ -557,41 +540,19 @@ extern "C" int sg_analyze_frames_ampl_starts(int64_t len, const sg_analyze_param
 }
 
 extern "C" int sg_formants_size(const sg_analyze_params* p, int32_t nFormants, int32_t* order, int32_t* cols) {
-  if (!p || !order || !cols) {
-    g_anl_err = "sg_formants_size: bad arguments";
-    return SG_E_ARG;
-  }
-  return size_guard([&]() {
+  return host_guarded([&]() {
+    if (!p || !order || !cols) bad_arguments("sg_formants_size");
     *order = sg::formants_order(p->samplingRate, nFormants);
     *cols = 2 * nFormants;
     sg::formants_window(sg::anl_setup_any(*p).spg.wl, *order);
   });
 }
 
-namespace {
-thread_local sg_pitch_params g_last_pp;
-thread_local sg::PitchSetup g_last_PS;
-thread_local bool g_have_p = false;
-
-const sg::PitchSetup& cached_pitch_setup(const sg_pitch_params& p) {
-  if (!g_have_p || std::memcmp(&p, &g_last_pp, sizeof p) != 0) {
-    g_have_p = false;
-    g_last_PS = sg::pitch_setup(p);
-    g_last_pp = p;
-    g_have_p = true;
-  }
-  return g_last_PS;
-}
-}  // namespace
-
 extern "C" int sg_pitch_candidates_size(int64_t len, const sg_pitch_params* p, int32_t* frames, int32_t* cols,
                                         int32_t* extra) {
-  if (!p || !frames || !cols) {
-    g_anl_err = "sg_pitch_candidates_size: bad arguments";
-    return SG_E_ARG;
-  }
-  return size_guard([&]() {
-    const sg::PitchSetup& S = cached_pitch_setup(*p);
+  return host_guarded([&]() {
+    if (!p || !frames || !cols) bad_arguments("sg_pitch_candidates_size");
+    const sg::PitchSetup& S = memo(sg::pitch_setup, *p);
     *frames = sg::anl_frames(S, len);
     *cols = S.cols;
     if (extra) {
@@ -603,40 +564,18 @@ extern "C" int sg_pitch_candidates_size(int64_t len, const sg_pitch_params* p, i
 }
 
 extern "C" int sg_pitch_candidates_cep_labels(const sg_pitch_params* p, double* labels, int32_t n) {
-  if (!p || (n > 0 && !labels)) {
-    g_anl_err = "sg_pitch_candidates_cep_labels: bad arguments";
-    return SG_E_ARG;
-  }
-  return size_guard([&]() {
-    const sg::PitchSetup& S = cached_pitch_setup(*p);
+  return host_guarded([&]() {
+    if (!p || (n > 0 && !labels)) bad_arguments("sg_pitch_candidates_cep_labels");
+    const sg::PitchSetup& S = memo(sg::pitch_setup, *p);
     if (n > S.ncep) throw sg::SgError(SG_E_ARG, "sg_pitch_candidates_cep_labels: n exceeds the band");
     for (int i = 0; i < n; ++i) labels[i] = S.cepf[i];
   });
 }
 
-namespace {
-thread_local sg_analyze_params_full g_last_tp;
-thread_local sg::TrackSetup g_last_TS;
-thread_local bool g_have_t = false;
-
-const sg::TrackSetup& cached_track_setup(const sg_analyze_params_full& p) {
-  if (!g_have_t || std::memcmp(&p, &g_last_tp, sizeof p) != 0) {
-    g_have_t = false;
-    g_last_TS = sg::track_setup(p);
-    g_last_tp = p;
-    g_have_t = true;
-  }
-  return g_last_TS;
-}
-}  // namespace
-
 extern "C" int sg_analyze_size(int64_t len, const sg_analyze_params_full* p, int32_t* frames, int32_t* cols, int32_t* extra) {
-  if (!p || !frames || !cols) {
-    g_anl_err = "sg_analyze_size: bad arguments";
-    return SG_E_ARG;
-  }
-  return size_guard([&]() {
-    const sg::TrackSetup& S = cached_track_setup(*p);
+  return host_guarded([&]() {
+    if (!p || !frames || !cols) bad_arguments("sg_analyze_size");
+    const sg::TrackSetup& S = memo(sg::track_setup, *p);
     *frames = sg::anl_frames(S, len);
     *cols = S.cols;
     const int hw = sg::track_hw(S.smooth, S.spg.sr, len, *frames);
@@ -649,11 +588,9 @@ extern "C" int sg_analyze_size(int64_t len, const sg_analyze_params_full* p, int
 
 extern "C" int sg_analyze_sweep_plan(const sg_analyze_params_full* rows, int64_t n_rows, int32_t* frame_group,
                                      int32_t* store_group, int32_t* cand_group) {
-  if (n_rows < 0 || (n_rows > 0 && (!rows || !frame_group || !store_group || !cand_group))) {
-    g_anl_err = "sg_analyze_sweep_plan: bad arguments";
-    return SG_E_ARG;
-  }
-  return size_guard([&]() {
+  return host_guarded([&]() {
+    if (n_rows < 0 || (n_rows > 0 && (!rows || !frame_group || !store_group || !cand_group)))
+      bad_arguments("sg_analyze_sweep_plan");
     const sg::SweepPlan W = sg::anl_sweep_plan(rows, n_rows);
     for (int64_t r = 0; r < n_rows; ++r) {
       frame_group[r] = W.frame_group[r];
@@ -665,14 +602,14 @@ extern "C" int sg_analyze_sweep_plan(const sg_analyze_params_full* rows, int64_t
 
 extern "C" int sg_analyze_sweep_size(const int64_t* lengths, int64_t n_calls, const sg_analyze_params_full* rows,
                                      int64_t n_rows, int64_t* bytes) {
-  if (n_rows < 0 || n_calls < 0 || !bytes || (n_rows > 0 && !rows) || (n_calls > 0 && !lengths)) {
-    g_anl_err = "sg_analyze_sweep_size: bad arguments";
-    return SG_E_ARG;
-  }
-  return size_guard([&]() { sg::anl_sweep_bytes(sg::anl_sweep_plan(rows, n_rows), lengths, n_calls, bytes); });
+  return host_guarded([&]() {
+    if (n_rows < 0 || n_calls < 0 || !bytes || (n_rows > 0 && !rows) || (n_calls > 0 && !lengths))
+      bad_arguments("sg_analyze_sweep_size");
+    sg::anl_sweep_bytes(sg::anl_sweep_plan(rows, n_rows), lengths, n_calls, bytes);
+  });
 }
 
-extern "C" const char* sg_analyze_frames_size_error(void) { return g_anl_err.c_str(); }
+extern "C" const char* sg_analyze_frames_size_error(void) { return sg::g_host_err.c_str(); }
 
 // analyze(summary = TRUE): the cells of a row (R/analyze.R:777-784), the variables in sg::sum_column's order
 extern "C" const char* sg_analyze_summary_name(int32_t i) {

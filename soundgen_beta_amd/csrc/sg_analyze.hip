@@ -963,12 +963,12 @@ void candidate_stages(DevBuf& db, hipStream_t s, FrameGroup<T>& G, const sg::Anl
   if (Q.do_spec) launch(kCsBana, [&]() { hipLaunchKernelGGL(sg_anl_bana, gF, bT, 0, s, G.fr, d_snd, G.Z, G.freq, X, d_out); });
 }
 
-double g_anl_ms[sg::kAnlStages];  // of the last profiled launch sequence
-double g_sweep_ms[sg::kSweepStages];
+sg::StageTimes<sg::kAnlStages> g_anl_ms;  // of the last profiled launch sequence
+sg::StageTimes<sg::kSweepStages> g_sweep_ms;
 int g_sweep_store = 1;  // sg_set_analyze_sweep_store
-double g_summary_ms[1];
-double g_pitch_ms[sg::kPitchStages];
-double g_track_ms[sg::kTrackStages];
+sg::StageTimes<1> g_summary_ms;
+sg::StageTimes<sg::kPitchStages> g_pitch_ms;
+sg::StageTimes<sg::kTrackStages> g_track_ms;
 
 }  // namespace
 
@@ -1089,7 +1089,7 @@ namespace {
 using sg::guarded;
 
 // The single-sound and the batch entry point of analyze_frames (pitch == nullptr, ms =
-// g_anl_ms) and of pitch_candidates (pitch == &S, ms = g_pitch_ms), behind their
+// g_anl_ms' sink) and of pitch_candidates (pitch == &S, ms = g_pitch_ms' sink), behind their
 // argument checks
 int frames_single(sg_ctx* ctx, const sg::AnlSetup& S, const sg::PitchSetup* pitch, double* ms, const double* wave,
                   int64_t len, double* out, const sg::TrackSetup* track = nullptr) {
@@ -1098,7 +1098,7 @@ int frames_single(sg_ctx* ctx, const sg::AnlSetup& S, const sg::PitchSetup* pitc
   sg::single_sound(ctx, wave, len, cells, out, [&](const double* d, double* d_o) {
     const int64_t off = 0;
     int32_t f = 0;
-    sg::analyze_device<double>(S, d, &off, &len, 1, d_o, &off, &f, ctx->stream, ctx->profiling ? ms : nullptr, pitch, track);
+    sg::analyze_device<double>(S, d, &off, &len, 1, d_o, &off, &f, ctx->stream, ms, pitch, track);
   });
   return SG_OK;
 }
@@ -1108,8 +1108,7 @@ int frames_batch(sg_ctx* ctx, const sg::AnlSetup& S, const sg::PitchSetup* pitch
                  int32_t* frames_out, const sg::TrackSetup* track = nullptr) {
   if (n_calls == 0) return SG_OK;
   HIPCHK(hipSetDevice(ctx->device));
-  sg::analyze_device<float>(S, d_wave, offsets, lengths, n_calls, d_out, out_off, frames_out, ctx->stream,
-                            ctx->profiling ? ms : nullptr, pitch, track);
+  sg::analyze_device<float>(S, d_wave, offsets, lengths, n_calls, d_out, out_off, frames_out, ctx->stream, ms, pitch, track);
   return SG_OK;
 }
 
@@ -1141,7 +1140,7 @@ void analyze_sweep(sg_ctx* ctx, const float* d_x, const int64_t* offsets, const 
   const bool use_store = g_sweep_store != 0;
   hipStream_t s = ctx->stream;
   HIPCHK(hipSetDevice(ctx->device));
-  StageClock clk(s, ctx->profiling ? g_sweep_ms : nullptr, kSweepStages);
+  StageClock clk(s, g_sweep_ms.sink(ctx), kSweepStages);
   clk.zero();
   auto timed = [&](int stage, auto&& launch) {  // what follows up to the next stamp (an upload at most) counts with it
     clk.stamp(stage);
@@ -1318,7 +1317,7 @@ int sg_analyze_frames(sg_ctx* ctx, const double* wave, int64_t len, const sg_ana
     if (len <= S.spg.wl)
       throw sg::SgError(SG_E_ARG, "sg_analyze_frames: the sound is not longer than the window (the reference's amplitude "
                                   "window sound[a:(a + wl)] leaves it)");
-    return frames_single(ctx, S, nullptr, g_anl_ms, wave, len, out);
+    return frames_single(ctx, S, nullptr, g_anl_ms.sink(ctx), wave, len, out);
   });
 }
 
@@ -1326,11 +1325,10 @@ int sg_analyze_frames_batch(sg_ctx* ctx, const float* d_wave, const int64_t* off
                             int64_t n_calls, const sg_analyze_params* p, double* d_out, const int64_t* out_off,
                             int32_t* frames_out) {
   return guarded(ctx, [&]() {
-    if (!ctx || !p || n_calls < 0 || n_calls > 2147483647LL ||
-        (n_calls > 0 && (!d_wave || !offsets || !lengths || !d_out || !out_off || !frames_out)))
-      throw sg::SgError(SG_E_ARG, "sg_analyze_frames_batch: bad arguments");
+    if (!ctx || !p) sg::bad_arguments("sg_analyze_frames_batch");
+    sg::batch_args("sg_analyze_frames_batch", n_calls, {d_wave, offsets, lengths, d_out, out_off, frames_out});
     const sg::AnlSetup S = sg::anl_setup(*p);
-    return frames_batch(ctx, S, nullptr, g_anl_ms, d_wave, offsets, lengths, n_calls, d_out, out_off, frames_out);
+    return frames_batch(ctx, S, nullptr, g_anl_ms.sink(ctx), d_wave, offsets, lengths, n_calls, d_out, out_off, frames_out);
   });
 }
 
@@ -1341,7 +1339,7 @@ int sg_pitch_candidates(sg_ctx* ctx, const double* wave, int64_t len, const sg_p
     if (len <= S.spg.wl)
       throw sg::SgError(SG_E_ARG, "sg_pitch_candidates: the sound is not longer than the window (the reference's amplitude "
                                   "window sound[a:(a + wl)] leaves it)");
-    return frames_single(ctx, S, &S, g_pitch_ms, wave, len, out);
+    return frames_single(ctx, S, &S, g_pitch_ms.sink(ctx), wave, len, out);
   });
 }
 
@@ -1349,11 +1347,10 @@ int sg_pitch_candidates_batch(sg_ctx* ctx, const float* d_wave, const int64_t* o
                               int64_t n_calls, const sg_pitch_params* p, double* d_out, const int64_t* out_off,
                               int32_t* frames_out) {
   return guarded(ctx, [&]() {
-    if (!ctx || !p || n_calls < 0 || n_calls > 2147483647LL ||
-        (n_calls > 0 && (!d_wave || !offsets || !lengths || !d_out || !out_off || !frames_out)))
-      throw sg::SgError(SG_E_ARG, "sg_pitch_candidates_batch: bad arguments");
+    if (!ctx || !p) sg::bad_arguments("sg_pitch_candidates_batch");
+    sg::batch_args("sg_pitch_candidates_batch", n_calls, {d_wave, offsets, lengths, d_out, out_off, frames_out});
     const sg::PitchSetup S = sg::pitch_setup(*p);
-    return frames_batch(ctx, S, &S, g_pitch_ms, d_wave, offsets, lengths, n_calls, d_out, out_off, frames_out);
+    return frames_batch(ctx, S, &S, g_pitch_ms.sink(ctx), d_wave, offsets, lengths, n_calls, d_out, out_off, frames_out);
   });
 }
 
@@ -1364,18 +1361,17 @@ int sg_analyze(sg_ctx* ctx, const double* wave, int64_t len, const sg_analyze_pa
     if (len <= S.spg.wl)
       throw sg::SgError(SG_E_ARG, "sg_analyze: the sound is not longer than the window (the reference's amplitude window "
                                   "sound[a:(a + wl)] leaves it)");
-    return frames_single(ctx, S, &S, g_track_ms, wave, len, out, &S);
+    return frames_single(ctx, S, &S, g_track_ms.sink(ctx), wave, len, out, &S);
   });
 }
 
 int sg_analyze_batch(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, const int64_t* lengths, int64_t n_calls,
                      const sg_analyze_params_full* p, double* d_out, const int64_t* out_off, int32_t* frames_out) {
   return guarded(ctx, [&]() {
-    if (!ctx || !p || n_calls < 0 || n_calls > 2147483647LL ||
-        (n_calls > 0 && (!d_wave || !offsets || !lengths || !d_out || !out_off || !frames_out)))
-      throw sg::SgError(SG_E_ARG, "sg_analyze_batch: bad arguments");
+    if (!ctx || !p) sg::bad_arguments("sg_analyze_batch");
+    sg::batch_args("sg_analyze_batch", n_calls, {d_wave, offsets, lengths, d_out, out_off, frames_out});
     const sg::TrackSetup S = sg::track_setup(*p);
-    return frames_batch(ctx, S, &S, g_track_ms, d_wave, offsets, lengths, n_calls, d_out, out_off, frames_out, &S);
+    return frames_batch(ctx, S, &S, g_track_ms.sink(ctx), d_wave, offsets, lengths, n_calls, d_out, out_off, frames_out, &S);
   });
 }
 
@@ -1401,7 +1397,7 @@ static int pitch_path_run(sg_ctx* ctx, const char* who, const double* table, int
     sg::DevBuf db;
     double* d_rows = sg::upload_sound(db, out, (int64_t)frames * P.cols, ctx->stream);
     double* d_segs = n_segments ? db.get<double>((size_t)sg::path_seg_cells(frames)) : nullptr;
-    sg::path_device(P, frames, hw, d_rows, ctx->stream, ctx->profiling ? g_track_ms : nullptr, d_segs);
+    sg::path_device(P, frames, hw, d_rows, ctx->stream, g_track_ms.sink(ctx), d_segs);
     HIPCHK(hipMemcpy(out, d_rows, (size_t)frames * P.cols * sizeof(double), hipMemcpyDeviceToHost));
     if (n_segments) {
       std::vector<double> h((size_t)sg::path_seg_cells(frames));
@@ -1439,7 +1435,7 @@ int sg_analyze_summary(sg_ctx* ctx, const double* table, int32_t frames, int32_t
     double* d_sum = db.get<double>(sg::kSumCols);
     // a failed call (len < 0) has no table: NaN, as in a batch
     const std::vector<sg::SumSound> one(1, sg::SumSound{0, len, len < 0 ? 0 : frames, 0});
-    sg::summary_device(one, cols, samplingRate, d_rows, d_sum, ctx->stream, ctx->profiling ? g_summary_ms : nullptr);
+    sg::summary_device(one, cols, samplingRate, d_rows, d_sum, ctx->stream, g_summary_ms.sink(ctx));
     HIPCHK(hipMemcpy(out, d_sum, sg::kSumCols * sizeof(double), hipMemcpyDeviceToHost));
     return (int)SG_OK;
   });
@@ -1449,15 +1445,13 @@ int sg_analyze_summary_batch(sg_ctx* ctx, const float* d_wave, const int64_t* of
                              int64_t n_calls, const sg_analyze_params_full* p, double* d_tables, const int64_t* out_off,
                              int32_t* frames_out, double* d_summary) {
   return guarded(ctx, [&]() {
-    if (!ctx || !p || n_calls < 0 || n_calls > 2147483647LL ||
-        (n_calls > 0 && (!d_wave || !offsets || !lengths || !d_tables || !out_off || !frames_out || !d_summary)))
-      throw sg::SgError(SG_E_ARG, "sg_analyze_summary_batch: bad arguments");
+    if (!ctx || !p) sg::bad_arguments("sg_analyze_summary_batch");
+    sg::batch_args("sg_analyze_summary_batch", n_calls, {d_wave, offsets, lengths, d_tables, out_off, frames_out, d_summary});
     const sg::TrackSetup S = sg::track_setup(*p);
     if (n_calls == 0) return (int)SG_OK;
     HIPCHK(hipSetDevice(ctx->device));
     sg::analyze_device<float>(S, d_wave, offsets, lengths, n_calls, d_tables, out_off, frames_out, ctx->stream,
-                              ctx->profiling ? g_track_ms : nullptr, &S, &S, d_summary,
-                              ctx->profiling ? g_summary_ms : nullptr);
+                              g_track_ms.sink(ctx), &S, &S, d_summary, g_summary_ms.sink(ctx));
     return (int)SG_OK;
   });
 }
@@ -1477,8 +1471,8 @@ int sg_analyze_summary_sound(sg_ctx* ctx, const double* wave, int64_t len, const
     double* d_o = db.get<double>((size_t)cells);
     double* d_sum = db.get<double>(sg::kSumCols);
     int32_t f = 0;
-    sg::analyze_device<double>(S, d, &off, &len, 1, d_o, &off, &f, ctx->stream, ctx->profiling ? g_track_ms : nullptr, &S, &S,
-                               d_sum, ctx->profiling ? g_summary_ms : nullptr);
+    sg::analyze_device<double>(S, d, &off, &len, 1, d_o, &off, &f, ctx->stream, g_track_ms.sink(ctx), &S, &S,
+                               d_sum, g_summary_ms.sink(ctx));
     if (out) HIPCHK(hipMemcpy(out, d_o, (size_t)cells * sizeof(double), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(summary, d_sum, sg::kSumCols * sizeof(double), hipMemcpyDeviceToHost));
     return (int)SG_OK;
@@ -1488,9 +1482,9 @@ int sg_analyze_summary_sound(sg_ctx* ctx, const double* wave, int64_t len, const
 int sg_analyze_sweep(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, const int64_t* lengths, int64_t n_calls,
                      const sg_analyze_params_full* rows, int64_t n_rows, int64_t workspace_cap, double* d_out) {
   return guarded(ctx, [&]() {
-    if (!ctx || n_calls < 0 || n_calls > 2147483647LL || n_rows < 0 || workspace_cap < 0 || (n_rows > 0 && !rows) ||
-        (n_calls > 0 && (!d_wave || !offsets || !lengths)) || (n_calls > 0 && n_rows > 0 && !d_out))
-      throw sg::SgError(SG_E_ARG, "sg_analyze_sweep: bad arguments");
+    if (!ctx || n_rows < 0 || workspace_cap < 0 || (n_rows > 0 && !rows) || (n_calls > 0 && n_rows > 0 && !d_out))
+      sg::bad_arguments("sg_analyze_sweep");
+    sg::batch_args("sg_analyze_sweep", n_calls, {d_wave, offsets, lengths});
     if (n_rows == 0) return (int)SG_OK;
     if (n_calls == 0) {
       (void)sg::anl_sweep_plan(rows, n_rows);  // the rows are still judged
@@ -1507,34 +1501,14 @@ int sg_set_analyze_sweep_store(int32_t mode) {
   return SG_OK;
 }
 
-int sg_debug_analyze_sweep_kernel_ms(double* out) {
-  if (!out) return SG_E_ARG;
-  for (int k = 0; k < sg::kSweepStages; ++k) out[k] = g_sweep_ms[k];
-  return SG_OK;
-}
+int sg_debug_analyze_sweep_kernel_ms(double* out) { return g_sweep_ms.read(out); }
 
-int sg_debug_summary_kernel_ms(double* out) {
-  if (!out) return SG_E_ARG;
-  out[0] = g_summary_ms[0];
-  return SG_OK;
-}
+int sg_debug_summary_kernel_ms(double* out) { return g_summary_ms.read(out); }
 
-int sg_debug_track_kernel_ms(double* out) {
-  if (!out) return SG_E_ARG;
-  for (int k = 0; k < sg::kTrackStages; ++k) out[k] = g_track_ms[k];
-  return SG_OK;
-}
+int sg_debug_track_kernel_ms(double* out) { return g_track_ms.read(out); }
 
-int sg_debug_pitch_kernel_ms(double* out) {
-  if (!out) return SG_E_ARG;
-  for (int k = 0; k < sg::kPitchStages; ++k) out[k] = g_pitch_ms[k];
-  return SG_OK;
-}
+int sg_debug_pitch_kernel_ms(double* out) { return g_pitch_ms.read(out); }
 
-int sg_debug_analyze_kernel_ms(double* out) {
-  if (!out) return SG_E_ARG;
-  for (int k = 0; k < sg::kAnlStages; ++k) out[k] = g_anl_ms[k];
-  return SG_OK;
-}
+int sg_debug_analyze_kernel_ms(double* out) { return g_anl_ms.read(out); }
 
 }  // extern "C"

@@ -161,7 +161,7 @@ __global__ __launch_bounds__(kRootWaves * 64) void sg_fmt_roots(const FmtFrame* 
   }
 }
 
-double g_fmt_ms[kFmtStages];  // of the last profiled run
+sg::StageTimes<kFmtStages> g_fmt_ms;  // of the last profiled run
 int64_t g_fmt_count[3];       // of the last run: capped, analysed, iterations
 
 // The two kernels on the context's stream for the frames in fr; synchronises
@@ -378,7 +378,7 @@ __global__ __launch_bounds__(128) void sg_fmt_sound_fold(const FmtSound* __restr
   lags[(int64_t)Sd.row * (sg::kFmtMaxOrder + 1) + k] = s;
 }
 
-double g_fmtw_ms[kFmtWholeStages];  // of the last profiled run
+sg::StageTimes<kFmtWholeStages> g_fmtw_ms;  // of the last profiled run
 int64_t g_fmtw_count[3];            // of the last run: capped, analysed, iterations
 
 // the order of findformants at fs; refuses what the wave cannot hold
@@ -487,7 +487,7 @@ int sg_formants_whole(sg_ctx* ctx, const double* wave, int64_t len, double fs, d
     HIPCHK(hipSetDevice(ctx->device));
     const int64_t off = 0;
     sg::single_sound(ctx, wave, len, 2 * sg::kFmtMaxFormants, out, [&](const double* d, double* d_o) {
-      formants_whole_device<double>(d, &off, &len, 1, order, fs, d_o, ctx->stream, ctx->profiling ? g_fmtw_ms : nullptr);
+      formants_whole_device<double>(d, &off, &len, 1, order, fs, d_o, ctx->stream, g_fmtw_ms.sink(ctx));
     });
     return (int)SG_OK;
   });
@@ -496,39 +496,35 @@ int sg_formants_whole(sg_ctx* ctx, const double* wave, int64_t len, double fs, d
 int sg_formants_whole_batch(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, const int64_t* lengths, int64_t n_calls,
                             double fs, double* d_out) {
   return sg::guarded(ctx, [&]() {
-    if (!ctx || n_calls < 0 || n_calls > 2147483647LL || (n_calls > 0 && (!d_wave || !offsets || !lengths || !d_out)))
-      throw sg::SgError(SG_E_ARG, "sg_formants_whole_batch: bad arguments");
+    if (!ctx) sg::bad_arguments("sg_formants_whole_batch");
+    sg::batch_args("sg_formants_whole_batch", n_calls, {d_wave, offsets, lengths, d_out});
     const int order = whole_order(fs);
     for (int64_t c = 0; c < n_calls; ++c) whole_chunks(lengths[c]);
     if (n_calls == 0) return (int)SG_OK;
     HIPCHK(hipSetDevice(ctx->device));
-    formants_whole_device<float>(d_wave, offsets, lengths, n_calls, order, fs, d_out, ctx->stream,
-                                 ctx->profiling ? g_fmtw_ms : nullptr);
+    formants_whole_device<float>(d_wave, offsets, lengths, n_calls, order, fs, d_out, ctx->stream, g_fmtw_ms.sink(ctx));
     return (int)SG_OK;
   });
 }
 
 int sg_debug_formants_whole_kernel_ms(double* out, int64_t* counts) {
-  if (!out) return SG_E_ARG;
-  for (int k = 0; k < kFmtWholeStages; ++k) out[k] = g_fmtw_ms[k];
-  for (int k = 0; counts && k < 3; ++k) counts[k] = g_fmtw_count[k];
-  return SG_OK;
+  for (int k = 0; out && counts && k < 3; ++k) counts[k] = g_fmtw_count[k];
+  return g_fmtw_ms.read(out);
 }
 
 int sg_formants_batch(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, const int64_t* lengths, int64_t n_calls,
                       const sg_analyze_params* p, int32_t nFormants, const double* d_tables, const int64_t* out_off,
                       int32_t table_cols, const int32_t* frames, double* d_fmt, const int64_t* fmt_off) {
   return sg::guarded(ctx, [&]() {
-    if (!ctx || !p || n_calls < 0 || n_calls > 2147483647LL || table_cols <= sg::kCondSilence ||
-        (n_calls > 0 && (!d_wave || !offsets || !lengths || !d_tables || !out_off || !frames || !d_fmt || !fmt_off)))
-      throw sg::SgError(SG_E_ARG, "sg_formants_batch: bad arguments");
+    if (!ctx || !p || table_cols <= sg::kCondSilence) sg::bad_arguments("sg_formants_batch");
+    sg::batch_args("sg_formants_batch", n_calls, {d_wave, offsets, lengths, d_tables, out_off, frames, d_fmt, fmt_off});
     const int order = sg::formants_order(p->samplingRate, nFormants);
     const sg::AnlSetup S = sg::anl_setup_any(*p);
     sg::formants_window(S.spg.wl, order);
     if (n_calls == 0) return (int)SG_OK;
     HIPCHK(hipSetDevice(ctx->device));
     formants_device<float>(S, order, nFormants, d_wave, offsets, lengths, n_calls, d_tables, out_off, table_cols, frames, d_fmt,
-                           fmt_off, ctx->stream, ctx->profiling ? g_fmt_ms : nullptr);
+                           fmt_off, ctx->stream, g_fmt_ms.sink(ctx));
     return (int)SG_OK;
   });
 }
@@ -552,7 +548,7 @@ int sg_formants_sound(sg_ctx* ctx, const double* wave, int64_t len, const sg_ana
     int32_t f = 0;
     sg::analyze_device<double>(S, d, &off, &len, 1, d_t, &off, &f, ctx->stream, nullptr);  // the gate
     formants_device<double>(S, order, nFormants, d, &off, &len, 1, d_t, &off, S.cols, &f, d_f, &off, ctx->stream,
-                            ctx->profiling ? g_fmt_ms : nullptr);
+                            g_fmt_ms.sink(ctx));
     HIPCHK(hipMemcpy(out, d_f, (size_t)nf * 2 * nFormants * sizeof(double), hipMemcpyDeviceToHost));
     return (int)SG_OK;
   });
@@ -574,17 +570,15 @@ int sg_formants_frames(sg_ctx* ctx, const double* frames, int32_t n, int32_t nfr
     std::vector<FmtFrame> fr(nframes);
     for (int32_t f = 0; f < nframes; ++f) fr[f] = FmtFrame{(int64_t)f * n, -1, (int64_t)f * 2 * nFormants, 0, 0};
     formants_launch<double>(d, fr, nullptr, nullptr, nullptr, make_k(n, order, nFormants, 0, fs), d_f, ctx->stream,
-                            ctx->profiling ? g_fmt_ms : nullptr);
+                            g_fmt_ms.sink(ctx));
     HIPCHK(hipMemcpy(out, d_f, (size_t)nframes * 2 * nFormants * sizeof(double), hipMemcpyDeviceToHost));
     return (int)SG_OK;
   });
 }
 
 int sg_debug_formants_kernel_ms(double* out, int64_t* counts) {
-  if (!out) return SG_E_ARG;
-  for (int k = 0; k < kFmtStages; ++k) out[k] = g_fmt_ms[k];
-  for (int k = 0; counts && k < 3; ++k) counts[k] = g_fmt_count[k];
-  return SG_OK;
+  for (int k = 0; out && counts && k < 3; ++k) counts[k] = g_fmt_count[k];
+  return g_fmt_ms.read(out);
 }
 
 }  // extern "C"

@@ -1,7 +1,6 @@
 // sg_invert.h — stft(), istft() and invert_spectrogram(): the integer side of the
 // operator pair (A, A+) that sg_invert.hip runs, for the host and for the device:
-// the frames of a sound and their starts (getFrameBank's, R/spectrogram.R:350-351, as
-// sg_spectrogram.cpp decides them), which frames cover a sample, the sizes of what a
+// which frames of a sound (getFrameBank's grid, sg_frame_grid.h) cover a sample, the sizes of what a
 // sound leaves in HBM and of the workspace an iteration needs, and the refusals that
 // are this feature's own. No HIP header is needed on the host side
 // (tests/cpp/ola_pins.cpp builds it alone).
@@ -12,37 +11,13 @@
 //       x^[t] = sum_i w[t - s_i] y_i[t - s_i] / sum_i w[t - s_i]^2 over the frames that
 //       cover t, in frame order; 0 where that denominator is 0. No other floor.
 #pragma once
-#include <math.h>
-#include <stdint.h>
-
-#if defined(__HIPCC__)
-#define SG_INV_HD __host__ __device__
-#else
-#define SG_INV_HD
-#endif
+#include "sg_frame_grid.h"
 
 namespace sg {
 
 constexpr int kInvStages = 6;  // sg_debug_invert_kernel_ms: statistics, forward (+ projection), start, inverse, overlap-add, error fold
 constexpr int kInvTile = 256;  // output samples per workgroup of sg_inv_ola
 constexpr int64_t kInvWorkspaceCap = (int64_t)1 << 30;  // bytes a chunk's workspace may take when the caller gives 0
-
-// seq(1, max(1, len - wl), by)'s count (0 for len <= 1 or len < wl) and floor(min(1 + i by, to)) - 1:
-// spg_frames / spg_frame_start (sg_spectrogram.cpp) restated, the product and the sum unfused as there
-SG_INV_HD inline int64_t inv_frames(double by, int wl, int64_t len) {
-  if (len <= 1 || len < wl) return 0;
-  const double to = (double)(len - wl > 1 ? len - wl : 1);
-  return (int64_t)floor((to - 1.0) / by + 1e-10) + 1;
-}
-SG_INV_HD inline int64_t inv_frame_start(double by, int wl, int64_t len, int64_t i) {
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
-  const double to = (double)(len - wl > 1 ? len - wl : 1);
-  const double prod = (double)i * by;
-  const double v = 1.0 + prod;
-  return (int64_t)floor(v < to ? v : to) - 1;
-}
 
 // The frames [first, last] of F with s_i <= t < s_i + wl; last < first: none covers t.
 // start(i) = s_i, non-decreasing in i (equal starts happen: by < 1, the clamp at len - wl).
@@ -53,7 +28,7 @@ struct InvCover {
   int64_t first, last;
 };
 template <class Start>
-SG_INV_HD inline InvCover inv_cover(int64_t t, int wl, int64_t F, double by, Start start) {
+SG_HD inline InvCover inv_cover(int64_t t, int wl, int64_t F, double by, Start start) {
   InvCover c{0, -1};
   if (F <= 0 || t < 0) return c;
   const double top = (double)(F - 1);
@@ -76,10 +51,10 @@ SG_INV_HD inline InvCover inv_cover(int64_t t, int wl, int64_t F, double by, Sta
 
 // What a sound of `frames` frames takes in HBM. A matrix has rows = bins (the reference's
 // shape: DC in, Nyquist out) or bins + 1 rows, frame after frame.
-SG_INV_HD inline bool inv_rows_ok(int rows, int bins) { return rows == bins || rows == bins + 1; }
+SG_HD inline bool inv_rows_ok(int rows, int bins) { return rows == bins || rows == bins + 1; }
 // bytes of workspace a sound needs inside istft / invert_spectrogram: the bins + 1 complex bins
 // of every frame, its wl windowed samples, and the two error sums of a frame
-SG_INV_HD inline int64_t inv_workspace_bytes(int64_t frames, int wl, int bins) {
+SG_HD inline int64_t inv_workspace_bytes(int64_t frames, int wl, int bins) {
   return frames * ((int64_t)(bins + 1) * 16 + (int64_t)wl * 8 + 16);
 }
 

@@ -219,8 +219,7 @@ __global__ __launch_bounds__(kT) void sg_inv_ola(const InvTile* __restrict__ til
   out[S.xbase + t] = den == 0 ? 0.0 : num / den;
 }
 
-double g_inv_ms[sg::kInvStages];  // of the last profiled launch sequence
-thread_local std::string g_inv_size_err;
+sg::StageTimes<sg::kInvStages> g_inv_ms;  // of the last profiled launch sequence
 
 // The tables of sounds [c0, c1) of a batch. Spectra and workspaces are laid out one sound after
 // the other from 0 unless spec_off says where each spectrum is.
@@ -238,7 +237,6 @@ InvTables inv_tables(const sg::SpgSetup& S, int64_t c0, int64_t c1, const int64_
   for (int64_t c = c0; c < c1; ++c) {
     const int64_t len = lengths[c] > 0 ? lengths[c] : 0;
     const int nf = sg::spg_frames(S, len);
-    if ((int64_t)nf != sg::inv_frames(S.by, S.wl, len)) throw sg::SgError(SG_E_DEVICE, "invert: frame counts disagree");
     InvSound& Q = T.snds[(size_t)(c - c0)];
     Q.xbase = xoff[c];
     Q.len = len;
@@ -250,9 +248,6 @@ InvTables inv_tables(const sg::SpgSetup& S, int64_t c0, int64_t c1, const int64_
     if ((int64_t)T.tiles.size() + len / kT + 1 > 2147483647LL)
       throw sg::SgError(SG_E_UNSUPPORTED, "invert: the frames of one launch exceed 2^31");
     sg::spg_list_frames(S, len, nf, (int32_t)(c - c0), "invert", T.fr);
-    for (int f = 0; f < nf; ++f)  // sg_invert.h's restatement, which sg_inv_ola's cover walks
-      if (T.fr[(size_t)Q.f0 + f].o != sg::inv_frame_start(S.by, S.wl, len, f))
-        throw sg::SgError(SG_E_DEVICE, "invert: a frame leaves its sound");
     if (with_tiles)
       for (int64_t k = 0; k * kT < len; ++k) T.tiles.push_back(InvTile{(int32_t)(c - c0), (int32_t)k});
     T.spec_cells += (int64_t)nf * rows;
@@ -313,7 +308,7 @@ void stft_device(sg_ctx* ctx, const sg::SpgSetup& S, const T* d_x, const int64_t
                  int64_t n_calls, int rows, double2* d_out, const int64_t* out_off) {
   hipStream_t s = ctx->stream;
   const InvTables Tb = inv_tables(S, 0, n_calls, offsets, lengths, out_off, nullptr, rows, false);
-  sg::StageClock clk(s, ctx->profiling ? g_inv_ms : nullptr, sg::kInvStages);
+  sg::StageClock clk(s, g_inv_ms.sink(ctx), sg::kInvStages);
   clk.zero();
   if (Tb.fr.empty()) return;
   DevBuf db;
@@ -400,16 +395,13 @@ int sg_spg_stft_batch(sg_ctx* ctx, const void* d_wave, int32_t is_f64, const int
     if (!p) throw sg::SgError(SG_E_ARG, "sg_spg_stft_batch: bad arguments");
     const sg::SpgSetup S = sg::spg_setup(*p);  // spectrogram()'s refusals, before anything else
     check_rows(S, rows, "sg_spg_stft_batch");
-    if (!ctx || n_calls < 0 || n_calls > 2147483647LL || (n_calls > 0 && (!d_wave || !offsets || !lengths || !d_out || !out_off)))
-      throw sg::SgError(SG_E_ARG, "sg_spg_stft_batch: bad arguments");
+    if (!ctx) sg::bad_arguments("sg_spg_stft_batch");
+    sg::batch_args("sg_spg_stft_batch", n_calls, {d_wave, offsets, lengths, d_out, out_off});
     if (n_calls == 0) return SG_OK;
     HIPCHK(hipSetDevice(ctx->device));
-    if (is_f64)
-      stft_device<double>(ctx, S, static_cast<const double*>(d_wave), offsets, lengths, n_calls, rows,
-                          reinterpret_cast<double2*>(d_out), out_off);
-    else
-      stft_device<float>(ctx, S, static_cast<const float*>(d_wave), offsets, lengths, n_calls, rows,
-                         reinterpret_cast<double2*>(d_out), out_off);
+    sg::with_samples(is_f64 != 0, d_wave, [&](auto* d_x) {
+      stft_device(ctx, S, d_x, offsets, lengths, n_calls, rows, reinterpret_cast<double2*>(d_out), out_off);
+    });
     return SG_OK;
   });
 }
@@ -420,13 +412,13 @@ int sg_spg_istft_batch(sg_ctx* ctx, const double* d_spec, const int64_t* spec_of
     if (!p) throw sg::SgError(SG_E_ARG, "sg_spg_istft_batch: bad arguments");
     const sg::SpgSetup S = sg::spg_setup(*p);
     check_rows(S, rows, "sg_spg_istft_batch");
-    if (!ctx || n_calls < 0 || n_calls > 2147483647LL || (n_calls > 0 && (!d_spec || !spec_off || !lengths || !d_out || !out_off)))
-      throw sg::SgError(SG_E_ARG, "sg_spg_istft_batch: bad arguments");
+    if (!ctx) sg::bad_arguments("sg_spg_istft_batch");
+    sg::batch_args("sg_spg_istft_batch", n_calls, {d_spec, spec_off, lengths, d_out, out_off});
     if (n_calls == 0) return SG_OK;
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const InvTables Tb = inv_tables(S, 0, n_calls, out_off, lengths, spec_off, nullptr, rows, true);
-    sg::StageClock clk(s, ctx->profiling ? g_inv_ms : nullptr, sg::kInvStages);
+    sg::StageClock clk(s, g_inv_ms.sink(ctx), sg::kInvStages);
     clk.zero();
     DevBuf db;
     const InvDev D = upload_tables(db, S, Tb, s);
@@ -448,9 +440,8 @@ int sg_invert_spectrogram_batch(sg_ctx* ctx, const double* d_mag, const int64_t*
     if (!p) throw sg::SgError(SG_E_ARG, "sg_invert_spectrogram_batch: bad arguments");
     const sg::SpgSetup S = sg::spg_setup(*p);
     check_rows(S, rows, "sg_invert_spectrogram_batch");
-    if (!ctx || n_calls < 0 || n_calls > 2147483647LL || n_iter < 0 || workspace_cap < 0 ||
-        (n_calls > 0 && (!d_mag || !mag_off || !lengths || !d_out || !out_off)))
-      throw sg::SgError(SG_E_ARG, "sg_invert_spectrogram_batch: bad arguments");
+    if (!ctx || n_iter < 0 || workspace_cap < 0) sg::bad_arguments("sg_invert_spectrogram_batch");
+    sg::batch_args("sg_invert_spectrogram_batch", n_calls, {d_mag, mag_off, lengths, d_out, out_off});
     if (n_calls == 0) return SG_OK;
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
@@ -458,7 +449,7 @@ int sg_invert_spectrogram_batch(sg_ctx* ctx, const double* d_mag, const int64_t*
     lds_opt_in(&sg_inv_frames, lds, "sg_inv_frames");
     lds_opt_in(&sg_inv_project, lds, "sg_inv_project");
     const std::vector<int64_t> ends = chunk_ends(S, lengths, n_calls, workspace_cap > 0 ? workspace_cap : sg::kInvWorkspaceCap);
-    sg::StageClock clk(s, ctx->profiling ? g_inv_ms : nullptr, sg::kInvStages);
+    sg::StageClock clk(s, g_inv_ms.sink(ctx), sg::kInvStages);
     clk.zero();
     DevBuf top;
     double* d_err = top.get<double>((size_t)n_calls * (size_t)std::max(n_iter, 1));
@@ -509,36 +500,22 @@ int sg_invert_spectrogram_batch(sg_ctx* ctx, const double* d_mag, const int64_t*
 
 int sg_invert_size(int64_t len, const sg_spectrogram_params* p, int32_t rows, int32_t* wl, int32_t* n_fft, int32_t* bins,
                    int32_t* frames, int64_t* samples, int64_t* workspace_bytes) {
-  if (!p || !wl || !n_fft || !bins || !frames || !samples || !workspace_bytes) {
-    g_inv_size_err = "sg_invert_size: bad arguments";
-    return SG_E_ARG;
-  }
-  try {
+  return sg::host_guarded([&]() {
+    if (!p || !wl || !n_fft || !bins || !frames || !samples || !workspace_bytes) sg::bad_arguments("sg_invert_size");
     const sg::SpgSetup S = sg::spg_setup(*p);
     if (rows != 0) check_rows(S, rows, "sg_invert_size");
-    if (len < 0) throw sg::SgError(SG_E_ARG, "sg_invert_size: bad arguments");
+    if (len < 0) sg::bad_arguments("sg_invert_size");
     *wl = S.wl;
     *n_fft = S.N;
     *bins = S.bins;
     *frames = sg::spg_frames(S, len);
     *samples = len;
     *workspace_bytes = sg::inv_workspace_bytes(*frames, S.wl, S.bins);
-    return SG_OK;
-  } catch (const sg::SgError& e) {
-    g_inv_size_err = e.what();
-    return e.code;
-  } catch (...) {
-    g_inv_size_err = "out of host memory";
-    return SG_E_NOMEM;
-  }
+  });
 }
 
-const char* sg_invert_size_error(void) { return g_inv_size_err.c_str(); }
+const char* sg_invert_size_error(void) { return sg::g_host_err.c_str(); }
 
-int sg_debug_invert_kernel_ms(double* out) {
-  if (!out) return SG_E_ARG;
-  for (int k = 0; k < sg::kInvStages; ++k) out[k] = g_inv_ms[k];
-  return SG_OK;
-}
+int sg_debug_invert_kernel_ms(double* out) { return g_inv_ms.read(out); }
 
 }  // extern "C"

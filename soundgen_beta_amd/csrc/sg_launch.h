@@ -1,15 +1,16 @@
 // sg_launch.h — what every host-side launch sequence (the synthesis executor sg_exec.cpp and
 // its launchers; the analysis features sg_mel.hip, sg_ssm.hip, sg_spectrogram.hip, sg_analyze.hip,
 // sg_segment.hip) and the C entry points (theirs and sg_api.cpp's) share: the HIP error check, the buffers of a
-// launch sequence, the opt-in for dynamic LDS, the exception-to-code mapping of an entry point, the per-stage
-// device clock and the single-sound round trip. Host code that needs the HIP runtime.
+// launch sequence, the opt-in for dynamic LDS, what an entry point needs around its launch sequence (guarded,
+// batch_args, with_samples, StageTimes; the exception ladder itself is sg_rmath.h's), the per-stage device
+// clock and the single-sound round trip. Host code that needs the HIP runtime.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <initializer_list>
 #include <map>
 #include <mutex>
-#include <new>
 #include <string>
 #include <utility>
 #include <vector>
@@ -86,27 +87,43 @@ void lds_opt_in(K* kernel, int lds_bytes, const char* name) {
   lds_opt_in(reinterpret_cast<const void*>(kernel), lds_bytes, name);
 }
 
-// The body of a C entry point: f()'s value, or the code of what it throws with
-// the text left in ctx (when there is one) for sg_last_error
+// The body of a C entry point with a context: sg::caught, the text left in ctx (when
+// there is one) for sg_last_error
 template <class F>
 int guarded(sg_ctx* ctx, F&& f) {
-  int code;
-  std::string msg;
-  try {
-    return f();
-  } catch (const SgError& e) {
-    code = e.code;
-    msg = e.what();
-  } catch (const std::bad_alloc&) {
-    code = SG_E_NOMEM;
-    msg = "out of host memory";
-  } catch (const std::exception& e) {
-    code = SG_E_ARG;
-    msg = e.what();
-  }
-  if (ctx) ctx->err = msg;
-  return code;
+  return caught(ctx ? &ctx->err : nullptr, f);
 }
+
+// What every batch entry point refuses as "`who`: bad arguments": a count that is negative or
+// beyond 2^31 - 1, or a null among the pointers a non-empty batch needs
+inline void batch_args(const char* who, int64_t n_calls, std::initializer_list<const void*> needed) {
+  bool bad = n_calls < 0 || n_calls > 2147483647LL;
+  for (const void* q : needed) bad = bad || (n_calls > 0 && !q);
+  if (bad) bad_arguments(who);
+}
+
+// f(const double*) or f(const float*) on the samples at d_wave: f is a generic lambda
+template <class F>
+void with_samples(bool is_f64, const void* d_wave, F&& f) {
+  if (is_f64)
+    f(static_cast<const double*>(d_wave));
+  else
+    f(static_cast<const float*>(d_wave));
+}
+
+// The stage milliseconds of a feature's last profiled launch sequence, which its
+// sg_debug_*_kernel_ms reader returns. Process-global because the readers take no context (the
+// ABI): two contexts that profile at once overwrite each other.
+template <int N>
+struct StageTimes {
+  double ms[N] = {};
+  double* sink(const sg_ctx* ctx) { return ctx->profiling ? ms : nullptr; }
+  int read(double* out) const {
+    if (!out) return SG_E_ARG;
+    std::copy(ms, ms + N, out);
+    return SG_OK;
+  }
+};
 
 // The device time of each stage of a launch sequence, between events on its stream
 // (profiling only; ms == nullptr: every call is a no-op). stamp() at each stage

@@ -537,7 +537,7 @@ void mel_run_spec(const MelRun& r, int64_t i, int nk, int nb, std::vector<double
   HIPCHK(hipStreamSynchronize(s));
 }
 
-double g_mel_pair_ms[2];  // of the last profiled compare_pairs (sg_debug_mel_pair_kernel_ms)
+StageTimes<2> g_mel_pair_ms;  // of the last profiled compare_pairs (sg_debug_mel_pair_kernel_ms)
 
 // compareSounds(target = sound pairs[2 p] of T, cand = sound pairs[2 p + 1] of C), two runs of
 // nb bands: sg_mel_pair, sg_mel_pair_reduce, then out[4 p + m] and summary[p] (may be null)
@@ -564,7 +564,7 @@ void compare_pairs(const MelRun& T, const MelRun& C, int nb, const int32_t* pair
   double* d_sims = db.get<double>((size_t)J * 4 + (size_t)n_pairs * 5);
   double* d_out = d_sims + J * 4;
   double* d_sum = d_out + n_pairs * 4;
-  StageClock clk(s, profile ? g_mel_pair_ms : nullptr, 2);
+  StageClock clk(s, profile ? g_mel_pair_ms.ms : nullptr, 2);
   clk.stamp();
   if (J > 0) {
     hipLaunchKernelGGL(sg_mel_pair, dim3((unsigned)J), dim3(64), (size_t)5 * nb * sizeof(double), s, d_pairs, d_job0,
@@ -644,9 +644,4 @@ void compare_sounds_pairs_device(const MelSet& T, const MelSet& C, const int32_t
 
 }  // namespace sg
 
-extern "C" int sg_debug_mel_pair_kernel_ms(double* out) {
-  if (!out) return SG_E_ARG;
-  out[0] = sg::g_mel_pair_ms[0];
-  out[1] = sg::g_mel_pair_ms[1];
-  return SG_OK;
-}
+extern "C" int sg_debug_mel_pair_kernel_ms(double* out) { return sg::g_mel_pair_ms.read(out); }

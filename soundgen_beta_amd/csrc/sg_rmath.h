@@ -5,6 +5,7 @@
 #pragma once
 #include <cmath>
 #include <cstdint>
+#include <new>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -50,6 +51,44 @@ struct SgError : std::runtime_error {
   int code;
   SgError(int c, const std::string& m) : std::runtime_error(m), code(c) {}
 };
+
+// The one exception ladder of the C boundary: f()'s value, or the code of what it throws, with
+// the text left in *text (when there is one)
+template <class F>
+int caught(std::string* text, F&& f) {
+  int code;
+  std::string msg;
+  try {
+    return f();
+  } catch (const SgError& e) {
+    code = e.code;
+    msg = e.what();
+  } catch (const std::bad_alloc&) {
+    code = SG_E_NOMEM;
+    msg = "out of host memory";
+  } catch (const std::exception& e) {
+    code = SG_E_ARG;
+    msg = e.what();
+  }
+  if (text) *text = msg;
+  return code;
+}
+
+[[noreturn]] inline void bad_arguments(const char* who) { throw SgError(SG_E_ARG, std::string(who) + ": bad arguments"); }
+
+// The body of a host-only entry point (the *_size family: no context to leave a text in), which
+// reports by throwing alone: SG_OK when f() returns. After such a call fails on a thread, every
+// *_size_error reader returns that call's text until the next host-only call on that thread,
+// which clears it on entry.
+inline thread_local std::string g_host_err;
+template <class F>
+int host_guarded(F&& f) {
+  g_host_err.clear();
+  return caught(&g_host_err, [&]() {
+    f();
+    return (int)SG_OK;
+  });
+}
 
 inline double r_round(double x) { return std::nearbyint(x); }
 

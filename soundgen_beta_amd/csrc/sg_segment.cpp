@@ -98,31 +98,12 @@ int64_t seg_out_cells(const sg_segment_params& p, const SegPlan& S) { return p.m
 
 }  // namespace sg
 
-namespace {
-thread_local std::string g_seg_size_err;
-
-template <class F>
-int size_guarded(F&& f) {
-  try {
-    g_seg_size_err.clear();
-    f();
-    return SG_OK;
-  } catch (const sg::SgError& e) {
-    g_seg_size_err = e.what();
-    return e.code;
-  } catch (...) {
-    g_seg_size_err = "out of host memory";
-    return SG_E_NOMEM;
-  }
-}
-}  // namespace
-
 extern "C" {
 
 int sg_segment_size(int64_t len, const sg_segment_params* p, int32_t* log2n, int32_t* n_env, int32_t* points,
                     int64_t* cells) {
-  if (!p || !log2n || !n_env || !points || !cells) return SG_E_ARG;
-  return size_guarded([&] {
+  return sg::host_guarded([&] {
+    if (!p || !log2n || !n_env || !points || !cells) sg::bad_arguments("sg_segment_size");
     const sg::SegPlan S = sg::seg_plan(*p, len, false);
     *log2n = S.p;
     *n_env = (int32_t)(p->mode == 1 ? S.n_env : S.m);
@@ -131,12 +112,12 @@ int sg_segment_size(int64_t len, const sg_segment_params* p, int32_t* log2n, int
   });
 }
 
-const char* sg_segment_size_error(void) { return g_seg_size_err.c_str(); }
+const char* sg_segment_size_error(void) { return sg::g_host_err.c_str(); }
 
 int sg_segment_windows(int64_t len, const sg_segment_params* p, int64_t* first, int64_t* points, int64_t* jump,
                        int32_t n, double* timestep) {
-  if (!p || !first || !points || !jump || !timestep || p->mode != 0) return SG_E_ARG;
-  return size_guarded([&] {
+  return sg::host_guarded([&] {
+    if (!p || !first || !points || !jump || !timestep || p->mode != 0) sg::bad_arguments("sg_segment_windows");
     const sg::SegPlan S = sg::seg_plan(*p, len, true);
     if (n != S.m) throw sg::SgError(SG_E_ARG, "sg_segment_windows: n is not the envelope's length");
     for (int32_t i = 0; i < n; ++i) {

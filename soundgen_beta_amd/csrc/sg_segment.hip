@@ -393,7 +393,7 @@ __global__ __launch_bounds__(kT) void sg_sweep_fit(const double* __restrict__ ma
   fit[r] = 1 - v;
 }
 
-double g_seg_ms[sg::kSegStages];  // of the last profiled launch sequence
+sg::StageTimes<sg::kSegStages> g_seg_ms;  // of the last profiled launch sequence
 
 // first root of the table of an M = 2^lg-point frame (2 M roots) among the tables of 2^1 .. 2^11
 int root_table(int lg) { return (1 << (lg + 1)) - 4; }
@@ -635,7 +635,7 @@ namespace {
 // other rows and sounds share the launch and however the rows are chunked.
 constexpr int kSweepLdsValues = 8192;  // 64 KiB of a CU's 160: two workgroups' envelopes
 int g_sweep_staging = 1;               // sg_set_sweep_staging
-double g_sweep_ms[sg::kSegStages];     // of the last profiled sweep
+sg::StageTimes<sg::kSegStages> g_sweep_ms;  // of the last profiled sweep
 
 struct Sweep : SegBehind {
   int64_t n_calls = 0;
@@ -751,8 +751,7 @@ void segment_sweep(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, con
   }
   W.chunk_end.push_back(n_rows);
   HIPCHK(hipSetDevice(ctx->device));
-  sg::segment_run<float>(p0, W.plans[0], d_wave, offsets, n_calls, nullptr, nullptr, ctx->stream,
-                         ctx->profiling ? g_sweep_ms : nullptr, &W);
+  sg::segment_run<float>(p0, W.plans[0], d_wave, offsets, n_calls, nullptr, nullptr, ctx->stream, g_sweep_ms.sink(ctx), &W);
 }
 
 void sweep_fitness(sg_ctx* ctx, const double* d_matrix, int64_t n_rows, int64_t n_calls, int32_t width, int32_t column,
@@ -776,9 +775,8 @@ extern "C" {
 int sg_segment_sweep(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, const int64_t* lengths, int64_t n_calls,
                      const sg_segment_params* rows, int64_t n_rows, double* d_out) {
   return sg::guarded(ctx, [&]() {
-    if (!ctx || n_calls < 0 || n_calls > 2147483647LL || n_rows < 0 || (n_rows > 0 && !rows) ||
-        (n_calls > 0 && (!d_wave || !offsets || !lengths)) || (n_calls > 0 && n_rows > 0 && !d_out))
-      throw sg::SgError(SG_E_ARG, "sg_segment_sweep: bad arguments");
+    if (!ctx || n_rows < 0 || (n_rows > 0 && !rows) || (n_calls > 0 && n_rows > 0 && !d_out)) sg::bad_arguments("sg_segment_sweep");
+    sg::batch_args("sg_segment_sweep", n_calls, {d_wave, offsets, lengths});
     if (n_calls == 0 || n_rows == 0) return (int)SG_OK;
     segment_sweep(ctx, d_wave, offsets, lengths, n_calls, rows, n_rows, d_out);
     return (int)SG_OK;
@@ -803,11 +801,7 @@ int sg_set_sweep_staging(int32_t mode) {
   return SG_OK;
 }
 
-int sg_debug_sweep_kernel_ms(double* out) {
-  if (!out) return SG_E_ARG;
-  for (int k = 0; k < sg::kSegStages; ++k) out[k] = g_sweep_ms[k];
-  return SG_OK;
-}
+int sg_debug_sweep_kernel_ms(double* out) { return g_sweep_ms.read(out); }
 
 int sg_segment(sg_ctx* ctx, const double* wave, int64_t len, const sg_segment_params* p, double* out) {
   return sg::guarded(ctx, [&]() {
@@ -817,7 +811,7 @@ int sg_segment(sg_ctx* ctx, const double* wave, int64_t len, const sg_segment_pa
     HIPCHK(hipSetDevice(ctx->device));
     sg::single_sound(ctx, wave, len, cells, out, [&](const double* d, double* d_o) {
       const int64_t off[2] = {0, cells}, zero = 0;
-      sg::segment_device<double>(*p, plans, d, &zero, 1, d_o, off, ctx->stream, ctx->profiling ? g_seg_ms : nullptr);
+      sg::segment_device<double>(*p, plans, d, &zero, 1, d_o, off, ctx->stream, g_seg_ms.sink(ctx));
     });
     return (int)SG_OK;
   });
@@ -826,25 +820,19 @@ int sg_segment(sg_ctx* ctx, const double* wave, int64_t len, const sg_segment_pa
 int sg_segment_batch(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, const int64_t* lengths, int64_t n_calls,
                      const sg_segment_params* p, double* d_out, const int64_t* out_off) {
   return sg::guarded(ctx, [&]() {
-    if (!ctx || !p || n_calls < 0 || n_calls > 2147483647LL || p->mode != 0 ||
-        (n_calls > 0 && (!d_wave || !offsets || !lengths || !d_out || !out_off)))
-      throw sg::SgError(SG_E_ARG, "sg_segment_batch: bad arguments");
+    if (!ctx || !p || p->mode != 0) sg::bad_arguments("sg_segment_batch");
+    sg::batch_args("sg_segment_batch", n_calls, {d_wave, offsets, lengths, d_out, out_off});
     (void)sg::seg_pars(*p);
     std::vector<sg::SegPlan> plans(n_calls);  // every refusal comes before the first launch
     for (int64_t c = 0; c < n_calls; ++c)
       if (lengths[c] >= 3) plans[c] = sg::seg_plan(*p, lengths[c], true);
     if (n_calls == 0) return (int)SG_OK;
     HIPCHK(hipSetDevice(ctx->device));
-    sg::segment_device<float>(*p, plans, d_wave, offsets, n_calls, d_out, out_off, ctx->stream,
-                              ctx->profiling ? g_seg_ms : nullptr);
+    sg::segment_device<float>(*p, plans, d_wave, offsets, n_calls, d_out, out_off, ctx->stream, g_seg_ms.sink(ctx));
     return (int)SG_OK;
   });
 }
 
-int sg_debug_segment_kernel_ms(double* out) {
-  if (!out) return SG_E_ARG;
-  for (int k = 0; k < sg::kSegStages; ++k) out[k] = g_seg_ms[k];
-  return SG_OK;
-}
+int sg_debug_segment_kernel_ms(double* out) { return g_seg_ms.read(out); }
 
 }  // extern "C"

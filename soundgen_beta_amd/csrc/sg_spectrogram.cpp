@@ -12,6 +12,7 @@
 #include <cmath>
 #include <string>
 
+#include "sg_frame_grid.h"
 #include "sg_rmath.h"
 
 namespace sg {
@@ -72,19 +73,12 @@ SpgSetup spg_setup(const sg_spectrogram_params& p) {
 }
 
 int spg_frames(const SpgSetup& S, int64_t len) {
-  if (len <= 1 || len < S.wl) return 0;
-  // seq(1, max(1, len - wl), by): from + (0:n) by, n = as.integer((to - from) / by + 1e-10)
-  const double to = (double)std::max<int64_t>(1, len - S.wl);
-  const double n = std::floor((to - 1.0) / S.by + 1e-10);
-  if (n + 1 > 2147483647.0) throw SgError(SG_E_UNSUPPORTED, "spectrogram: more than 2^31 frames");
-  return (int)n + 1;
+  const int64_t n = grid_frames(S.by, S.wl, len);
+  if (n > 2147483647LL) throw SgError(SG_E_UNSUPPORTED, "spectrogram: more than 2^31 frames");
+  return (int)n;
 }
 
-int64_t spg_frame_start(const SpgSetup& S, int64_t len, int i) {
-  const double to = (double)std::max<int64_t>(1, len - S.wl);
-  const double v = 1.0 + (double)i * S.by;
-  return (int64_t)std::floor(v < to ? v : to) - 1;  // pmin(x, to); indexing truncates
-}
+int64_t spg_frame_start(const SpgSetup& S, int64_t len, int i) { return grid_frame_start(S.by, S.wl, len, i); }
 
 void spg_list_frames(const SpgSetup& S, int64_t len, int nf, int32_t snd, const char* who, std::vector<SpgFrame>& fr) {
   if ((int64_t)fr.size() + nf > 2147483647LL)
@@ -134,30 +128,16 @@ std::vector<double> spg_window(int wl, int wn) {
 
 }  // namespace sg
 
-namespace {
-thread_local std::string g_size_err;
-}
-
 extern "C" int sg_spectrogram_size(int64_t len, const sg_spectrogram_params* p, int32_t* wl, int32_t* n_fft,
                                    int32_t* bins, int32_t* frames) {
-  if (!p || !wl || !n_fft || !bins || !frames) {
-    g_size_err = "sg_spectrogram_size: bad arguments";
-    return SG_E_ARG;
-  }
-  try {
+  return sg::host_guarded([&]() {
+    if (!p || !wl || !n_fft || !bins || !frames) sg::bad_arguments("sg_spectrogram_size");
     const sg::SpgSetup S = sg::spg_setup(*p);
     *wl = S.wl;
     *n_fft = S.N;
     *bins = S.bins;
     *frames = sg::spg_frames(S, len);
-    return SG_OK;
-  } catch (const sg::SgError& e) {
-    g_size_err = e.what();
-    return e.code;
-  } catch (...) {
-    g_size_err = "out of host memory";
-    return SG_E_NOMEM;
-  }
+  });
 }
 
-extern "C" const char* sg_spectrogram_size_error(void) { return g_size_err.c_str(); }
+extern "C" const char* sg_spectrogram_size_error(void) { return sg::g_host_err.c_str(); }

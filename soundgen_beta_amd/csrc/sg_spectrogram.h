@@ -26,8 +26,8 @@ struct SpgSetup {
   int wn = 6, deriv = 0, processed = 1;
 };
 SpgSetup spg_setup(const sg_spectrogram_params& p);
-// frames of a sound of len samples (0 for len <= 1 or len < wl), and the 0-based
-// first sample of frame i: floor(min(1 + i by, max(1, len - wl))) - 1
+// frames of a sound of len samples (0 for len <= 1 or len < wl; more than 2^31 are refused), and
+// the 0-based first sample of frame i: sg_frame_grid.h's grid at S.by and S.wl
 int spg_frames(const SpgSetup& S, int64_t len);
 int64_t spg_frame_start(const SpgSetup& S, int64_t len, int i);
 // ftwindow_modif(wl, wn) in R's operation order

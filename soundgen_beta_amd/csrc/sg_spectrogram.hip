@@ -450,7 +450,7 @@ __global__ __launch_bounds__(kT) void sg_spg_final(const SpgFrame* __restrict__ 
   }
 }
 
-double g_spg_ms[sg::kSpgStages];  // of the last profiled launch sequence
+sg::StageTimes<sg::kSpgStages> g_spg_ms;  // of the last profiled launch sequence
 
 }  // namespace
 
@@ -673,8 +673,7 @@ int sg_spectrogram(sg_ctx* ctx, const double* wave, int64_t len, const sg_spectr
     sg::single_sound(ctx, wave, len, cells, out, [&](const double* d, double* d_o) {
       const int64_t off = 0;
       int32_t b = 0, f = 0;
-      sg::spectrogram_device<double>(S, d, &off, &len, 1, d_o, &off, &b, &f, ctx->stream,
-                                     ctx->profiling ? g_spg_ms : nullptr);
+      sg::spectrogram_device<double>(S, d, &off, &len, 1, d_o, &off, &b, &f, ctx->stream, g_spg_ms.sink(ctx));
     });
     return SG_OK;
   });
@@ -684,14 +683,13 @@ int sg_spectrogram_batch(sg_ctx* ctx, const float* d_wave, const int64_t* offset
                          int64_t n_calls, const sg_spectrogram_params* p, double* d_out, const int64_t* out_off,
                          int32_t* bins_out, int32_t* frames_out) {
   return guarded(ctx, [&]() {
-    if (!ctx || !p || n_calls < 0 || n_calls > 2147483647LL ||
-        (n_calls > 0 && (!d_wave || !offsets || !lengths || !d_out || !out_off || !bins_out || !frames_out)))
-      throw sg::SgError(SG_E_ARG, "sg_spectrogram_batch: bad arguments");
+    if (!ctx || !p) sg::bad_arguments("sg_spectrogram_batch");
+    sg::batch_args("sg_spectrogram_batch", n_calls, {d_wave, offsets, lengths, d_out, out_off, bins_out, frames_out});
     const sg::SpgSetup S = sg::spg_setup(*p);
     if (n_calls == 0) return SG_OK;
     HIPCHK(hipSetDevice(ctx->device));
     sg::spectrogram_device<float>(S, d_wave, offsets, lengths, n_calls, d_out, out_off, bins_out, frames_out,
-                                  ctx->stream, ctx->profiling ? g_spg_ms : nullptr);
+                                  ctx->stream, g_spg_ms.sink(ctx));
     return SG_OK;
   });
 }
@@ -728,10 +726,6 @@ int sg_debug_fft64(sg_ctx* ctx, int32_t M, int32_t inverse, int32_t nframes, con
   });
 }
 
-int sg_debug_spectrogram_kernel_ms(double* out) {
-  if (!out) return SG_E_ARG;
-  for (int k = 0; k < sg::kSpgStages; ++k) out[k] = g_spg_ms[k];
-  return SG_OK;
-}
+int sg_debug_spectrogram_kernel_ms(double* out) { return g_spg_ms.read(out); }
 
 }  // extern "C"

@@ -122,18 +122,13 @@ void ssm_dct(const SsmSetup& S, std::vector<double>& dct, std::vector<double>& l
 
 extern "C" int sg_ssm_size(int64_t len, const sg_ssm_params* p, int32_t* n_frames, int32_t* n, int32_t* win,
                            int32_t* kernel_size) {
-  if (!p || !n_frames || !n || !win || !kernel_size) return SG_E_ARG;
-  try {
+  return sg::host_guarded([&]() {
+    if (!p || !n_frames || !n || !win || !kernel_size) sg::bad_arguments("sg_ssm_size");
     const sg::SsmSetup S = sg::ssm_setup(*p);
     const sg::SsmDims d = sg::ssm_dims(S, len);
     *n_frames = d.nf;
     *n = (int32_t)d.idx.size();
     *win = d.win;
     *kernel_size = S.K;
-    return SG_OK;
-  } catch (const sg::SgError& e) {
-    return e.code;
-  } catch (...) {
-    return SG_E_NOMEM;
-  }
+  });
 }

@@ -387,7 +387,7 @@ __global__ __launch_bounds__(256) void sg_ssm_out(const SsmSound* __restrict__ s
 }
 
 constexpr int kSsmStages = 7;  // stats, frames, feat, winstat, gram, novelty, out
-double g_ssm_ms[kSsmStages];   // of the last profiled launch sequence (sg_debug_ssm_kernel_ms)
+sg::StageTimes<kSsmStages> g_ssm_ms;  // of the last profiled launch sequence (sg_debug_ssm_kernel_ms)
 constexpr int64_t kMaxCells = (int64_t)1 << 28;  // 2 GiB of fp64 cells per launch sequence
 
 }  // namespace
@@ -603,7 +603,7 @@ int sg_ssm(sg_ctx* ctx, const double* wave, int64_t len, const sg_ssm_params* p,
     const int64_t off = 0;
     int32_t n = 0;
     sg::ssm_device<double>(S, d, &off, &len, 1, &n, novelty_out, &off, ssm_out, &off, ctx->stream,
-                           ctx->profiling ? g_ssm_ms : nullptr);
+                           g_ssm_ms.sink(ctx));
     return SG_OK;
   });
 }
@@ -620,7 +620,7 @@ int sg_ssm_batch(sg_ctx* ctx, const float* d_wave, const int64_t* offsets, const
     const sg::SsmSetup S = sg::ssm_setup(*p);
     if (n_calls == 0) return SG_OK;
     sg::ssm_device<float>(S, d_wave, offsets, lengths, n_calls, n_out, novelty_out, novelty_off, ssm_out, ssm_off,
-                          ctx->stream, ctx->profiling ? g_ssm_ms : nullptr);
+                          ctx->stream, g_ssm_ms.sink(ctx));
     return SG_OK;
   });
 }
@@ -634,10 +634,6 @@ int sg_debug_ssm_gram(sg_ctx* ctx, const double* feat, int32_t L, int32_t n, dou
   });
 }
 
-int sg_debug_ssm_kernel_ms(double* out) {
-  if (!out) return SG_E_ARG;
-  for (int k = 0; k < kSsmStages; ++k) out[k] = g_ssm_ms[k];
-  return SG_OK;
-}
+int sg_debug_ssm_kernel_ms(double* out) { return g_ssm_ms.read(out); }
 
 }  // extern "C"

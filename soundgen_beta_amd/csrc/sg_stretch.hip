@@ -187,8 +187,7 @@ __global__ __launch_bounds__(kT) void sg_str_resample(const T* __restrict__ x, c
   if (active) out[Q.obase + r] = acc;
 }
 
-double g_str_ms[sg::kStrStages];  // of the last profiled launch sequence
-thread_local std::string g_str_size_err;
+sg::StageTimes<sg::kStrStages> g_str_ms;  // of the last profiled launch sequence
 
 struct StrCall {
   int64_t len, out_len;  // as given
@@ -237,7 +236,7 @@ void stretch_device(sg_ctx* ctx, const sg::SpgSetup& S, const T* d_x, const int6
     len_out[(size_t)c] = Q.fin ? Q.out_len : 0;
   }
   const std::vector<int64_t> ends = sg::inv_chunk_ends(need, cap > 0 ? cap : sg::kInvWorkspaceCap);
-  sg::StageClock clk(s, ctx->profiling ? g_str_ms : nullptr, sg::kStrStages);
+  sg::StageClock clk(s, g_str_ms.sink(ctx), sg::kStrStages);
   clk.zero();
   // X, X' and the windowed frames of the largest chunk, once: every chunk reuses them
   int64_t max_in = 0, max_out = 0, max_ws = 0, c0 = 0;
@@ -350,7 +349,7 @@ RsPlan resample_plan(const int64_t* offsets, const int64_t* lengths, const int64
 template <typename T>
 void resample_device(sg_ctx* ctx, const RsPlan& P, const T* d_x, double* d_out) {
   hipStream_t s = ctx->stream;
-  sg::StageClock clk(s, ctx->profiling ? g_str_ms : nullptr, sg::kStrStages);
+  sg::StageClock clk(s, g_str_ms.sink(ctx), sg::kStrStages);
   clk.zero();
   if (P.tiles.empty()) return;
   DevBuf db;
@@ -377,20 +376,17 @@ int sg_time_stretch_batch(sg_ctx* ctx, const void* d_wave, int32_t is_f64, const
   return guarded(ctx, [&]() {
     if (!p) throw sg::SgError(SG_E_ARG, "sg_time_stretch_batch: bad arguments");
     const sg::SpgSetup S = sg::spg_setup(*p);  // spectrogram()'s refusals, before anything else
-    if (n_calls < 0 || n_calls > 2147483647LL || workspace_cap < 0 ||
-        (n_calls > 0 && (!lengths || !out_lengths || !positions || !pos_off || !pos_count)))
-      throw sg::SgError(SG_E_ARG, "sg_time_stretch_batch: bad arguments");
+    if (workspace_cap < 0) sg::bad_arguments("sg_time_stretch_batch");
+    sg::batch_args("sg_time_stretch_batch", n_calls, {lengths, out_lengths, positions, pos_off, pos_count});
     const std::vector<StrCall> calls = str_calls(S, lengths, out_lengths, positions, pos_off, pos_count, n_calls);
-    if (!ctx || (n_calls > 0 && (!d_wave || !offsets || !d_out || !out_off)) || (d_spec && !spec_off))
-      throw sg::SgError(SG_E_ARG, "sg_time_stretch_batch: bad arguments");
+    if (!ctx || (d_spec && !spec_off)) sg::bad_arguments("sg_time_stretch_batch");
+    sg::batch_args("sg_time_stretch_batch", n_calls, {d_wave, offsets, d_out, out_off});
     if (n_calls == 0) return SG_OK;
     HIPCHK(hipSetDevice(ctx->device));
-    if (is_f64)
-      stretch_device<double>(ctx, S, static_cast<const double*>(d_wave), offsets, calls, positions, pos_off, d_out, out_off,
-                             workspace_cap, reinterpret_cast<double2*>(d_spec), spec_off);
-    else
-      stretch_device<float>(ctx, S, static_cast<const float*>(d_wave), offsets, calls, positions, pos_off, d_out, out_off,
-                            workspace_cap, reinterpret_cast<double2*>(d_spec), spec_off);
+    sg::with_samples(is_f64 != 0, d_wave, [&](auto* d_x) {
+      stretch_device(ctx, S, d_x, offsets, calls, positions, pos_off, d_out, out_off, workspace_cap,
+                     reinterpret_cast<double2*>(d_spec), spec_off);
+    });
     return SG_OK;
   });
 }
@@ -398,24 +394,20 @@ int sg_time_stretch_batch(sg_ctx* ctx, const void* d_wave, int32_t is_f64, const
 int sg_resample_batch(sg_ctx* ctx, const void* d_wave, int32_t is_f64, const int64_t* offsets, const int64_t* lengths,
                       int64_t n_calls, const int64_t* up, const int64_t* down, double* d_out, const int64_t* out_off) {
   return guarded(ctx, [&]() {
-    if (n_calls < 0 || n_calls > 2147483647LL || (n_calls > 0 && (!lengths || !up || !down)))
-      throw sg::SgError(SG_E_ARG, "sg_resample_batch: bad arguments");
+    sg::batch_args("sg_resample_batch", n_calls, {lengths, up, down});
     const RsPlan P = resample_plan(offsets, lengths, up, down, out_off, n_calls);  // the refusals, before ctx is looked at
-    if (!ctx || (n_calls > 0 && (!d_wave || !offsets || !d_out || !out_off)))
-      throw sg::SgError(SG_E_ARG, "sg_resample_batch: bad arguments");
+    if (!ctx) sg::bad_arguments("sg_resample_batch");
+    sg::batch_args("sg_resample_batch", n_calls, {d_wave, offsets, d_out, out_off});
     if (n_calls == 0) return SG_OK;
     HIPCHK(hipSetDevice(ctx->device));
-    if (is_f64)
-      resample_device<double>(ctx, P, static_cast<const double*>(d_wave), d_out);
-    else
-      resample_device<float>(ctx, P, static_cast<const float*>(d_wave), d_out);
+    sg::with_samples(is_f64 != 0, d_wave, [&](auto* d_x) { resample_device(ctx, P, d_x, d_out); });
     return SG_OK;
   });
 }
 
 int sg_stretch_size(int64_t len, const sg_spectrogram_params* p, int64_t out_len, int64_t up, int64_t down, int32_t* frames_in,
                     int32_t* frames_out, int64_t* workspace_bytes, int64_t* n_out, int64_t* taps) {
-  try {
+  return sg::host_guarded([&]() {
     if (len < 0) throw sg::SgError(SG_E_ARG, "sg_stretch_size: bad arguments");
     if (p) {
       if (!frames_in || !frames_out || !workspace_bytes) throw sg::SgError(SG_E_ARG, "sg_stretch_size: bad arguments");
@@ -424,29 +416,18 @@ int sg_stretch_size(int64_t len, const sg_spectrogram_params* p, int64_t out_len
       *frames_in = sg::spg_frames(S, len);
       *frames_out = sg::spg_frames(S, out_len);
       *workspace_bytes = sg::str_workspace_bytes(*frames_in, *frames_out, S.wl, S.bins);
-      return SG_OK;
+      return;
     }
     if (!n_out || !taps) throw sg::SgError(SG_E_ARG, "sg_stretch_size: bad arguments");
     const int64_t off = 0;
     const RsPlan P = resample_plan(&off, &len, &up, &down, &off, 1);
     *n_out = P.snds[0].n_out;
     *taps = sg::str_tap_count(sg::StrRatio{P.snds[0].up, P.snds[0].down, P.snds[0].D});
-    return SG_OK;
-  } catch (const sg::SgError& e) {
-    g_str_size_err = e.what();
-    return e.code;
-  } catch (...) {
-    g_str_size_err = "out of host memory";
-    return SG_E_NOMEM;
-  }
+  });
 }
 
-const char* sg_stretch_size_error(void) { return g_str_size_err.c_str(); }
+const char* sg_stretch_size_error(void) { return sg::g_host_err.c_str(); }
 
-int sg_debug_stretch_kernel_ms(double* out) {
-  if (!out) return SG_E_ARG;
-  for (int k = 0; k < sg::kStrStages; ++k) out[k] = g_str_ms[k];
-  return SG_OK;
-}
+int sg_debug_stretch_kernel_ms(double* out) { return g_str_ms.read(out); }
 
 }  // extern "C"

@@ -263,13 +263,12 @@ def _gate_settings(samplingRate, duration, kw):
 
 def formants_size(s, nFormants):
     """sg_formants_size (host only): (order, cols) for repair()'s dict s."""
-    from .analyze import _params, _raise
+    from .analyze import _host_check, _params
     L = native.lib()
     P = _params(s)
     order, cols = C.c_int32(), C.c_int32()
     rc = L.sg_formants_size(C.byref(P), int(nFormants), C.byref(order), C.byref(cols))
-    if rc < 0:
-        _raise(rc, L.sg_analyze_frames_size_error().decode())
+    _host_check(rc)
     return order.value, cols.value
 
 

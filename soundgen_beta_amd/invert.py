@@ -235,8 +235,7 @@ def invert_size(length, samplingRate, rows=0, **kw):
 def _size(L, P, length, rows=0):
     o = [C.c_int32() for _ in range(4)] + [C.c_int64(), C.c_int64()]
     rc = L.sg_invert_size(int(length), C.byref(P), int(rows), *[C.byref(v) for v in o])
-    if rc < 0:
-        raise native.SoundgenError(rc, L.sg_invert_size_error().decode())
+    native.host_check(rc, L.sg_invert_size_error)
     return dict(zip(("wl", "N", "bins", "frames", "samples", "workspace_bytes"), (v.value for v in o)))
 
 

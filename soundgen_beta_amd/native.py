@@ -307,6 +307,21 @@ def check(rc, ctx=None):
     return rc
 
 
+def raise_code(rc, msg, value_error=False):
+    """The return-code policy of the analysis features: SoundgenError(rc, msg), or, for the modules
+    that say so, ValueError for SG_E_ARG (-1)."""
+    if value_error and rc == -1:
+        raise ValueError(msg)
+    raise SoundgenError(rc, msg)
+
+
+def host_check(rc, reader, value_error=False):
+    """Nothing for rc >= 0; otherwise raises with the text that reader() returns (a *_size_error
+    reader after a host-only entry point, sg_last_error behind a context)."""
+    if rc < 0:
+        raise_code(rc, reader().decode(), value_error)
+
+
 class Context:
     """A device context (one HIP stream on one GPU)."""
 

@@ -417,12 +417,6 @@ def _params(samplingRate, windowLength=40, overlap=80, shortestSyl=40, shortestP
                                   int(bool(troughRight)), int(mode), 0, int(workspace_cap))
 
 
-def _raise(rc, msg):
-    if rc == -1:
-        raise ValueError(msg)
-    raise native.SoundgenError(rc, msg)
-
-
 def segment_size_native(length, P):
     """sg_segment_size (host only): dict(log2n, n_env, points, cells) for a sound of `length`
     samples; n_env is the smoothed envelope's length (the raw one's for mode 1)."""
@@ -430,8 +424,7 @@ def segment_size_native(length, P):
     o = [C.c_int32() for _ in range(3)]
     cells = C.c_int64()
     rc = L.sg_segment_size(int(length), C.byref(P), *[C.byref(v) for v in o], C.byref(cells))
-    if rc < 0:
-        _raise(rc, L.sg_segment_size_error().decode())
+    native.host_check(rc, L.sg_segment_size_error, value_error=True)
     return dict(log2n=o[0].value, n_env=o[1].value, points=o[2].value, cells=cells.value)
 
 
@@ -444,8 +437,7 @@ def segment_windows_native(length, P, n):
     i64p = C.POINTER(C.c_int64)
     rc = L.sg_segment_windows(int(length), C.byref(P), first.ctypes.data_as(i64p), cnt.ctypes.data_as(i64p),
                               jump.ctypes.data_as(i64p), n, C.byref(ts))
-    if rc < 0:
-        _raise(rc, L.sg_segment_size_error().decode())
+    native.host_check(rc, L.sg_segment_size_error, value_error=True)
     return first[:n], cnt[:n], jump[:n], ts.value
 
 
@@ -477,8 +469,7 @@ def _detail(h):
 
 
 def _check(rc, ctx):
-    if rc < 0:
-        _raise(rc, native.lib().sg_last_error(ctx).decode())
+    native.host_check(rc, lambda: native.lib().sg_last_error(ctx), value_error=True)
 
 
 def segment(x, samplingRate=None, windowLength=40, overlap=80, shortestSyl=40, shortestPause=40, sylThres=0.9,

@@ -335,8 +335,7 @@ def _params(sr, windowLength, step, overlap, wn, zp, smoothFreq, smoothTime, qTi
 def _size(L, P, length):
     o = [C.c_int32() for _ in range(4)]
     rc = L.sg_spectrogram_size(int(length), C.byref(P), *[C.byref(v) for v in o])
-    if rc < 0:
-        raise native.SoundgenError(rc, L.sg_spectrogram_size_error().decode())
+    native.host_check(rc, L.sg_spectrogram_size_error)
     return tuple(v.value for v in o)
 
 

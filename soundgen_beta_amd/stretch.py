@@ -208,8 +208,7 @@ def shift_pitch_numpy(x, samplingRate, multiplier, dtype=np.float64, **kw):
 
 # ------------------------------------------------------------------ on the GPU (sg_stretch.hip)
 def _err(L, rc):
-    if rc < 0:
-        raise native.SoundgenError(rc, L.sg_stretch_size_error().decode())
+    native.host_check(rc, L.sg_stretch_size_error)
 
 
 def stretch_size(length, samplingRate=None, out_length=None, up=None, down=None, **kw):

@@ -27,11 +27,11 @@ int main() {
     const double bys[6] = {0.4, 1.0, 3.7, 20.8, (double)wl, (double)wl + 5};
     for (long long len : lens)
       for (double by : bys) {
-        const int64_t F = sg::inv_frames(by, wl, len);
+        const int64_t F = sg::grid_frames(by, wl, len);
         if (F < 1) return fail("frames", wl, len, by, 0, F, 1);
         std::vector<int64_t> s((size_t)F);
         for (int64_t i = 0; i < F; ++i) {
-          s[(size_t)i] = sg::inv_frame_start(by, wl, len, i);
+          s[(size_t)i] = sg::grid_frame_start(by, wl, len, i);
           if (s[(size_t)i] < 0 || s[(size_t)i] + wl > len) return fail("start", wl, len, by, i, s[(size_t)i], len);
           if (i > 0 && s[(size_t)i] < s[(size_t)i - 1]) return fail("order", wl, len, by, i, s[(size_t)i], s[(size_t)i - 1]);
         }
@@ -58,13 +58,13 @@ int main() {
       }
   }
   // by hand. len = wl: to = max(1, 0) = 1, one frame at 0. len = wl + 1: the same, sample wl uncovered.
-  if (sg::inv_frames(3.7, 44, 44) != 1 || sg::inv_frames(3.7, 44, 45) != 1 || sg::inv_frame_start(3.7, 44, 45, 0) != 0) return 2;
-  if (sg::inv_frames(3.7, 44, 43) != 0 || sg::inv_frames(1.0, 8, 1) != 0) return 2;
+  if (sg::grid_frames(3.7, 44, 44) != 1 || sg::grid_frames(3.7, 44, 45) != 1 || sg::grid_frame_start(3.7, 44, 45, 0) != 0) return 2;
+  if (sg::grid_frames(3.7, 44, 43) != 0 || sg::grid_frames(1.0, 8, 1) != 0) return 2;
   // len = wl + 7: to = 7; by = 1: floor(6 / 1) + 1 = 7 frames at 0 .. 6; by = 3.7: floor(6 / 3.7) + 1 = 2 at 0 and floor(4.7) - 1 = 3
-  if (sg::inv_frames(1.0, 44, 51) != 7 || sg::inv_frame_start(1.0, 44, 51, 6) != 6) return 3;
-  if (sg::inv_frames(3.7, 44, 51) != 2 || sg::inv_frame_start(3.7, 44, 51, 1) != 3) return 3;
+  if (sg::grid_frames(1.0, 44, 51) != 7 || sg::grid_frame_start(1.0, 44, 51, 6) != 6) return 3;
+  if (sg::grid_frames(3.7, 44, 51) != 2 || sg::grid_frame_start(3.7, 44, 51, 1) != 3) return 3;
   // wl = 44, len = 1000, by = 20.8: to = 956, floor(955 / 20.8 = 45.9) + 1 = 46 frames; the last at floor(1 + 45 * 20.8 = 937) - 1
-  if (sg::inv_frames(20.8, 44, 1000) != 46 || sg::inv_frame_start(20.8, 44, 1000, 45) != 936) return 4;
+  if (sg::grid_frames(20.8, 44, 1000) != 46 || sg::grid_frame_start(20.8, 44, 1000, 45) != 936) return 4;
   // zp = 64 on wl = 44: pad 10, N = 64, 32 bins: 33 complex bins (528 B), 44 samples (352 B), two sums (16 B) per frame
   if (sg::inv_workspace_bytes(46, 44, 32) != 46 * 896 || sg::inv_workspace_bytes(0, 44, 32) != 0) return 5;
   if (!sg::inv_rows_ok(32, 32) || !sg::inv_rows_ok(33, 32) || sg::inv_rows_ok(34, 32) || sg::inv_rows_ok(31, 32)) return 5;

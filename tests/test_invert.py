@@ -142,9 +142,22 @@ def test_coverage_header_on_the_host_equals_brute_force(tmp_path):
         assert r.stdout.split()[:2] == ["ok", "72"]
 
 
+# the frame grid alone (sizes only): a step under one point (0.32: equal consecutive starts), and a
+# length whose last start is clamped at len - wl (1 + 25 * 17.6 = 441.00000000000006 > 537 - 96);
+# the fractional step is w44_fractional's
+GRID_CASES = {
+    "w44_equal_starts": dict(n=300, kw=dict(windowLength=2.75, step=0.02)),
+    "w96_clamped": dict(n=537, kw=dict(windowLength=6, step=1.1)),
+}
+
+
 def test_header_and_restatement_agree_on_frames():
     """sg_invert_size (host only) against the restatement's frame count and sizes."""
-    for name, c in CASES.items():
+    st = IV._starts(300, SR, 44, 0.02)
+    assert len(st) == 797 and np.all(np.diff(st) >= 0) and (np.diff(st) == 0).sum() > 500
+    st = IV._starts(537, SR, 96, 1.1)
+    assert st[-1] == 537 - 96 - 1 and 1.0 + (len(st) - 1) * (1.1 / 1000 * SR) > 537 - 96
+    for name, c in dict(CASES, **GRID_CASES).items():
         z = IV.invert_size(c["n"], SR, **c["kw"])
         wl, pad, N, starts, _ = IV._setup(c["n"], SR, IV._args(c["kw"]), np.float64)
         assert (z["wl"], z["N"], z["bins"], z["frames"], z["samples"]) == (wl, N, N // 2, len(starts), c["n"]), name
@@ -218,6 +231,18 @@ def test_own_refusals_without_a_context():
         IV.invert_spectrogram_numpy(-np.ones((48, 3)), SR, windowLength=6)
     with pytest.raises(ValueError):
         IV.istft_numpy(np.ones((50, 3)), SR, windowLength=6)
+
+
+def test_size_error_text_lasts_until_the_next_host_only_call():
+    """The readers of the host-only entry points share one text per thread: a refused sg_invert_size
+    leaves its text, and the next host-only call (a sg_spectrogram_size that succeeds) clears it."""
+    L = native.lib()
+    with pytest.raises(native.SoundgenError):
+        IV.invert_size(1000, SR, windowLength=4.7)
+    text = L.sg_invert_size_error().decode()
+    assert "37" in text and text.startswith("spectrogram: a frame of")
+    assert SP.spectrogram_size_native(1000, SR, windowLength=6)[0] == 96
+    assert L.sg_invert_size_error() == b"" and L.sg_spectrogram_size_error() == b""
 
 
 # ---- GPU -------------------------------------------------------------------------------------
